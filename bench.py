@@ -17,6 +17,9 @@ aggregate.  Prints ONE JSON line on rank 0.
 --scaling strong: the fixed-size job instead -- ONE such sequence and 10 M pairs whatever N is, its blocks split over the N ranks
 by expected pairs (sharding.block_weights); the line says "scaling": "strong".  Under --gpus N > 1 the default (weak) line also
 carries a `strong_scaling` leg measured after the headline's timed region, so that one driver run records both kinds.
+
+--dump-outputs DIR writes what the last timed step computed (calls, and a seeded sample and MiB sums of both FASTQ texts; StepOutputs) as .npy files; the inputs
+are generated from fixed seeds, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import glob
@@ -283,6 +286,74 @@ def committed_counters(tiles=1):
         return None
 
 
+DUMP_WINDOWS, DUMP_WIDTH, MIB = 1024, 4096, 1 << 20      # --dump-outputs: 2 files x 1024 x 4096 sampled bytes as float32 = 32 MiB, plus tens of kB
+
+
+def _take(text, idx):
+    """bytes of a FASTQ text (numpy on the host, torch on the device) at int64 positions, as a numpy uint8 array"""
+    if isinstance(text, np.ndarray):
+        return text[idx]
+    import torch
+    return text[torch.from_numpy(idx).to(text.device)].cpu().numpy()
+
+
+def _mib_sums(text):
+    """byte sums of every MiB of a FASTQ text (the last one shorter), summed where the text is, 256 MiB at a time"""
+    out = [np.zeros(0, np.int64)]
+    for lo in range(0, len(text), 256 * MIB):
+        part = text[lo:lo + 256 * MIB]
+        rows = len(part) // MIB
+        for p in [part[:rows * MIB].reshape(rows, MIB)] + ([part[rows * MIB:].reshape(1, -1)] if len(part) % MIB else []):
+            if isinstance(p, np.ndarray):
+                out.append(p.sum(1, dtype=np.int64))
+            else:
+                import torch
+                out.append(p.sum(1, dtype=torch.int64).cpu().numpy())
+    return np.concatenate(out)
+
+
+class StepOutputs:
+    """--dump-outputs DIR: what the timed path hands its caller in the last timed step, for comparing two builds output for output on the same seeded inputs.
+    calls.npy (float64, one row per rsq_sim_pairs call of the step): pairs, bytes of FASTQ file 1, bytes of file 2.  Per file f in 1, 2:
+    fastq<f>_sample.npy (float32): the text's bytes in DUMP_WIDTH-byte windows at seeded offsets (a call's text no longer than its windows is kept whole),
+    fastq<f>_offsets.npy (float64): where each window starts in the step's text, fastq<f>_mib_sums.npy (float64): byte sums of every MiB of each call's
+    whole text, in call order.
+    Ranks of a multi-GPU run write rank<r>_<name>.npy and share the windows."""
+
+    def __init__(self, seed, n_calls, rank=0, world=1):
+        self.seed, self.rank, self.world = seed, rank, world
+        self.windows = max(1, DUMP_WINDOWS // (n_calls * world))
+        self.calls, self.at = [], [0, 0]
+        self.sample, self.offsets, self.sums = ([], []), ([], []), ([], [])
+
+    def add(self, n, text1, text2):
+        """one call's pairs and the two texts (numpy or torch uint8 of exactly the call's length)"""
+        self.calls.append((n, len(text1), len(text2)))
+        for f, text in enumerate((text1, text2)):
+            length = len(text)
+            if length <= self.windows * DUMP_WIDTH:
+                starts, idx = np.zeros(min(length, 1), np.int64), np.arange(length, dtype=np.int64)
+            else:
+                rng = np.random.default_rng([self.seed, self.rank, len(self.calls), f])
+                starts = np.sort(rng.integers(0, length - DUMP_WIDTH + 1, self.windows))
+                idx = (starts[:, None] + np.arange(DUMP_WIDTH)).reshape(-1)
+            self.sample[f].append(_take(text, idx))
+            self.offsets[f].append(starts + self.at[f])
+            self.sums[f].append(_mib_sums(text))
+            self.at[f] += length
+
+    def write(self, directory):
+        os.makedirs(directory, exist_ok=True)
+        prefix = f"rank{self.rank}_" if self.world > 1 else ""
+        arrays = {"calls": np.asarray(self.calls, np.float64).reshape(-1, 3)}
+        for f in (0, 1):
+            arrays[f"fastq{f + 1}_sample"] = np.concatenate(self.sample[f]).astype(np.float32)
+            arrays[f"fastq{f + 1}_offsets"] = np.concatenate(self.offsets[f]).astype(np.float64)
+            arrays[f"fastq{f + 1}_mib_sums"] = np.concatenate(self.sums[f]).astype(np.float64)
+        for name, a in arrays.items():
+            np.save(os.path.join(directory, prefix + name + ".npy"), a)
+
+
 class TorchBuffer:
     """device memory from torch (uint8) with the two attributes api.Simulator.pairs_device reads"""
 
@@ -470,9 +541,11 @@ class PairsJob:
             self.need1, self.need2 = max(self.need1, l1), max(self.need2, l2)
         self.bufs = [(TorchBuffer(torch, self.need1 + 4096, dev), TorchBuffer(torch, self.need2 + 4096, dev)) for _ in range(2)]
 
-    def step(self):
+    def step(self, keep=None):
+        """one pass over the rank's batches; `keep` (a StepOutputs) takes every call's output -- rsq_sim_pairs returns with the text complete -- and the
+        seconds it spends doing so are returned, to come off the timed window"""
         pairs = nbytes = launches = 0
-        fill_ms = 0.0
+        fill_ms = kept_s = 0.0
         for lo, hi in self.batches:
             n, l1, l2, rc = self.sim.pairs_device(lo, hi, self.bufs[0][0], self.bufs[0][1])
             if rc != api.RSQ_OK:
@@ -482,28 +555,34 @@ class PairsJob:
             if n:
                 fill_ms += self.sim.last_kernel_ms("fill_reads")              # summed over the call's launches (pipelined sub-ranges)
                 launches += self.sim.last_kernel_launches("fill_reads")
-        return pairs, nbytes, fill_ms, launches
+            if keep is not None:
+                t = time.perf_counter()
+                keep.add(n, self.bufs[0][0].t[:l1], self.bufs[0][1].t[:l2])
+                kept_s += time.perf_counter() - t
+        return pairs, nbytes, fill_ms, launches, kept_s
 
     def sync(self):
         self.torch.cuda.synchronize()
         if self.dist is not None:
             self.dist.barrier()
 
-    def measure(self, steps, warmup):
+    def measure(self, steps, warmup, keep=None):
+        """`keep`: a StepOutputs that receives the output of the last timed step"""
         for _ in range(warmup):
             self.step()
         self.sync()
         t0 = time.perf_counter()
         pairs = nbytes = launches = 0
-        fill_ms = 0.0
-        for _ in range(steps):
-            p, b, f, n_launch = self.step()
+        fill_ms = kept_s = 0.0
+        for i in range(steps):
+            p, b, f, n_launch, k = self.step(keep if i == steps - 1 else None)
             pairs += p
             nbytes += b
             fill_ms += f
             launches += n_launch
+            kept_s += k
         self.sync()
-        return {"pairs": pairs, "nbytes": nbytes, "fill_ms": fill_ms, "launches": launches, "elapsed": time.perf_counter() - t0}
+        return {"pairs": pairs, "nbytes": nbytes, "fill_ms": fill_ms, "launches": launches, "elapsed": time.perf_counter() - t0 - kept_s}
 
     def close(self):
         self.bufs = None
@@ -581,13 +660,20 @@ def main_emulated(args, rank, world):
     my_lo, my_hi = sharding.partition_blocks(info["total_blocks"], world, weights)[rank]
     batches = sharding.batches(my_lo, my_hi, args.batch_blocks)
 
-    def step():
+    keep = StepOutputs(args.seed, len(batches), rank, world) if args.dump_outputs else None
+
+    def step(keep=None):
         pairs = nbytes = 0
+        kept_s = 0.0
         for lo, hi in batches:
             fr, r1, r2 = sim.pairs(lo, hi)
             pairs += len(fr)
             nbytes += len(r1) + len(r2)
-        return pairs, nbytes
+            if keep is not None:
+                t = time.perf_counter()
+                keep.add(len(fr), np.frombuffer(r1, np.uint8), np.frombuffer(r2, np.uint8))
+                kept_s += time.perf_counter() - t
+        return pairs, nbytes, kept_s
 
     def sync():
         if dist is not None:
@@ -598,12 +684,16 @@ def main_emulated(args, rank, world):
     sync()
     t0 = time.perf_counter()
     pairs = nbytes = 0
-    for _ in range(args.steps):
-        p, b = step()
+    kept_s = 0.0
+    for i in range(args.steps):
+        p, b, k = step(keep if i == args.steps - 1 else None)
         pairs += p
         nbytes += b
+        kept_s += k
     sync()
-    elapsed = time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0 - kept_s
+    if keep is not None:
+        keep.write(args.dump_outputs)
     per_rank = rank_times(dist, "cpu", elapsed, args.steps, world)
     total_pairs, total_bytes, elapsed = sharding.job_totals(dist, "cpu", pairs, nbytes, elapsed)
     sim.close()
@@ -645,7 +735,11 @@ def main():
     ap.add_argument("--other-configs", default="2,3,4", help="which of configs[2], [3], [4] the leg runs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-delivery", action="store_true", help="skip the value_to_host leg (it is skipped anyway with more than one GPU: every rank would pin 15 GB of host memory)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32 / float64, "
+                    "about 34 MB in all: see StepOutputs), outside the timed window")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.lib:
         api.use_library(args.lib)
@@ -695,7 +789,10 @@ def main():
     job = PairsJob(torch, dist, dev, rank, world, ppath, fpath, args.seed, args.pairs * n_seqs, [args.genome] * n_seqs, args.batch_blocks)
     sim, info, prep_s, my_lo, my_hi, bufs, need1, need2 = job.sim, job.info, job.prep_s, job.my_lo, job.my_hi, job.bufs, job.need1, job.need2
     sync = job.sync
-    m = job.measure(args.steps, args.warmup)
+    keep = StepOutputs(args.seed, len(job.batches), rank, world) if args.dump_outputs else None
+    m = job.measure(args.steps, args.warmup, keep)
+    if keep is not None:
+        keep.write(args.dump_outputs)
     pairs, nbytes, fill_ms, fill_launches, elapsed = m["pairs"], m["nbytes"], m["fill_ms"], m["launches"], m["elapsed"]
     kernel_ms = {k: sim.last_kernel_ms(k) for k in ("sieve", "sieve_screen", "sieve_emit", "fill_reads", "format_write", "scan")}
     plan = sim.fill_plan()

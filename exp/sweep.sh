@@ -1,4 +1,4 @@
-cd $GRAFT_REPO_ROOT
+cd "$(dirname "$0")/.."
 for lib in exp/lib_*.so; do
 timeout 300 python bench.py --lib $PWD/$lib --steps 2 --warmup 1 --no-cpu-baseline > /tmp/b.json 2>/tmp/b.err || tail -2 /tmp/b.err
 python -c "

@@ -1,4 +1,4 @@
-cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
+export TMPDIR=/tmp; cd "$(dirname "$0")/.."
 rm -rf gpurun_out/trace
 rocprofv3 --kernel-trace --memory-copy-trace -d gpurun_out/trace -o t --output-format csv -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
 ls -la gpurun_out/trace

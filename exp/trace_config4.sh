@@ -1,4 +1,4 @@
-cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
+export TMPDIR=/tmp; cd "$(dirname "$0")/.."
 rm -rf gpurun_out/trace4
 rocprofv3 --kernel-trace --stats -d gpurun_out/trace4 -o t --output-format csv -- python tools/run_config4.py > /dev/null 2>&1
 python - <<'PY'

@@ -3,7 +3,7 @@
 # passes (each counter group in its own run, no tracing domains combined with --pmc).  Run on the GPU box from the repo
 # root: bash profiles/collect.sh <tag>; results land in gpurun_out/<tag>/ and are summarised into profiles/<tag>_*.
 tag=${1:-r01}; shift          # further arguments go to every bench.py command (e.g. --tiles 96)
-cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
+export TMPDIR=/tmp; cd "$(dirname "$0")/.."
 out=gpurun_out/$tag; rm -rf $out; mkdir -p $out
 # --no-host-delivery: the value_to_host leg launches the same kernels on smaller batches, which would mix into the per-kernel averages
 B="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-host-delivery --no-other-configs $*"

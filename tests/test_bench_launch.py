@@ -7,6 +7,8 @@ import pathlib
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 
 
@@ -40,6 +42,29 @@ def test_bare_gpus_2_starts_two_ranks():
 def test_one_rank_with_a_process_group():
     out = _line(_bench("--gpus", "1", "--emulate", "--backend", "gloo", "--dist-single", "--steps", "1", "--warmup", "0"))
     assert out["n_gpus"] == 1 and len(out["ms_per_step_per_rank"]) == 1
+
+
+def test_dump_outputs_of_the_last_step(tmp_path):
+    """--dump-outputs: the last timed step's calls and FASTQ text as float32 / float64 arrays under 64 MB, the same from run to run with the same arguments"""
+    flags = ("--gpus", "1", "--emulate", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--batch-blocks", "2")
+    line = _line(_bench(*flags, "--dump-outputs", str(tmp_path / "a")))
+    _line(_bench(*flags, "--dump-outputs", str(tmp_path / "b")))
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "b").iterdir())
+    a = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert {"calls", "fastq1_sample", "fastq2_sample", "fastq1_offsets", "fastq2_offsets", "fastq1_mib_sums", "fastq2_mib_sums"} <= set(a)
+    for n in names:
+        assert a[n[:-4]].dtype in (np.float32, np.float64) and np.array_equal(a[n[:-4]], np.load(tmp_path / "b" / n))
+    assert sum(x.nbytes for x in a.values()) <= 64e6
+    calls = a["calls"]
+    blocks = line["config"]["total_blocks"]
+    assert calls.shape == ((blocks + 1) // 2, 3) and calls[:, 0].sum() == line["config"]["pairs_per_step"]
+    assert calls[:, 1:].sum() == line["config"]["fastq_bytes_per_step"]
+    for f in (1, 2):                                                   # the emulation's texts are small: kept whole, one stretch per call
+        assert a[f"fastq{f}_sample"].size == calls[:, f].sum() and a[f"fastq{f}_sample"].sum() == a[f"fastq{f}_mib_sums"].sum()
+        assert np.array_equal(a[f"fastq{f}_offsets"], np.concatenate([[0], np.cumsum(calls[:-1, f])])[calls[:, f] > 0])
+        assert a[f"fastq{f}_sample"][0] == ord("@")
 
 
 def test_world_size_that_is_not_gpus_is_refused():

@@ -1,7 +1,7 @@
 #!/bin/bash
 # the configurations that run the read kernels, for comparing builds (e.g. RSQ_FILL_BLOCK=1024 against 768): bash tools/gpu_block_compare.sh <tag>
 tag=${1:-blk}; out=gpurun_out/$tag; mkdir -p $out
-cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
+export TMPDIR=/tmp; cd "$(dirname "$0")/.."
 line() { python -c "
 import sys,json,re
 m=re.findall(r'\{\"metric\".*\}', sys.stdin.read())

@@ -1,4 +1,4 @@
-cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
+export TMPDIR=/tmp; cd "$(dirname "$0")/.."
 out=gpurun_out/pmc_rec; rm -rf $out; mkdir -p $out
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE SQ_INSTS_VMEM_RD -d $out/a -o p --output-format csv -- python tools/bench_error_model.py 8000000 > /dev/null 2>&1
 rocprofv3 --pmc TA_BUSY_avr SQ_WAIT_INST_ANY SQ_WAVES GRBM_GUI_ACTIVE TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum -d $out/b -o p --output-format csv -- python tools/bench_error_model.py 8000000 > /dev/null 2>&1

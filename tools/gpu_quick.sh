@@ -1,7 +1,7 @@
 #!/bin/bash
 # a bench line and the read kernel's VALU / LDS counters of the current build: bash tools/gpu_quick.sh <tag> [bench.py flags]
 tag=${1:-quick}; shift
-cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
+export TMPDIR=/tmp; cd "$(dirname "$0")/.."
 out=gpurun_out/$tag; rm -rf $out; mkdir -p $out
 B="python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-host-delivery --no-other-configs $*"
 timeout 600 $B > $out/bench.json 2> $out/bench.err

@@ -1,6 +1,6 @@
 #!/bin/bash
 # round 4: N writers behind one GPU into one pair of files, buffered / direct, against a pair per process; tmpfs and the box's disk-backed file system
-cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
+export TMPDIR=/tmp; cd "$(dirname "$0")/.."
 out=gpurun_out/r04w; rm -rf $out; mkdir -p $out
 mkdir -p /var/tmp/rsq_w
 ( df -T / /tmp /var/tmp /dev/shm; cat /proc/mounts | grep -E " / | /tmp | /var" ) > $out/file_systems.txt 2>&1

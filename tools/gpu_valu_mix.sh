@@ -1,4 +1,4 @@
-cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
+export TMPDIR=/tmp; cd "$(dirname "$0")/.."
 out=gpurun_out/valu_mix; rm -rf $out; mkdir -p $out
 P="python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-host-delivery"
 rocprofv3 -L 2>/dev/null | grep -o "SQ_INSTS_VALU[A-Z0-9_]*\|SQ_INSTS_SALU\|SQ_INSTS_SMEM\|SQ_INST_CYCLES_VMEM[A-Z_]*\|SQ_INSTS_[A-Z0-9_]*" | sort -u > $out/counters.txt

@@ -1,5 +1,5 @@
 import ctypes as C, json, os, sys, tempfile, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
 from reseq_amd import api, workloads
 tmp = tempfile.mkdtemp(prefix="rsq_small_")

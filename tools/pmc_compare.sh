@@ -1,7 +1,7 @@
 #!/bin/bash
 # Counters of the read kernel for several bench.py variants side by side (each counter group in its own run; no tracing domains with --pmc).
 #   bash tools/pmc_compare.sh <outdir> "<name>:<bench args>" ...
-cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
+export TMPDIR=/tmp; cd "$(dirname "$0")/.."
 out=$1; shift; mkdir -p $out
 for spec in "$@"; do
   name=${spec%%:*}; args=${spec#*:}

@@ -2,7 +2,8 @@
 """Randomised parity stress of the seqToIllumina path (rsq_sim_error_model against the oracle): 30 record sets of random size, template
 length, seed and profile.  Run on a GPU box."""
 import sys, pathlib, tempfile
-sys.path.insert(0,'/root/repo/tests'); sys.path.insert(0,'/root/repo')
+ROOT = pathlib.Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT / 'tests')); sys.path.insert(0, str(ROOT))
 import numpy as np
 import parity_cases as P
 from backends import GpuBackend

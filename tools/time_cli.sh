@@ -1,7 +1,7 @@
 #!/bin/bash
 # end-to-end time of the command line on the bench workload (E. coli-sized reference, 10 M pairs), FASTQ written to /dev/shm
 set -e
-cd $GRAFT_REPO_ROOT
+cd "$(dirname "$0")/.."
 python - <<'PY'
 import sys; sys.path.insert(0, '.')
 from reseq_amd import synth
