@@ -15,8 +15,14 @@ data-path collective -- torch.distributed (RCCL) carries the timing barrier and 
 aggregate.  Prints ONE JSON line on rank 0.
 
 --scaling strong: the fixed-size job instead -- ONE such sequence and 10 M pairs whatever N is, its blocks split over the N ranks
-by expected pairs (sharding.block_weights); the line says "scaling": "strong".  Under --gpus N > 1 the default (weak) line also
+by expected pairs (sharding.block_weights); the line says "scaling": "strong".  Under --gpus N > 1 and --full the weak line also
 carries a `strong_scaling` leg measured after the headline's timed region, so that one driver run records both kinds.
+
+A plain run does what the headline needs and nothing else: the synthetic inputs, the job's setup (loading, pre-passes, the read kernel compiled
+for the profile, buffers sized), --warmup untimed and --steps timed steps, --dump-outputs, the line.  --full adds what is measured beside the
+headline: on one GPU the CPU oracle's rates and a parity sample against it (`cpu_baseline`, `parity_sample`; the oracle runs first, before the
+device is opened), the same steps delivered to host memory (`value_to_host`) and BASELINE.json's configs[2]-[4] (`other_configs`); under
+--gpus N > 1 the `strong_scaling` leg.  The --no-... switches leave one of them out of a --full run.
 
 --dump-outputs DIR writes what the last timed step computed (calls, and a seeded sample and MiB sums of both FASTQ texts; StepOutputs) as .npy files; the inputs
 are generated from fixed seeds, so two builds run with the same arguments can be compared output for output.
@@ -730,11 +736,13 @@ def main():
                     "(tests/hostemu, the TINY profile, a few thousand pairs) in the device's place -- what the CPU suite runs with --gpus 2 --backend gloo")
     ap.add_argument("--dist-single", action="store_true", help="initialise torch.distributed although there is one rank (the RCCL calls of the N-rank path on one GPU)")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak", help="weak (default): N sequences and N x --pairs on N GPUs; strong: ONE sequence and --pairs pairs split over the N GPUs")
-    ap.add_argument("--no-strong-leg", action="store_true", help="with --gpus N > 1 and weak scaling: skip the extra fixed-size measurement (`strong_scaling` in the line)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the `other_configs` leg (BASELINE.json's configs[2]-[4] on one GPU after the headline; about two minutes)")
+    ap.add_argument("--full", action="store_true", help="also measure what is beside the headline (one GPU: cpu_baseline + parity_sample, value_to_host, other_configs; "
+                    "--gpus N > 1: strong_scaling); a plain run does only the headline's setup, warm-up, timed steps and --dump-outputs")
+    ap.add_argument("--no-strong-leg", action="store_true", help="with --full, --gpus N > 1 and weak scaling: skip the extra fixed-size measurement (`strong_scaling` in the line)")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the `other_configs` leg (BASELINE.json's configs[2]-[4] on one GPU after the headline; about two minutes)")
     ap.add_argument("--other-configs", default="2,3,4", help="which of configs[2], [3], [4] the leg runs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-delivery", action="store_true", help="skip the value_to_host leg (it is skipped anyway with more than one GPU: every rank would pin 15 GB of host memory)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle's `cpu_baseline` and the `parity_sample` against it")
+    ap.add_argument("--no-host-delivery", action="store_true", help="with --full: skip the value_to_host leg (it is skipped anyway with more than one GPU: every rank would pin 15 GB of host memory)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32 / float64, "
                     "about 34 MB in all: see StepOutputs), outside the timed window")
     args = ap.parse_args()
@@ -759,14 +767,14 @@ def main():
         seqs += synth.make_reference(2 + i, [args.genome], gc=args.gc, names=[f"synthEcoli{i} len={args.genome}"])
     synth.write_fasta(fpath, seqs)
     ppath1, fpath1 = ppath, fpath
-    if n_seqs > 1 and not args.no_strong_leg:        # the fixed-size job of the strong-scaling leg: the first sequence alone
+    if args.full and n_seqs > 1 and not args.no_strong_leg:        # the fixed-size job of the strong-scaling leg: the first sequence alone
         ppath1, fpath1 = os.path.join(tmp, "p0_one.rsqp"), os.path.join(tmp, "ref_one.fa")
         synth.write_profile(ppath1, synth.make_profile(cfg, seed=103741084, n_ref_seqs=1))
         synth.write_fasta(fpath1, seqs[:1])
 
-    # the CPU oracle first (rank 0 of a single-GPU run only): its worker processes are forked before any device context exists
+    # the CPU oracle first (--full, rank 0 of a single-GPU run only): its worker processes are forked before any device context exists
     baseline = oracle_text = None
-    if not args.no_cpu_baseline and world == 1 and not args.dist_single and "TORCHELASTIC_RUN_ID" not in os.environ:
+    if args.full and not args.no_cpu_baseline and world == 1 and not args.dist_single and "TORCHELASTIC_RUN_ID" not in os.environ:
         baseline, oracle_text = cpu_baseline(ppath, seqs, args.seed)
 
     import torch
@@ -809,7 +817,7 @@ def main():
     # the fixed-size job beside the weak one (N > 1): ONE sequence and --pairs pairs, its blocks split over the ranks by expected pairs -- BASELINE's configs[3] / [4]
     # are of this kind (one genome sharded over 8).  After the headline's timed region, with its own barriers and the same max-over-ranks timing.
     strong = None
-    if world > 1 and args.scaling == "weak" and not args.no_strong_leg:
+    if args.full and world > 1 and args.scaling == "weak" and not args.no_strong_leg:
         fixed = PairsJob(torch, dist, dev, rank, world, ppath1, fpath1, args.seed, args.pairs, [args.genome], args.batch_blocks)
         ms = fixed.measure(args.steps, 1)
         s_rank = rank_times(dist, xdev, ms["elapsed"], args.steps, world)
@@ -822,7 +830,7 @@ def main():
     # the same steps delivered to the host (what Simulator::Flush hands to the writer, Simulator.cpp:150-182): generation of batch k+1
     # overlaps the copy of batch k into page-locked host memory on a second stream
     to_host = None
-    if not args.no_host_delivery and world == 1:
+    if args.full and not args.no_host_delivery and world == 1:
         host = [(torch.empty(need1 + 4096, dtype=torch.uint8, pin_memory=True), torch.empty(need2 + 4096, dtype=torch.uint8, pin_memory=True)) for _ in range(2)]
         copy_stream = torch.cuda.Stream(device=dev)
         done = [torch.cuda.Event(), torch.cuda.Event()]
@@ -911,7 +919,7 @@ def main():
                    "overlapping the generation of batch k+1 (the link binds: 7.5 GB per step and GPU)"}
 
     others = None
-    if world == 1 and not args.no_other_configs and args.tiles <= 1:
+    if args.full and world == 1 and not args.no_other_configs and args.tiles <= 1:
         job.close()                                                        # the headline's buffers go back first
         sim = None
         others = other_configs(local_rank, args.seed, tuple(args.other_configs.split(",")))

@@ -1,6 +1,7 @@
 """bench.py's launch path on CPU: `--gpus N` started bare must start N ranks itself (the driver's multi-GPU command is `bench.py --gpus N` under
 torch.distributed.run; a bare `python bench.py --gpus 2` used to run ONE rank and print n_gpus 1), and a launcher's world size that is not --gpus is refused.
-The ranks run the host emulation of the kernels over gloo (--emulate: a test switch whose line says so)."""
+The ranks run the host emulation of the kernels over gloo (--emulate: a test switch whose line says so).  On the device (-m gpu): a run without --full
+measures the headline alone."""
 import json
 import os
 import pathlib
@@ -8,6 +9,7 @@ import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 
@@ -72,3 +74,13 @@ def test_world_size_that_is_not_gpus_is_refused():
     assert r.returncode != 0 and "--gpus 2" in r.stderr and "1 rank" in r.stderr
     r = _bench("--gpus", "2", "--backend", "gloo", env={"RANK": "0", "LOCAL_RANK": "0", "WORLD_SIZE": "2"}, check=False)
     assert r.returncode != 0 and "gloo" in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_alone(tmp_path):
+    """without --full the line carries the headline and none of the legs beside it (CPU oracle, parity sample, host delivery, other configs)"""
+    line = _line(_bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--pairs", "1000000", env={"XDG_CACHE_HOME": str(tmp_path)}))
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line)
+    assert line["n_gpus"] == 1 and line["steps"] == 2 and line["value"] > 0 and line["ms_per_step"] > 0 and line["roofline"]["frac"] > 0
+    assert 0.9e6 < line["config"]["pairs_per_step_per_gpu"] < 1.1e6
+    assert not {"cpu_baseline", "parity_sample", "kmer_kl", "value_to_host", "other_configs", "strong_scaling"} & set(line)

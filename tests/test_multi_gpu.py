@@ -329,7 +329,7 @@ def test_only_one_rank_of_a_host_opens_the_reference(mode, job):
 # ------------------------------------------------------------------------------------------------------------------------ (v)
 @pytest.mark.timeout(1800)
 def test_bench_on_two_ranks(mode, job):
-    flags = ["--gpus", "2", "--steps", "2", "--warmup", "1"] + (["--backend", "gloo", "--emulate"] if mode == "gloo" else ["--pairs", "1000000", "--no-cpu-baseline"])
+    flags = ["--gpus", "2", "--steps", "2", "--warmup", "1"] + (["--backend", "gloo", "--emulate"] if mode == "gloo" else ["--pairs", "1000000", "--full", "--no-cpu-baseline"])
     if mode == "shared":
         flags += ["--backend", "gloo", "--shareDevice", "--genome", "1000000", "--pairs", "400000"]
     for scaling in ("weak", "strong"):
@@ -345,6 +345,9 @@ def test_bench_on_two_ranks(mode, job):
             assert line["config"]["ranks_share_devices"] and "not a scaling" in line["config"]["note"]
         if mode != "gloo":
             assert "roofline" in line and line["roofline"]["frac"] > 0
+            assert ("strong_scaling" in line) == (scaling == "weak")                # --full: the weak line carries the fixed-size leg
+            if scaling == "weak":
+                assert line["strong_scaling"]["value"] > 0 and len(line["strong_scaling"]["ms_per_step_per_rank"]) == 2
 
 
 # ----------------------------------------------------------------------------------------------------------------------- (vi)
