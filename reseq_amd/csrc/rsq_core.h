@@ -200,22 +200,28 @@ RSQ_HD uint32_t draw_rows_k(uint32_t K, double u, double &prob_sum, const Rs &..
 // outcome of the double-precision recipe above, otherwise the lane repeats the draw in double precision (draw<NM>, from HBM).
 // Rows are float copies of the tables (the read kernel's families: FamilyGeo, rsq_types.h; the chains': DevTable::off32), four columns per 16-byte load, pad columns zero.
 //
-// Pass 1 forms the products ((r0*r1)*r2)*r3 of all columns from the bottom quad up and keeps, per quad, the sum of the columns below it; S = the sum of all.
-// Pass 2 finds the last quad whose sum-below is less than r = (1-u)*S among those sums (no loads), reloads that quad and finds the column.  Let B(j) be the exact sum
-// of the columns below j (over the double-precision values), T the exact total and T(j) = T - B(j) the sum of the columns j and above: the reference returns the
-// highest j >= 1 with T(j) > u*T up to its own rounding (relative 1e-14 of T), else 0 -- the highest j with B(j) < (1-u)*T.
-// Error of the single-precision quantities, w = 2^-24, all terms non-negative: a product carries (1+w)^7 (four roundings to float, three multiplications), a term
-// passes at most 2 + Q additions in S (Q quads) and Q + 5 in a sum from the bottom, and r takes two more roundings -- 1-u = (2^32 - word) * 2^-32 is formed from the
-// integer, so its error is relative to ITSELF: |S32 - T| <= (Q+9) w T, |bot32(j) - B(j)| <= (Q+12) w B(j), |r32 - (1-u) T| <= (Q+11) w (1-u) T.
+// Pass 1 forms, per quad, the products of all margins but the last, (r0*r1)*r2, and folds the last factor into ONE running sum by fused multiply-adds from the
+// bottom quad up; it keeps, per quad, the sum of the columns below it; S = the sum of all.  Pass 2 finds the last quad whose sum-below is less than r = (1-u)*S
+// among those sums (no loads), reloads that quad and finds the column by four more fused multiply-adds.  Let B(j) be the exact sum of the columns below j (over the
+// double-precision values), T the exact total and T(j) = T - B(j) the sum of the columns j and above: the reference returns the highest j >= 1 with T(j) > u*T up to
+// its own rounding (relative 1e-14 of T), else 0 -- the highest j with B(j) < (1-u)*T.
+// Error of the single-precision quantities, w = 2^-24, all terms non-negative: a term enters a sum carrying (1+w)^6 (four roundings to float, two multiplications:
+// the last product is exact inside the FMA, whose rounding counts as the term's first addition).  The running pair takes two FMAs per quad (lo, then hi), so a term
+// of quad c passes 2(Q-c) <= 2Q roundings there and one more across the pair: |S32 - T| <= (2Q+7) w T; bot[c] for c <= Q-1 passes at most 2Q-1 and the chosen
+// quad's four FMAs add four, the quad's own terms 6 + 4: |bot32(j) - B(j)| <= (2Q+9) w B(j); r takes two more roundings than S -- 1-u = (2^32 - word) * 2^-32 is
+// formed from the integer, so its error is relative to ITSELF: |r32 - (1-u) T| <= (2Q+9) w (1-u) T.
 // Sums of non-negative terms have errors relative to themselves, and near the decision all three are about bot32(j+1) =: hi.  So with
-//     delta = kScreenSafety * (2Q + 24) * w * (hi + 2^-20 S32)
+//     delta = kScreenSafety * (4Q + 20) * w * (hi + 2^-20 S32)
+// (2 (2Q+9) for r32 and one of the sums, two more for the roundings of r32 - lo, hi - r32 and of delta itself)
 // r32 - bot32(j) > delta and bot32(j+1) - r32 >= delta imply B(j) < (1-u) T <= B(j+1) with room for the reference's own rounding (the 2^-20 S32 term: 1e-12 T):
-// column j is the reference's answer.  Everything else is "undecided": a band of 2 delta around every column boundary, i.e. 2 (2Q+24) w kScreenSafety * sum over
+// column j is the reference's answer.  Everything else is "undecided": a band of 2 delta around every column boundary, i.e. 2 (4Q+20) w kScreenSafety * sum over
 // the boundaries of B(j)/T of all draws.  The columns are sorted by ascending likelihood (ProbabilityEstimates.h GetResults), so B(j)/T is tiny for all but the last
-// few: about 5e-5 of the quality draws of profile P0 (K = 40), where the sums from the top down -- errors relative to T at every boundary -- left 2.2e-4 undecided.
+// few: about 1e-4 of the quality draws of profile P0 (K = 40; 6e-5 with separate multiplications and additions, which round a term fewer times in the running pair:
+// (2Q+24) instead of (4Q+20) -- DESIGN_LOG §13), where the sums from the top down -- errors relative to T at every boundary -- left 2.2e-4 undecided.
 // Preconditions, checked when the tables are packed (DevTable::f32_ok) and here: values are 0 or in [2^-60, 2^29] (no overflow;
 // an intermediate product that underflows -- (r0*r1) itself below 2^-126, i.e. two factors near 2^-60 and below -- is lost entirely: at most 2^-68 absolutely after the
 // largest factors 2^29 * 2^29, far below delta >= 2^-30 * 2^-20 * 2^-19; this assumes gradual or flushed underflow alike, no other denormal mode) and S32 >= 2^-30.
+// The FMAs are explicit (fma2 / fma1): the screen never leaves contraction to the compiler, and the double-precision recipe above is built with -ffp-contract=off.
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef float Float2 __attribute__((ext_vector_type(2)));      // v_pk_mul_f32 / v_pk_add_f32
 #else
@@ -225,6 +231,15 @@ struct Float2 {
 inline Float2 operator*(const Float2 &a, const Float2 &b) { return Float2{a.x * b.x, a.y * b.y}; }
 inline Float2 operator+(const Float2 &a, const Float2 &b) { return Float2{a.x + b.x, a.y + b.y}; }
 #endif
+// a * b + c with one rounding: v_pk_fma_f32 / v_fma_f32 on the device, the correctly rounded fmaf on the host (the emulation decides as the device does)
+RSQ_HD Float2 fma2(const Float2 &a, const Float2 &b, const Float2 &c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_elementwise_fma(a, b, c);
+#else
+    return Float2{__builtin_fmaf(a.x, b.x, c.x), __builtin_fmaf(a.y, b.y, c.y)};
+#endif
+}
+RSQ_HD float fma1(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 struct alignas(16) Quad {              // columns 4c .. 4c+3 of a row: lo = (4c, 4c+1), hi = (4c+2, 4c+3)
     Float2 lo, hi;
 };
@@ -258,15 +273,19 @@ struct MixedRow32 {
 };
 
 RSQ_HD Quad mul_quad(const Quad &a, const Quad &b) { return Quad{a.lo * b.lo, a.hi * b.hi}; }
+// the screen's form of a quad: the products of all margins but the last (`head`) and the last margin's values, which the FMAs multiply in
+struct QuadFactors {
+    Quad head, last;
+};
 template <class R0, class R1, class R2>
-RSQ_HD Quad prod_quad(uint32_t c, const R0 &r0, const R1 &r1, const R2 &r2) {
+RSQ_HD QuadFactors quad_factors(uint32_t c, const R0 &r0, const R1 &r1, const R2 &r2) {
     const Quad a = r0.quad(c), b = r1.quad(c), d = r2.quad(c);
-    return mul_quad(mul_quad(a, b), d);
+    return QuadFactors{mul_quad(a, b), d};
 }
 template <class R0, class R1, class R2, class R3>
-RSQ_HD Quad prod_quad(uint32_t c, const R0 &r0, const R1 &r1, const R2 &r2, const R3 &r3) {
+RSQ_HD QuadFactors quad_factors(uint32_t c, const R0 &r0, const R1 &r1, const R2 &r2, const R3 &r3) {
     const Quad a = r0.quad(c), b = r1.quad(c), d = r2.quad(c), e = r3.quad(c);
-    return mul_quad(mul_quad(mul_quad(a, b), d), e);
+    return QuadFactors{mul_quad(mul_quad(a, b), d), e};
 }
 #if defined(__HIP_DEVICE_COMPILE__)
 #define RSQ_SCHED_BARRIER() __builtin_amdgcn_sched_barrier(0)
@@ -284,26 +303,27 @@ constexpr float kScreenMinSum = 9.313225746154785e-10f;      // 2^-30
 template <int Q, class... Rs>
 RSQ_HD bool draw_screened(uint32_t word, uint32_t &col, const Rs &...rs) {
     constexpr int G = Q % RSQ_SCREEN_BATCH == 0 ? RSQ_SCREEN_BATCH : (Q % 2 == 0 ? 2 : 1);      // quads per batch
-    constexpr bool kKeep = Q <= 2;                           // short rows: the products stay in registers, pass 2 loads nothing
-    // pass 1 runs from the bottom quad up with ONE running sum, kept as a pair (the columns 0, 1 and 2, 3 of the quads so far): bot[c] = the sum of the quads below
-    // c, S = bot[Q].  A term passes one addition inside its quad, at most Q in the running pair and one across the pair: the bounds above hold (Q + 2 additions
-    // in S and in a sum from the bottom, four more inside the chosen quad).  [One sum instead of a sum per quad, a total and a second pass over the per-quad sums: 20
-    // additions and the compiler's shuffles to pair them up less per draw of 40 columns.]
+    constexpr bool kKeep = Q <= 2;                           // short rows: the factors stay in registers, pass 2 loads nothing
+    // pass 1 runs from the bottom quad up with ONE running sum, kept as a pair (the columns 0, 2 and 1, 3 of the quads so far): bot[c] = the sum of the quads below
+    // c, S = bot[Q].  Per quad two packed FMAs take the last factor and the addition together (the bounds above: 2Q roundings in the pair, one across it).  [One sum
+    // instead of a sum per quad, a total and a second pass over the per-quad sums: 20 additions and the compiler's shuffles to pair them up less per draw of 40
+    // columns; the FMAs: two multiplications and two additions less per quad.]
     float bot[Q + 1];
-    Quad kept[kKeep ? Q : 1];
+    QuadFactors kept[kKeep ? Q : 1];
     Float2 run;
     run.x = run.y = 0.f;
     bot[0] = 0.f;
 #pragma unroll
     for (int g = 0; g < Q; g += G) {
-        Quad p[G];
+        QuadFactors f[G];
 #pragma unroll
-        for (int i = 0; i < G; ++i) p[i] = prod_quad((uint32_t)(g + i), rs...);
+        for (int i = 0; i < G; ++i) f[i] = quad_factors((uint32_t)(g + i), rs...);
 #pragma unroll
         for (int i = 0; i < G; ++i) {
-            run = run + (p[i].lo + p[i].hi);
+            run = fma2(f[i].head.lo, f[i].last.lo, run);
+            run = fma2(f[i].head.hi, f[i].last.hi, run);
             bot[g + i + 1] = run.x + run.y;
-            if constexpr (kKeep) kept[g + i] = p[i];
+            if constexpr (kKeep) kept[g + i] = f[i];
         }
         RSQ_SCHED_BARRIER();                                 // keeps the scheduler from hoisting the loads of every batch to the top (registers)
     }
@@ -319,14 +339,15 @@ RSQ_HD bool draw_screened(uint32_t word, uint32_t &col, const Rs &...rs) {
         below += hit ? 1u : 0u;
     }
     const uint32_t fc = below ? below - 1u : 0u;             // below == 0: r is 0 (word 0, or S is 0), left undecided
-    Quad p;
+    QuadFactors f;
     if constexpr (kKeep) {
-        p = kept[0];
+        f = kept[0];
 #pragma unroll
         for (int c = 1; c < Q; ++c)
-            if (fc == (uint32_t)c) p = kept[c];
-    } else p = prod_quad(fc, rs...);
-    const float b1 = base + p.lo.x, b2 = b1 + p.lo.y, b3 = b2 + p.hi.x, b4 = b3 + p.hi.y;
+            if (fc == (uint32_t)c) f = kept[c];
+    } else f = quad_factors(fc, rs...);
+    const float b1 = fma1(f.head.lo.x, f.last.lo.x, base), b2 = fma1(f.head.lo.y, f.last.lo.y, b1), b3 = fma1(f.head.hi.x, f.last.hi.x, b2),
+                b4 = fma1(f.head.hi.y, f.last.hi.y, b3);
     uint32_t j;
     float hi, lo;
     if (b3 < r) j = 3u, lo = b3, hi = b4;
@@ -334,7 +355,8 @@ RSQ_HD bool draw_screened(uint32_t word, uint32_t &col, const Rs &...rs) {
     else if (b1 < r) j = 1u, lo = b1, hi = b2;
     else j = 0u, lo = base, hi = b1;
     col = 4u * fc + j;
-    const float delta = (kScreenSafety * (float)(2 * Q + 24) * 5.9604644775390625e-08f) * (hi + 9.5367431640625e-07f * S);
+    constexpr float kBand = kScreenSafety * (float)(4 * Q + 20) * 5.9604644775390625e-08f;
+    const float delta = fma1(kBand, hi, (kBand * 9.5367431640625e-07f) * S);      // kBand * (hi + 2^-20 S): two roundings, as the sum and the product had
     return S >= kScreenMinSum && below != 0u && r - lo > delta && hi - r >= delta;      // S >= 2^-30 also rejects NaN
 }
 

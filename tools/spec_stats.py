@@ -58,9 +58,9 @@ def main():
         m = re.search(r"(\.LBB[0-9_]+)", t)
         if op.startswith(("s_cbranch", "s_branch")) and m and labels.get(m.group(1), i + 1) <= i:
             s0 = labels[m.group(1)]
-            loops.append((sum(1 for _, o, _ in insts[s0:i] if o.startswith("v_pk_mul")), -(i - s0), s0, i))
+            loops.append((sum(1 for _, o, _ in insts[s0:i] if o.startswith(("v_pk_mul", "v_pk_fma"))), -(i - s0), s0, i))
     # the step loops: since round 5 there are two (every lane in the template part / the general one) -- the smallest loops that hold the three draws' packed
-    # multiplies (at least 60 of them), none containing another
+    # multiplies and FMAs (at least 60 of them), none containing another
     # (a loop shows as several backward branches to neighbouring labels: overlapping ranges are one loop, reported over their hull -- but a range that spans two
     # loops which each hold the draws is the chunk loop around them, not a step loop)
     cands = sorted((l for l in loops if l[0] >= 60), key=lambda l: l[3] - l[2])
@@ -92,7 +92,7 @@ def report(insts, labels, lo, hi, dump, title):
     valu = sum(v for k, v in ops.items() if k.startswith("v_") and not k.startswith(("v_readlane", "v_writelane", "v_readfirstlane")))
     group = collections.Counter()
     for k, v in ops.items():
-        for cls in ("v_mov_b32", "v_cndmask", "v_cmp", "v_pk_mul", "v_pk_add", "v_mad_u64", "v_lshl_add_u64", "v_readlane", "v_writelane", "ds_read", "ds_write", "global_load", "global_store",
+        for cls in ("v_mov_b32", "v_cndmask", "v_cmp", "v_pk_mul", "v_pk_fma", "v_pk_add", "v_fma_f32", "v_add_f32", "v_mad_u64", "v_lshl_add_u64", "v_readlane", "v_writelane", "ds_read", "ds_write", "global_load", "global_store",
                     "buffer_load", "buffer_store", "scratch_", "s_load", "s_nop", "s_waitcnt", "s_cbranch", "s_swappc"):
             if k.startswith(cls):
                 group[cls] += v
