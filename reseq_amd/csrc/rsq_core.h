@@ -403,7 +403,7 @@ RSQ_HD uint32_t draw_slim(const DevTable &t, const double *__restrict__ pool, Pa
 }
 
 // How FillRead reaches its tables.  GlobalTables reads descriptors and rows from HBM; the read kernel uses LdsTables
-// (rsq_kernels.h) which serves descriptors and the per-lane-varying margins from LDS.
+// (rsq_reads.h) which serves descriptors and the per-lane-varying margins from LDS.
 struct GlobalTables {
     using Sum = double;            // what a draw reports of prob_sum; the callers only ask whether it is 0
     const DevSim &S;

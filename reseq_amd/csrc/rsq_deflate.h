@@ -388,7 +388,7 @@ RSQ_HD void member_header(uint8_t *h, uint32_t member_bytes) {
 }
 
 
-#if RSQ_DEVICE_BUILD && !defined(RSQ_SPEC)
+#if RSQ_DEVICE_BUILD
 // ------------------------------------------------------------------------------------------------------------------------- device
 struct LdsOr {
     RSQ_LDS uint32_t *words;

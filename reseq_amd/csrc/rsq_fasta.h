@@ -116,7 +116,7 @@ RSQ_HD bool record_start(const uint8_t *text, uint64_t p) { return text[p] == '>
 
 // Where a record's codes go.  ByteArrays: three arrays of bytes (what rsq_sim_error_model takes from its callers, and what the tests read).  Packed: a half-word
 // per base -- base code in bits 0-1, dominant error in bits 2-4, error percent in bits 8-15 -- so that the read kernel's lane gets eight bases of all three
-// with ONE 16-byte load instead of three 8-byte ones (PackedRecordSrc, rsq_kernels.h: a lane's record is 450 bytes of its own, every load touches 64 lines).
+// with ONE 16-byte load instead of three 8-byte ones (PackedRecordSrc, rsq_reads.h: a lane's record is 450 bytes of its own, every load touches 64 lines).
 struct ByteArrays {
     uint8_t *seqs, *dom, *rate;
     RSQ_HD void eight(uint64_t k, uint64_t s, uint64_t d, uint64_t r) const {
@@ -219,7 +219,7 @@ RSQ_HD RecordError parse_record(P rec, uint64_t size, const Out &out, RecordFiel
     return any & (kOnes * 4u) ? kContainsN : kRecordOk;
 }
 
-#if RSQ_DEVICE_BUILD && !defined(RSQ_SPEC)
+#if RSQ_DEVICE_BUILD
 constexpr uint32_t kTileBytes = 4096, kStartsBlock = 256;        // a wave per tile, four tiles per workgroup
 // record starts in tile `tile`: f(position, rank within the tile) for each, returns their number.  A lane takes 16 bytes of a step's 1024 as two words: the '>'
 // bytes whose byte in front is a line end (zero_bytes of the words; the byte in front of the lane's first one is the lane before's last), counted with popcounts

@@ -2,7 +2,7 @@
 // packing the profile tables and the 2-bit reference, the number of pairs / block numbering, the chain list of
 // the systematic-error pre-pass and the spline / threshold arithmetic of the bias normalisation.
 // The shipped library uploads through hipMalloc (rsq_sim.hip); tests/hostemu keeps the arrays in host memory so
-// that the per-lane functions of rsq_core.h / rsq_kernels.h can be checked against the oracle without a GPU.
+// that the per-lane functions of rsq_core.h and of the stages' headers can be checked against the oracle without a GPU.
 #pragma once
 #include <math.h>
 #include <stdio.h>
@@ -22,7 +22,9 @@
 #include <thread>
 
 #include "rsq_host.h"
-#include "rsq_kernels.h"
+#include "rsq_chains.h"      // the chain list and the bias parameters the pre-passes are handed
+#include "rsq_sieve.h"       // kMaxDevAlleles: more alleles than a cell of the sieve holds are refused
+#include "rsq_reads.h"       // the LDS plan of the read kernels is made here
 
 namespace rsq {
 
@@ -379,7 +381,7 @@ inline void pack_tables(SimState &s, Uploader &up) {
         family_values(plan.i, indels, plan.slot_i);
     }
 
-    // LDS plan of the read kernels (rsq_kernels.h "LDS staging"): one image per template segment with the tables of ALL tiles when they fit the 160 KiB,
+    // LDS plan of the read kernels (rsq_reads.h "LDS staging"): one image per template segment with the tables of ALL tiles when they fit the 160 KiB,
     // else one image per (segment, tile) -- the read kernel then serves one tile per workgroup (k_fill_reads<MASK, VAR, true>: reads binned by tile).  The
     // most valuable rows first: descriptors and outcome values, quality margins 0 + 1, base-call margin 0, the waves' rings and one error-rate row are
     // required; more error-rate rows, base-call margin 2 and indel margin 0 take what is left.
@@ -1305,7 +1307,7 @@ constexpr const char *kWalkErrorMessage =
     "(GetSysErrorFromBlock, Simulator.cpp:232-292); such a variant set cannot be simulated";
 
 // ------------------------------------------------------------------------------- chains of the a13 pre-pass
-// Positions per chunk of a chain (one lane each) and the run-up in front of a chunk in pass 0 (rsq_kernels.h, "Speculative chunking").  The chunks of a pass are
+// Positions per chunk of a chain (one lane each) and the run-up in front of a chunk in pass 0 (rsq_chains.h, "Speculative chunking").  The chunks of a pass are
 // independent, so they only have to be many enough to fill the device (2 M: eight waves on each of its 1024 SIMDs twice over); beyond that longer chunks make
 // the run-up -- work that is thrown away -- a smaller share: 256 positions up to 0.5 Gb of strands, 4096 for a human-sized reference (6.2 Gb, 1.5 M chunks).  The
 // run-up is half a chunk, at most 384 positions (three times the distance within which two runs were measured to meet; on the human-sized reference, chunk
@@ -1838,7 +1840,7 @@ inline void upload_normalization(SimState &s, Uploader &up) {
     s.dev.thresholds = up.put(s.thresholds);
     s.dev.bias_normalization = s.bias_normalization;
     // The sieve draws the gaps between the lengths whose cell passes the zero threshold instead of one uniform per cell (k_sieve_gaps,
-    // rsq_kernels.h): q[len] = product of thr1 over the lengths of len's segment up to len = the probability that none of them passes.
+    // rsq_sieve.h): q[len] = product of thr1 over the lengths of len's segment up to len = the probability that none of them passes.
     // A segment ends where the product falls below 2^-500 (a threshold of exactly zero ends its segment at once), so no product
     // underflows; the next segment starts from 1 with a fresh draw.
     const uint32_t to = s.dev.insert_to, from = s.dev.insert_from;

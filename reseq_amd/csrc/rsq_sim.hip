@@ -1,5 +1,5 @@
 // rsq_sim.hip -- the simulator object behind the C ABI (include/reseq_amd.h): packs profile + reference into
-// HBM, runs the pre-passes and drives the kernels of rsq_kernels.h.  Compiled for gfx950 only.
+// HBM, runs the pre-passes and drives the kernels of the stages' headers (rsq_chains.h, rsq_sieve.h, rsq_scan.h, rsq_reads.h, rsq_format.h).  Compiled for gfx950 only.
 #include <hip/hip_runtime.h>
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -21,6 +21,12 @@
 #include "../../include/reseq_amd.h"
 #include "rsq_deflate.h"
 #include "rsq_fasta.h"
+#include "rsq_chains.h"
+#include "rsq_sieve.h"
+#include "rsq_scan.h"
+#include "rsq_text.h"
+#include "rsq_reads.h"
+#include "rsq_format.h"
 #include "rsq_pack.h"
 #include "rsq_spec.h"
 #include "rsq_textio.h"
@@ -536,6 +542,23 @@ static FillShape fill_shape(const rsq_sim &s, size_t lds_bytes, uint64_t n_items
     return FillShape{(blocks + 1u) & ~1u, waves * 64u};                     // segments alternate over blockIdx.x
 }
 
+// The tail of both read kernels' launches: the chunk counters reserved and cleared (counter_bytes: 8, or the longer trace area of an RSQ_TRACE_FILL build), then,
+// under the fill_reads timer, the kernel compiled for the profile (`spec` with `args`, its parameters in order) or, without one, the library's own instantiation
+// (`launch_own`).  `counters`: the caller's variable that `args` and `launch_own` read, set here once the area is reserved.
+template <class LaunchOwn>
+static void launch_read_kernel(rsq_sim &s, hipStream_t st, const FillShape &shape, size_t lds_bytes, size_t counter_bytes, hipFunction_t spec, void **args, uint32_t *&counters,
+                               LaunchOwn &&launch_own) {
+    s.cur->fill_counters.reserve(counter_bytes);
+    counters = s.cur->fill_counters.as<uint32_t>();
+    HIP_CHECK(hipMemsetAsync(counters, 0, counter_bytes, st));
+    s.timers["fill_reads"].start(st);
+    if (spec) {
+        spec_allow_lds(spec, lds_bytes);
+        HIP_CHECK(hipModuleLaunchKernel(spec, shape.blocks, 1, 1, shape.threads, 1, 1, (unsigned)lds_bytes, st, args, nullptr));
+    } else launch_own();
+    s.timers["fill_reads"].stop(st);
+    HIP_CHECK(hipGetLastError());
+}
 // k_fill_reads: persistent waves, one workgroup per CU slot; MASK = quads per quality row (screened draws on the LDS image planned by
 // pack_tables) or 0 (double precision from HBM: the reference path the tests compare with)
 // they return the order of the raw arrays' rows: nullptr = row i is item i, else row i is item perm[i] (binned by tile)
@@ -548,22 +571,13 @@ static const uint32_t *launch_fill_kernel(rsq_sim &s, const Fragment *frags, uin
         }, frags, fvars);
     const size_t lds_bytes = fill_lds_bytes(s, MASK != 0, BINNED, &k_fill_reads<MASK, VAR, BINNED>);
     const FillShape shape = fill_shape(s, lds_bytes, n_pairs, 2, fill_block(VAR));
-    const uint32_t blocks = shape.blocks, kBlock = shape.threads;
-    s.cur->fill_counters.reserve(8);
-    HIP_CHECK(hipMemsetAsync(s.cur->fill_counters.as<uint32_t>(), 0, 8, st));
-    hipFunction_t spec = spec_kernel(s, SpecKind::kReads, MASK, VAR, BINNED);
-    s.timers["fill_reads"].start(st);
-    if (spec) {
-        uint32_t *sizes = s.cur->sizes.as<uint32_t>(), *counters = s.cur->fill_counters.as<uint32_t>();
-        RawLayout raw_arg = raw;
-        void *args[] = {&s.dev, &s.names, &frags, &n_pairs, &adapter_first, &raw_arg, &sizes, &counters, &fvars, &bins};
-        spec_allow_lds(spec, lds_bytes);
-        HIP_CHECK(hipModuleLaunchKernel(spec, blocks, 1, 1, kBlock, 1, 1, (unsigned)lds_bytes, st, args, nullptr));
-    } else
-        hipLaunchKernelGGL((k_fill_reads<MASK, VAR, BINNED>), dim3(blocks), dim3(kBlock), lds_bytes, st, s.dev, s.names, frags, n_pairs, adapter_first, raw, s.cur->sizes.as<uint32_t>(),
-                           s.cur->fill_counters.as<uint32_t>(), fvars, bins);
-    s.timers["fill_reads"].stop(st);
-    HIP_CHECK(hipGetLastError());
+    uint32_t *sizes = s.cur->sizes.as<uint32_t>(), *counters = nullptr;
+    RawLayout raw_arg = raw;
+    void *args[] = {&s.dev, &s.names, &frags, &n_pairs, &adapter_first, &raw_arg, &sizes, &counters, &fvars, &bins};
+    launch_read_kernel(s, st, shape, lds_bytes, 8, spec_kernel(s, SpecKind::kReads, MASK, VAR, BINNED), args, counters, [&] {
+        hipLaunchKernelGGL((k_fill_reads<MASK, VAR, BINNED>), dim3(shape.blocks), dim3(shape.threads), lds_bytes, st, s.dev, s.names, frags, n_pairs, adapter_first, raw, sizes, counters, fvars,
+                           bins);
+    });
     return bins.perm;
 }
 template <uint32_t MASK, bool VAR = false>
@@ -583,24 +597,18 @@ static const uint32_t *launch_records_kernel(rsq_sim &s, const RecordJob &job, c
     const FillShape shape = fill_shape(s, lds_bytes, n, 1, kFillBlockWalk);
     const uint32_t blocks = shape.blocks;
 #if defined(RSQ_TRACE_FILL)
-    s.cur->fill_counters.reserve(16 + 32 * (size_t)blocks);
-    HIP_CHECK(hipMemsetAsync(s.cur->fill_counters.as<uint32_t>(), 0, 16 + 32 * (size_t)blocks, st));
+    const size_t counter_bytes = 16 + 32 * (size_t)blocks;
 #else
-    s.cur->fill_counters.reserve(8);
-    HIP_CHECK(hipMemsetAsync(s.cur->fill_counters.as<uint32_t>(), 0, 8, st));
+    const size_t counter_bytes = 8;
 #endif
-    hipFunction_t spec = spec_kernel(s, SpecKind::kRecords, MASK, PACKED, BINNED);      // (the variant's `var` flag names the packed records here)
-    s.timers["fill_reads"].start(st);
-    if (spec) {
-        uint32_t *counters = s.cur->fill_counters.as<uint32_t>();
-        RecordJob job_arg = job;
-        RawLayout raw_arg = raw;
-        void *args[] = {&s.dev, &job_arg, &raw_arg, &counters, &bins};
-        spec_allow_lds(spec, lds_bytes);
-        HIP_CHECK(hipModuleLaunchKernel(spec, blocks, 1, 1, shape.threads, 1, 1, (unsigned)lds_bytes, st, args, nullptr));
-    } else
-        hipLaunchKernelGGL((k_fill_records<MASK, BINNED, PACKED>), dim3(blocks), dim3(shape.threads), lds_bytes, st, s.dev, job, raw, s.cur->fill_counters.as<uint32_t>(), bins);
-    s.timers["fill_reads"].stop(st);
+    uint32_t *counters = nullptr;
+    RecordJob job_arg = job;
+    RawLayout raw_arg = raw;
+    void *args[] = {&s.dev, &job_arg, &raw_arg, &counters, &bins};
+    // (the variant's `var` flag names the packed records here)
+    launch_read_kernel(s, st, shape, lds_bytes, counter_bytes, spec_kernel(s, SpecKind::kRecords, MASK, PACKED, BINNED), args, counters, [&] {
+        hipLaunchKernelGGL((k_fill_records<MASK, BINNED, PACKED>), dim3(blocks), dim3(shape.threads), lds_bytes, st, s.dev, job, raw, counters, bins);
+    });
 #if defined(RSQ_TRACE_FILL)
     {
         std::vector<uint64_t> t(2 + 4 * (size_t)blocks);
@@ -625,7 +633,6 @@ static const uint32_t *launch_records_kernel(rsq_sim &s, const RecordJob &job, c
                 shape.threads, (unsigned long long)n, (last_start - first) / 100.0, (last_end - first) / 100.0, stage / 100.0 / blocks, run / 100.0 / blocks);
     }
 #endif
-    HIP_CHECK(hipGetLastError());
     return bins.perm;
 }
 template <uint32_t MASK>
@@ -634,37 +641,29 @@ static const uint32_t *launch_records_mask(rsq_sim &s, const RecordJob &job, con
         if (fill_is_binned(s)) return job.codes ? launch_records_kernel<MASK, true, true>(s, job, seg_dev, n, raw, st) : launch_records_kernel<MASK, true, false>(s, job, seg_dev, n, raw, st);
     return job.codes ? launch_records_kernel<MASK, false, true>(s, job, seg_dev, n, raw, st) : launch_records_kernel<MASK, false, false>(s, job, seg_dev, n, raw, st);
 }
+// The read kernels are instantiated for 0 quads and for every entry of kQualityQuads: f(std::integral_constant<uint32_t, Q>) for the Q that equals `mask`
+template <class F, size_t... I>
+static const uint32_t *with_fill_mask(uint32_t mask, const char *kernel, F &&f, std::index_sequence<I...>) {
+    const uint32_t *order = nullptr;
+    auto tried = [&](auto q) { return mask == q() && (order = f(q), true); };
+    if (!(tried(std::integral_constant<uint32_t, 0u>{}) || ... || tried(std::integral_constant<uint32_t, kQualityQuads[I]>{})))
+        throw Error(std::string("no ") + kernel + " instantiation for " + std::to_string(mask) + " quads");
+    return order;
+}
+template <class F>
+static const uint32_t *with_fill_mask(rsq_sim &s, const char *kernel, F &&f) {
+    return with_fill_mask(effective_fill_mask(s.dev.lds.mask, s.force_fill_mode), kernel, f, std::make_index_sequence<sizeof(kQualityQuads) / sizeof(kQualityQuads[0])>{});
+}
 static const uint32_t *launch_fill_reads(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_first, const RawLayout &raw, hipStream_t st,
                               const FragmentVar *fvars = nullptr) {
-    const uint32_t mask = effective_fill_mask(s.dev.lds.mask, s.force_fill_mode);
     const bool var = frags && s.has_variants;            // with variants the error walk is per lane state
-#define RSQ_FILL_CASE(Q)                                                                       \
-    if (mask == Q) {                                                                                  \
-        if (var) return launch_fill_mask<Q, true>(s, frags, n_pairs, adapter_first, raw, st, fvars);  \
-        return launch_fill_mask<Q>(s, frags, n_pairs, adapter_first, raw, st);                        \
-    }
-    RSQ_FILL_CASE(0u)
-    RSQ_FILL_CASE(kQualityQuads[0])
-    RSQ_FILL_CASE(kQualityQuads[1])
-    RSQ_FILL_CASE(kQualityQuads[2])
-    RSQ_FILL_CASE(kQualityQuads[3])
-    RSQ_FILL_CASE(kQualityQuads[4])
-    static_assert(sizeof(kQualityQuads) == 5 * sizeof(uint32_t), "one case per entry");
-#undef RSQ_FILL_CASE
-    throw Error("no k_fill_reads instantiation for " + std::to_string(mask) + " quads");
+    return with_fill_mask(s, "k_fill_reads", [&](auto q) {
+        if (var) return launch_fill_mask<decltype(q)::value, true>(s, frags, n_pairs, adapter_first, raw, st, fvars);
+        return launch_fill_mask<decltype(q)::value>(s, frags, n_pairs, adapter_first, raw, st);
+    });
 }
 static const uint32_t *launch_fill_records(rsq_sim &s, const RecordJob &job, const uint8_t *seg_dev, uint64_t n, const RawLayout &raw, hipStream_t st) {
-    const uint32_t mask = effective_fill_mask(s.dev.lds.mask, s.force_fill_mode);
-#define RSQ_REC_CASE(Q) \
-    if (mask == Q) return launch_records_mask<Q>(s, job, seg_dev, n, raw, st);
-    RSQ_REC_CASE(0u)
-    RSQ_REC_CASE(kQualityQuads[0])
-    RSQ_REC_CASE(kQualityQuads[1])
-    RSQ_REC_CASE(kQualityQuads[2])
-    RSQ_REC_CASE(kQualityQuads[3])
-    RSQ_REC_CASE(kQualityQuads[4])
-#undef RSQ_REC_CASE
-    throw Error("no k_fill_records instantiation for " + std::to_string(mask) + " quads");
+    return with_fill_mask(s, "k_fill_records", [&](auto q) { return launch_records_mask<decltype(q)::value>(s, job, seg_dev, n, raw, st); });
 }
 
 // ---- the stages of one (sub-)range; they work on the simulator's current workspace (s.cur)
@@ -1031,7 +1030,7 @@ __global__ void __launch_bounds__(256) k_record_text_sizes(RawLayout raw, uint64
     const uint64_t i = raw.item_of(row);
     sizes[i] = error_model_record_size(raw.meta[row], ids.length(i));
 }
-// The text by waves, as k_format_write writes the pairs' (rsq_kernels.h): a wave takes 16 consecutive raw rows, four lanes per record (the header and the first
+// The text by waves, as k_format_write writes the pairs' (rsq_format.h): a wave takes 16 consecutive raw rows, four lanes per record (the header and the first
 // half of the bases, the second half, the two halves of the qualities), formats them into an LDS image of their contiguous stretch of the output and copies
 // the image out in aligned 16-byte stores; PERM (rows binned by tile): a slot of the image per record.  (One lane per record with word-granular stores, the
 // kernel of rounds 2-4, wrote 0.3 TB/s: 8.3 ms per 8 M records.)  A wave whose records do not fit the image writes them lane by lane.

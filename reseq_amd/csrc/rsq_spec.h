@@ -2,7 +2,7 @@
 //
 // What a loaded profile fixes -- the LDS plan, the three table families' common geometry (FamilyGeo), tiles, phred offset, longest deletion -- are run-time values of the
 // by-value kernel argument in the library's own instantiations of k_fill_reads / k_fill_records: they occupy scalar registers (the kernels sit at the cap and spill
-// them into vector lanes), and every row address is integer arithmetic on them.  Here the same kernel bodies (rsq_kernels.h, embedded in the library as text) are
+// them into vector lanes), and every row address is integer arithmetic on them.  Here the same kernel bodies (rsq_reads.h and what it includes, embedded in the library as text) are
 // compiled by hiprtc with those values as LITERALS (RSQ_SPEC: the macros RSQ_PLAN / RSQ_SIM of rsq_types.h read namespace rsq::spec instead of the argument).  One
 // program per kernel variant (reads / records, with variants, binned by tile), compiled when the variant is first needed, kept per simulator; the code object is
 // also kept on disk ($XDG_CACHE_HOME or ~/.cache, under reseq_amd/) under a hash of sources, literals, variant, architecture and compiler version.
@@ -26,12 +26,19 @@
 #include <vector>
 
 #include "rsq_host.h"
-#include "rsq_kernels.h"
+#include "rsq_reads.h"
 
 namespace rsq {
 
-// the kernel sources as the build embedded them (build/rsq_embedded.inc: one raw string per header)
+// the kernel sources as the build embedded them (build/rsq_embedded.inc: one raw string per header): rsq_reads.h and every header it reaches, the same list as
+// EMBED in the Makefile.  hiprtc is handed exactly these, and the cache key hashes exactly these.
 #include "build/rsq_embedded.inc"
+struct SpecHeader {
+    const char *name, *text;
+};
+constexpr SpecHeader kSpecHeaders[] = {{"rsq_types.h", kSrc_rsq_types_h}, {"rsq_core.h", kSrc_rsq_core_h}, {"rsq_variants.h", kSrc_rsq_variants_h},
+                                       {"rsq_text.h", kSrc_rsq_text_h},   {"rsq_reads.h", kSrc_rsq_reads_h}};
+constexpr int kSpecHeaderCount = sizeof(kSpecHeaders) / sizeof(kSpecHeaders[0]);
 
 struct Hiprtc {                                   // the few entry points, bound at run time: the library must load where libhiprtc is absent
     using Program = void *;
@@ -128,7 +135,7 @@ struct SpecVariant {
 inline const char *spec_kernel_name(SpecKind k) { return k == SpecKind::kReads ? "rsq_spec_fill_reads" : "rsq_spec_fill_records"; }
 
 inline std::string spec_program(const std::string &literals, const SpecVariant &v) {
-    std::string t = "#define RSQ_SPEC 1\n#include \"rsq_types.h\"\n" + literals + "#include \"rsq_kernels.h\"\nusing namespace rsq;\n";
+    std::string t = "#define RSQ_SPEC 1\n#include \"rsq_types.h\"\n" + literals + "#include \"rsq_reads.h\"\nusing namespace rsq;\n";
     const std::string m = std::to_string(v.mask) + "u, ";
     if (v.kind == SpecKind::kReads)
         t += std::string("extern \"C\" __global__ void __launch_bounds__(fill_block(") + (v.var ? "true" : "false") + ")) rsq_spec_fill_reads(DevSim S, NameTable names, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_only_first, "
@@ -195,8 +202,8 @@ inline bool spec_compile(const DevSim &dev, const SpecVariant &v, const std::str
     }
     const std::string literals = spec_literals(dev), program = spec_program(literals, v);
     rtc.version(&out.rtc_major, &out.rtc_minor);
-    const char *headers[] = {kSrc_rsq_types_h, kSrc_rsq_core_h, kSrc_rsq_variants_h, kSrc_rsq_kernels_h};
-    const char *names[] = {"rsq_types.h", "rsq_core.h", "rsq_variants.h", "rsq_kernels.h"};
+    const char *headers[kSpecHeaderCount], *names[kSpecHeaderCount];
+    for (int i = 0; i < kSpecHeaderCount; ++i) headers[i] = kSpecHeaders[i].text, names[i] = kSpecHeaders[i].name;
     uint64_t h = fnv1a(program + " " + std::to_string(RSQ_FILL_BLOCK) + " " + std::to_string(RSQ_FILL_BLOCK_WALK) + " " + std::to_string(RSQ_SCREEN_BATCH) + " " + std::to_string(RSQ_CHUNK_LARGE)
 #if defined(RSQ_TRACE_FILL)
                                 + " trace"
@@ -234,7 +241,7 @@ inline bool spec_compile(const DevSim &dev, const SpecVariant &v, const std::str
     if (!out.code.empty()) return true;
     const auto t0 = std::chrono::steady_clock::now();
     Hiprtc::Program prog = nullptr;
-    if (rtc.create(&prog, program.c_str(), "rsq_spec.hip", 4, headers, names) != 0) {
+    if (rtc.create(&prog, program.c_str(), "rsq_spec.hip", kSpecHeaderCount, headers, names) != 0) {
         note = "hiprtcCreateProgram failed: the read kernels run in the library's own instantiation";
         return false;
     }

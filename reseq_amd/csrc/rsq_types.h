@@ -112,7 +112,7 @@ struct FamilyGeo {
     uint32_t values_src;         // DevSim::par0, bytes: the same for all tables of the profile (what an image copies)
 };
 
-// LDS image of k_fill_reads (rsq_kernels.h "LDS staging"), in single precision: one per template segment holding the tables of all tiles
+// LDS image of k_fill_reads (rsq_reads.h "LDS staging"), in single precision: one per template segment holding the tables of all tiles
 // (img_tiles == n_tiles; built once per workgroup) or, when those do not fit, one per (segment, tile) (img_tiles == 1; a workgroup builds the
 // image of the tile whose reads it is about to serve).  Contents:
 // the table descriptors of the image's tiles and of the indel tables, their outcome values (both for the double-precision route), the outcome values by column

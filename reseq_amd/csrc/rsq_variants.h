@@ -57,6 +57,9 @@ struct VarView {
 RSQ_HD VarView var_view(const DevSim &S, uint32_t seq) {
     return VarView{S.ref_words, S.gc_prefix, S.seq_word_off[seq], S.seq_len[seq], S.variants + S.var_ptr[seq], S.var_ptr[seq + 1] - S.var_ptr[seq], S.var_bases};
 }
+// substitutions only (DevSim::hap_stride): an allele's own copy of the packed reference and of its G/C prefix sums
+RSQ_HD const uint64_t *hap_words(const DevSim &S, uint32_t allele) { return S.hap_stride ? S.ref_words + (1u + allele) * S.hap_stride : S.ref_words; }
+RSQ_HD const uint32_t *hap_gc_prefix(const DevSim &S, uint32_t allele) { return S.hap_stride ? S.gc_prefix + (1u + allele) * S.hap_stride : S.gc_prefix; }
 
 // the start of a pass at a start position: bias_mod.first_variant_id_, start_variant_pos_ (a pass with start_variant_pos > 0 starts
 // inside the inserted bases of variant first_variant_id, CheckForInsertedBasesToStartFrom :1870-1896)

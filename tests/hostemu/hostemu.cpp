@@ -2,7 +2,7 @@
 //
 // The shipped library (reseq_amd/libreseq_amd.so) has no CPU path.  This file builds a separate test artefact
 // (tests/hostemu/libhostemu.so, g++) that instantiates the very same __host__ __device__ functions the HIP
-// kernels call (rsq_core.h, rsq_kernels.h) and the same packing code (rsq_pack.h) with the arrays kept in host
+// kernels call (rsq_core.h and the stages' headers) and the same packing code (rsq_pack.h) with the arrays kept in host
 // memory, and walks them with plain loops in place of the grid.  `pytest -m "not gpu"` compares it with the
 // oracle so that state-machine, packing and counter-layout mistakes are caught in a container without a GPU.
 // Nothing in reseq_amd/ links to or loads this file.
@@ -18,6 +18,10 @@ static uint32_t g_ring_lag = 0;                    // emu_set_ring_lag
 
 #include "../../reseq_amd/csrc/rsq_deflate.h"
 #include "../../reseq_amd/csrc/rsq_fasta.h"
+#include "../../reseq_amd/csrc/rsq_chains.h"
+#include "../../reseq_amd/csrc/rsq_sieve.h"
+#include "../../reseq_amd/csrc/rsq_text.h"
+#include "../../reseq_amd/csrc/rsq_reads.h"
 #include "../../reseq_amd/csrc/rsq_pack.h"
 
 using namespace rsq;

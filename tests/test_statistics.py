@@ -169,7 +169,7 @@ def test_conditionals_of_the_product(workdir):
 
 def test_gap_draws_pass_every_cell_with_its_own_probability(workdir):
     """The sieve draws the gaps between the cells that pass the zero threshold instead of a uniform per cell (oracle_sim.c orc_gap_hits,
-    rsq_kernels.h sieve_gaps; Simulator.cpp:2304-2306).  Per fragment length the passes over many start positions must be binomial with
+    rsq_sieve.h sieve_gaps; Simulator.cpp:2304-2306).  Per fragment length the passes over many start positions must be binomial with
     p = 1 - thr1[length], passes of neighbouring lengths must be uncorrelated, and probability_chosen of a passing cell must be uniform
     on [thr1, 1).  Also with thresholds small enough that the running product is restarted (segments), and with a threshold of zero."""
     import parity_cases as P
@@ -604,7 +604,7 @@ def _chi2_two_samples(a, b, min_expected=5.0):
 
 
 def test_gap_sieve_and_the_references_loop_are_two_samples_of_one_process(workdir):
-    """Product and oracle draw the sieve's passing cells by their gaps (oracle_sim.c orc_gap_hits, rsq_kernels.h sieve_gaps); the reference draws one uniform per
+    """Product and oracle draw the sieve's passing cells by their gaps (oracle_sim.c orc_gap_hits, rsq_sieve.h sieve_gaps); the reference draws one uniform per
     (start, fragment length) cell (Simulator.cpp:2302-2306).  orc_sieve_blocks_literal is that loop as written, on a random stream of its own, so for one seed the
     two routes are independent samples and bit parity between product and oracle says nothing about them being the same process -- this test does: over 1.4 * 10^7
     cells (8 seeds x 20 000 start positions x 89 lengths) the two routes must agree in (i) passing cells per fragment length, (ii) simulated sites per fragment length,
