@@ -129,6 +129,29 @@ RSQ_HD void sys_chain_chunk(const DevSim &S, const Acc &acc, uint32_t c1, uint32
     }
 }
 
+// What the lane of a chunk settles before it walks the chunk (k_sys_chain below, "Speculative chunking"; the host emulation's loop over the chunks): the state the
+// chunk is entered with -- the outgoing state of its left neighbour in the pass before, the chain's own entering state for its first chunk -- the chunk's
+// positions [lo, hi), and where the walk begins: in pass 0 a run-up of `warmup` positions in front of lo, whose end is the guess of the chunk's incoming state.
+RSQ_HD uint32_t chain_incoming(const Chain &ch, uint32_t c, const uint32_t *out_prev, int pass) {
+    const uint32_t local = c - ch.first_chunk;
+    if (local == 0) return ch.in_state;
+    return pass > 0 ? out_prev[c - 1] : 0u;                          // pass 0: the guess (0, 0)
+}
+struct ChunkEntry {
+    uint32_t want, lo, hi, from;
+    ChainAcc acc;
+};
+RSQ_HD ChunkEntry chain_chunk_entry(const DevSim &S, const Chain &ch, uint32_t c, const uint32_t *out_prev, int pass, uint32_t chunk_len, uint32_t warmup) {
+    const uint32_t local = c - ch.first_chunk;
+    ChunkEntry e;
+    e.want = chain_incoming(ch, c, out_prev, pass);
+    e.acc = ChainAcc{S.ref_words, ch.kind, ch.len, ch.kind < 2 ? S.seq_word_off[ch.id] : 0, ch.kind == 2 ? S.adapters[ch.seg].seqs + S.adapters[ch.seg].seq_ptr[ch.id] : nullptr};
+    e.lo = (ch.chunk_lo + local) * chunk_len;
+    e.hi = e.lo + chunk_len < ch.len ? e.lo + chunk_len : ch.len;
+    e.from = pass == 0 && local ? e.lo - (warmup < e.lo ? warmup : e.lo) : e.lo;      // pass 0: the guess is the end of a run-up from (0,0)
+    return e;
+}
+
 #if RSQ_DEVICE_BUILD
 // The same positions for the 64 chunks of a wave, with the expensive part of a position -- an error-rate draw that has to read its rows, about one position in
 // thirty -- done for several lanes at once: a lane whose draw the random word does not decide waits (its chunk is its own: nothing orders the lanes of a wave)
@@ -215,11 +238,6 @@ RSQ_HD double site_bias(const DevSim &S, uint64_t word_off, uint32_t L, uint32_t
 //       matter: chunks of one pass are independent), the others keep their outgoing state.  A wave of the run kernel then holds 64 chunks
 //       that all have work, whatever share of the chunks changed.
 //   k_sys_chain: one lane per listed chunk (pass 0: every chunk, list == nullptr).
-RSQ_HD uint32_t chain_incoming(const Chain &ch, uint32_t c, const uint32_t *out_prev, int pass) {
-    const uint32_t local = c - ch.first_chunk;
-    if (local == 0) return ch.in_state;
-    return pass > 0 ? out_prev[c - 1] : 0u;                          // pass 0: the guess (0, 0)
-}
 __global__ void __launch_bounds__(256) k_sys_chain_select(const Chain *chains, const uint32_t *chunk_chain, uint32_t n_chunks, const uint32_t *used_state, const uint32_t *out_prev,
                                                          uint32_t *out_new, uint32_t *list, uint32_t *n_listed, int pass) {
     // places in the list are reserved once per workgroup (ranks in LDS): one global atomic per wave queues at one L2 channel (see k_sieve_finish)
@@ -244,14 +262,10 @@ __global__ void __launch_bounds__(64) k_sys_chain(DevSim S, const Chain *chains,
     if (i >= n_run) return;
     const uint32_t c = list ? list[i] : i;
     const Chain ch = chains[chunk_chain[c]];
-    const uint32_t local = c - ch.first_chunk;
-    const uint32_t want = chain_incoming(ch, c, out_prev, pass);
-    ChainAcc acc{S.ref_words, ch.kind, ch.len, ch.kind < 2 ? S.seq_word_off[ch.id] : 0, ch.kind == 2 ? S.adapters[ch.seg].seqs + S.adapters[ch.seg].seq_ptr[ch.id] : nullptr};
-    uint32_t dist = want & 0xFFFFFFu, start_rate = want >> 24;
-    const uint32_t lo = (ch.chunk_lo + local) * chunk_len, hi = lo + chunk_len < ch.len ? lo + chunk_len : ch.len;
-    const uint32_t from = pass == 0 && local ? lo - (warmup < lo ? warmup : lo) : lo;      // pass 0: the guess is the end of a run-up from (0,0)
-    uint32_t used = want;
-    sys_chain_chunk_batched(S, acc, ch.c1, ch.c2, from, hi, ch.initial_dom, dist, start_rate, ch.out, lo, &used);
+    const ChunkEntry e = chain_chunk_entry(S, ch, c, out_prev, pass, chunk_len, warmup);
+    uint32_t dist = e.want & 0xFFFFFFu, start_rate = e.want >> 24;
+    uint32_t used = e.want;
+    sys_chain_chunk_batched(S, e.acc, ch.c1, ch.c2, e.from, e.hi, ch.initial_dom, dist, start_rate, ch.out, e.lo, &used);
     used_state[c] = used;
     out_new[c] = dist | (start_rate << 24);
 }

@@ -1,5 +1,5 @@
 // rsq_sim.hip -- the simulator object behind the C ABI (include/reseq_amd.h): packs profile + reference into
-// HBM, runs the pre-passes and drives the kernels of the stages' headers (rsq_chains.h, rsq_sieve.h, rsq_scan.h, rsq_reads.h, rsq_format.h).  Compiled for gfx950 only.
+// HBM, gives the pre-passes (rsq_prepass.h) their kernels and drives the kernels of the stages' headers (rsq_chains.h, rsq_sieve.h, rsq_scan.h, rsq_reads.h, rsq_format.h).  Compiled for gfx950 only.
 #include <hip/hip_runtime.h>
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -28,6 +28,7 @@
 #include "rsq_reads.h"
 #include "rsq_format.h"
 #include "rsq_pack.h"
+#include "rsq_prepass.h"
 #include "rsq_spec.h"
 #include "rsq_textio.h"
 
@@ -191,7 +192,7 @@ struct MappedFile {                                                   // a whole
 };
 
 // ------------------------------------------------------------------------------------------------ rsq_sim
-struct rsq_sim : SimState {
+struct rsq_sim : PrepassSim {
     int device = 0;
     DeviceUploader up;
     // workspace of the hot path (grow-only): two sets, so that the sieve of one sub-range of a call can run beside the FASTQ text of the one before it
@@ -243,17 +244,11 @@ struct rsq_sim : SimState {
     SpecKernels spec;
     std::string arch;              // hipDeviceProp_t::gcnArchName
     bool specialize = true;
-    // the sharded pre-pass (rsq_sim_prepare_plan ... rsq_sim_prepare_finish): what lives between its calls
-    BiasPlan bias_plan;
-    bool planned = false;
-    struct ChainRun {
-        std::vector<Chain> chains;
-        ShardEdges edges;
-        uint32_t n_chunks = 0, passes = 0, block_lo = 0, block_hi = 0;
-        bool pass_through = false;     // the rank has no blocks: its neighbours' states go straight through
-        DevBuf d_chains, d_chunk_chain, d_used, d_out[2], d_changed, d_list;
-        bool valid = false;
-    } chain_run;
+    // the device's part of the chain run PrepassSim::pre.run (DevicePrepass): the chains, the chain of every chunk, per chunk the state it was entered with and its
+    // outgoing states of two passes, the count and the list of the chunks that run again
+    struct ChainBufs {
+        DevBuf chains, chunk_chain, used, out[2], changed, list;
+    } chain_bufs;
 };
 
 static bool fill_is_binned(const rsq_sim &s) { return effective_fill_mask(s.dev.lds.mask, s.force_fill_mode) != 0 && s.dev.lds.binned; }
@@ -271,198 +266,128 @@ static hipFunction_t spec_kernel(rsq_sim &s, SpecKind kind, uint32_t mask, bool 
 
 namespace rsq {
 
-// --------------------------------------------------------------------------------- systematic errors (a13)
-// passes of k_sys_chain over the run's chunks until no chunk's incoming state changed; `first_pass`: 0 for a new run, the run's pass
-// count to resume one whose entering states (Chain::in_state) were replaced
-static void iterate_sys_chains(rsq_sim &s, rsq_sim::ChainRun &run, hipStream_t st, uint32_t first_pass) {
-    run.d_list.reserve((size_t)run.n_chunks * 4 + 16);
-    uint32_t pass = first_pass;
-    for (;; ++pass) {
-        uint32_t *out_prev = run.d_out[(pass + 1) & 1].as<uint32_t>(), *out_new = run.d_out[pass & 1].as<uint32_t>();
+// ------------------------------------------------------------------------------------------ pre-passes
+// what the drivers of rsq_prepass.h run on the device, on stream `st`
+constexpr uint64_t kBiasWindow = 512ull << 20;       // start positions per pass of the bias sums: 2 x 4 GB of tracks
+struct DevicePrepass : PrepassBackend {
+    rsq_sim &s;
+    hipStream_t st;
+    DevicePrepass(rsq_sim &sim, void *stream) : s(sim), st((hipStream_t)stream) {}
+
+    // FragmentDistributionStats.cpp:3504-3582 CalculateBiasNormalization; the SumBias scans (Reference.cpp:622-659) run on
+    // the GPU, one launch for all (sequence, sampled length) pairs; partial sums are combined in a fixed order.
+    void bias_partials(const BiasPlan &plan, uint64_t g_lo, uint64_t g_hi, std::vector<double> &h_sum, std::vector<double> &h_max) override {
+        const bool trace = s.opt.trace_prepare != 0;
+        auto t0 = std::chrono::steady_clock::now();
+        auto lap = [&](const char *what) {
+            if (!trace) return;
+            HIP_CHECK(hipStreamSynchronize(st));
+            const auto t1 = std::chrono::steady_clock::now();
+            fprintf(stderr, "prepare:   bias sums: %-18s %8.3f s\n", what, std::chrono::duration<double>(t1 - t0).count());
+            t0 = t1;
+        };
+        const uint32_t n_chunks = bias_chunks(plan);
+        if (!n_chunks) return;
+        DevBuf d_params, d_chunk_param, d_chunk_ptr, d_sum, d_max, d_start_bias, d_end_bias;
+        d_params.upload(plan.params);
+        d_chunk_param.upload(plan.chunk_param);
+        d_chunk_ptr.upload(plan.chunk_ptr);
+        d_sum.reserve((size_t)n_chunks * 8);
+        d_max.reserve((size_t)n_chunks * 8);
+        HIP_CHECK(hipMemsetAsync(d_sum.as<double>(), 0, (size_t)n_chunks * 8, st));
+        HIP_CHECK(hipMemsetAsync(d_max.as<double>(), 0, (size_t)n_chunks * 8, st));
+        lap("chunk tables");
+        // The share in windows of kBiasWindow positions: the tracks of one window (16 bytes per position; allocating them for a whole human-sized
+        // reference takes a second) are computed, its chunks summed, the buffers used again.  A window's chunks read start positions up to a chunk
+        // behind its end and end positions a fragment length further.
+        const uint64_t lo = std::min<uint64_t>(g_lo, s.total_ref_size), hi = std::min<uint64_t>(g_hi, s.total_ref_size);
+        uint64_t window = kBiasWindow;
+        if (s.opt.bias_window > 0) window = (uint64_t)s.opt.bias_window;
+        const uint64_t reach = (uint64_t)kBiasBlock * kBiasRun + s.dev.insert_to, track_len = std::min(hi - lo, window) + reach;
+        d_start_bias.reserve(track_len * 8 + 16);
+        d_end_bias.reserve(track_len * 8 + 16);
+        lap("track buffers");
+        for (uint64_t a = lo; a < hi; a += window) {
+            const uint64_t b = std::min(hi, a + window), w_hi = std::min<uint64_t>(s.total_ref_size, b + reach);
+            hipLaunchKernelGGL(k_surrounding_bias_tracks, dim3((uint32_t)cdiv(w_hi - a, 256)), dim3(256), 0, st, s.dev, d_start_bias.as<double>(), d_end_bias.as<double>(), a, w_hi);
+            HIP_CHECK(hipGetLastError());
+            hipLaunchKernelGGL(k_sum_bias, dim3(n_chunks), dim3(kBiasBlock), 0, st, s.dev, d_params.as<BiasParam>(), d_chunk_param.as<uint32_t>(), d_chunk_ptr.as<uint32_t>(),
+                               d_start_bias.as<double>(), d_end_bias.as<double>(), a, d_sum.as<double>(), d_max.as<double>(), a, b);
+            HIP_CHECK(hipGetLastError());
+        }
+        lap("track and sum kernels");
+        HIP_CHECK(hipMemcpyAsync(h_sum.data(), d_sum.as<double>(), h_sum.size() * 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(h_max.data(), d_max.as<double>(), h_max.size() * 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        lap("download");
+    }
+
+    // ---- systematic errors (a13): k_sys_chain over the run's chunks
+    void begin_run(const ChainRun &run, const std::vector<uint32_t> &chunk_chain) override {
+        rsq_sim::ChainBufs &b = s.chain_bufs;
+        publish_chains(run);
+        b.chunk_chain.upload(chunk_chain);
+        b.used.reserve(run.n_chunks * 4);
+        b.out[0].reserve(run.n_chunks * 4);
+        b.out[1].reserve(run.n_chunks * 4);
+        b.changed.reserve(8);
+        b.list.reserve((size_t)run.n_chunks * 4 + 16);
+    }
+    void publish_chains(const ChainRun &run) override { s.chain_bufs.chains.upload(run.chains); }
+    uint32_t run_pass(const ChainRun &run, uint32_t pass, int prev, int cur) override {
+        rsq_sim::ChainBufs &b = s.chain_bufs;
+        uint32_t *out_prev = b.out[prev].as<uint32_t>(), *out_new = b.out[cur].as<uint32_t>();
         uint32_t n_run = run.n_chunks;
         const uint32_t *list = nullptr;
         if (pass > 0) {                                             // which chunks were entered with a state that has changed since
-            HIP_CHECK(hipMemsetAsync(run.d_changed.as<uint32_t>(), 0, 4, st));
-            hipLaunchKernelGGL(k_sys_chain_select, dim3(cdiv(run.n_chunks, 256)), dim3(256), 0, st, run.d_chains.as<Chain>(), run.d_chunk_chain.as<uint32_t>(), run.n_chunks,
-                               run.d_used.as<uint32_t>(), out_prev, out_new, run.d_list.as<uint32_t>(), run.d_changed.as<uint32_t>(), (int)pass);
+            HIP_CHECK(hipMemsetAsync(b.changed.as<uint32_t>(), 0, 4, st));
+            hipLaunchKernelGGL(k_sys_chain_select, dim3(cdiv(run.n_chunks, 256)), dim3(256), 0, st, b.chains.as<Chain>(), b.chunk_chain.as<uint32_t>(), run.n_chunks,
+                               b.used.as<uint32_t>(), out_prev, out_new, b.list.as<uint32_t>(), b.changed.as<uint32_t>(), (int)pass);
             HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipMemcpyAsync(&n_run, run.d_changed.as<uint32_t>(), 4, hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(&n_run, b.changed.as<uint32_t>(), 4, hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipStreamSynchronize(st));
-            list = run.d_list.as<uint32_t>();
+            list = b.list.as<uint32_t>();
         }
         if (n_run) {
-            hipLaunchKernelGGL(k_sys_chain, dim3(cdiv(n_run, 64)), dim3(64), 0, st, s.dev, run.d_chains.as<Chain>(), run.d_chunk_chain.as<uint32_t>(), list, n_run, s.chain_chunk,
-                               chain_warmup_len(s.chain_chunk, s.opt), run.d_used.as<uint32_t>(), out_prev, out_new, (int)pass);
+            hipLaunchKernelGGL(k_sys_chain, dim3(cdiv(n_run, 64)), dim3(64), 0, st, s.dev, b.chains.as<Chain>(), b.chunk_chain.as<uint32_t>(), list, n_run, s.chain_chunk,
+                               chain_warmup_len(s.chain_chunk, s.opt), b.used.as<uint32_t>(), out_prev, out_new, (int)pass);
             HIP_CHECK(hipGetLastError());
         }
-        if (pass > 0 && !n_run) break;
-        if (pass > first_pass + run.n_chunks + 2) throw Error("systematic-error chains did not converge");
+        return n_run;
     }
-    HIP_CHECK(hipStreamSynchronize(st));
-    run.passes = pass + 1;                                          // the final states are in d_out[(run.passes - 1) & 1]
-}
-// -V after a finished run: the variants' own systematic errors.  The chain state in front of every variant comes from the device (k_variant_chain_states: 8 bytes per
-// variant come back instead of the tracks' 4 bytes per reference position), the pass over the variants' bases runs on the host's threads.
-static void variant_sys_errors_from_run(rsq_sim &s, hipStream_t st) {
-    rsq_sim::ChainRun &run = s.chain_run;
-    const uint32_t n_variants = (uint32_t)s.variants.size();
-    if (!s.has_variants || !n_variants) return;
-    std::vector<ChainSpan> span((size_t)s.dev.n_seqs * 2, ChainSpan{-1, 0});
-    for (size_t c = 0; c < run.chains.size(); ++c) {
-        const Chain &ch = run.chains[c];
-        if (ch.kind > 1u) continue;
-        span[(size_t)ch.id * 2 + ch.kind] = ChainSpan{(int32_t)c, (c + 1 < run.chains.size() ? run.chains[c + 1].first_chunk : run.n_chunks) - ch.first_chunk};
+    uint32_t out_state(const ChainRun &, int cur, size_t chunk) override {
+        uint32_t state = 0;
+        HIP_CHECK(hipMemcpy(&state, s.chain_bufs.out[cur].as<uint32_t>() + chunk, 4, hipMemcpyDeviceToHost));
+        return state;
     }
-    DevBuf d_span, d_states;
-    d_span.upload(span);
-    d_states.reserve((size_t)n_variants * 8);
-    hipLaunchKernelGGL(k_variant_chain_states, dim3(cdiv(n_variants, 256), 2), dim3(256), 0, st, s.dev, run.d_chains.as<Chain>(), d_span.as<ChainSpan>(), run.d_used.as<uint32_t>(),
-                       s.chain_chunk, n_variants, d_states.as<uint32_t>());
-    HIP_CHECK(hipGetLastError());
-    std::vector<uint32_t> states((size_t)n_variants * 2);
-    HIP_CHECK(hipMemcpyAsync(states.data(), d_states.as<uint32_t>(), states.size() * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    const std::vector<StrandTask> windows = strand_tasks(s.opt, run.chains, run.n_chunks, s.chain_chunk, [](uint32_t) { return 0u; });      // the windows' entering states are not needed
-    build_variant_sys_errors(s, s.up, &windows, states.data(), states.data() + n_variants);
-}
-static uint32_t run_sys_chains(rsq_sim &s, hipStream_t st, ChainSet set, const ShardRange *range = nullptr) {
-    rsq_sim::ChainRun &run = s.chain_run;
-    run.valid = false;
-    run.chains.clear();
-    run.edges = ShardEdges{};
-    std::vector<uint32_t> chunk_chain;
-    s.chain_chunk = chain_chunk_len(s.total_ref_size, s.opt);
-    build_chains(s, set, run.chains, chunk_chain, range, &run.edges);
-    run.n_chunks = (uint32_t)chunk_chain.size();
-    run.passes = 0;
-    if (!run.n_chunks) return 0;
-    run.d_chains.upload(run.chains);
-    run.d_chunk_chain.upload(chunk_chain);
-    run.d_used.reserve(run.n_chunks * 4);
-    run.d_out[0].reserve(run.n_chunks * 4);
-    run.d_out[1].reserve(run.n_chunks * 4);
-    run.d_changed.reserve(8);
-    iterate_sys_chains(s, run, st, 0);
-    run.valid = true;
-    return run.passes;
-}
-
-// ------------------------------------------------------------------------------- bias normalisation (a14)
-// FragmentDistributionStats.cpp:3504-3582 CalculateBiasNormalization; the SumBias scans (Reference.cpp:622-659) run on
-// the GPU, one launch for all (sequence, sampled length) pairs; partial sums are combined in a fixed order.
-constexpr uint64_t kBiasWindow = 512ull << 20;       // start positions per pass of the bias sums: 2 x 4 GB of tracks
-// partial sums and maxima of the chunks (kBiasBlock * kBiasRun start positions each, BiasPlan::chunk_ptr) whose first start position lies in
-// the share [g_lo, g_hi) of the concatenated sequences; zero elsewhere
-static void bias_partials(rsq_sim &s, hipStream_t st, const BiasPlan &plan, uint64_t g_lo, uint64_t g_hi, std::vector<double> &h_sum, std::vector<double> &h_max) {
-    const bool trace = s.opt.trace_prepare != 0;
-    auto t0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!trace) return;
-        HIP_CHECK(hipStreamSynchronize(st));
-        const auto t1 = std::chrono::steady_clock::now();
-        fprintf(stderr, "prepare:   bias sums: %-18s %8.3f s\n", what, std::chrono::duration<double>(t1 - t0).count());
-        t0 = t1;
-    };
-    const uint32_t n_chunks = bias_chunks(plan);
-    h_sum.assign(n_chunks, 0.0);
-    h_max.assign(n_chunks, 0.0);
-    if (!n_chunks) return;
-    DevBuf d_params, d_chunk_param, d_chunk_ptr, d_sum, d_max, d_start_bias, d_end_bias;
-    d_params.upload(plan.params);
-    d_chunk_param.upload(plan.chunk_param);
-    d_chunk_ptr.upload(plan.chunk_ptr);
-    d_sum.reserve((size_t)n_chunks * 8);
-    d_max.reserve((size_t)n_chunks * 8);
-    HIP_CHECK(hipMemsetAsync(d_sum.as<double>(), 0, (size_t)n_chunks * 8, st));
-    HIP_CHECK(hipMemsetAsync(d_max.as<double>(), 0, (size_t)n_chunks * 8, st));
-    lap("chunk tables");
-    // The share in windows of kBiasWindow positions: the tracks of one window (16 bytes per position; allocating them for a whole human-sized
-    // reference takes a second) are computed, its chunks summed, the buffers used again.  A window's chunks read start positions up to a chunk
-    // behind its end and end positions a fragment length further.
-    const uint64_t lo = std::min<uint64_t>(g_lo, s.total_ref_size), hi = std::min<uint64_t>(g_hi, s.total_ref_size);
-    uint64_t window = kBiasWindow;
-    if (s.opt.bias_window > 0) window = (uint64_t)s.opt.bias_window;
-    const uint64_t reach = (uint64_t)kBiasBlock * kBiasRun + s.dev.insert_to, track_len = std::min(hi - lo, window) + reach;
-    d_start_bias.reserve(track_len * 8 + 16);
-    d_end_bias.reserve(track_len * 8 + 16);
-    lap("track buffers");
-    for (uint64_t a = lo; a < hi; a += window) {
-        const uint64_t b = std::min(hi, a + window), w_hi = std::min<uint64_t>(s.total_ref_size, b + reach);
-        hipLaunchKernelGGL(k_surrounding_bias_tracks, dim3((uint32_t)cdiv(w_hi - a, 256)), dim3(256), 0, st, s.dev, d_start_bias.as<double>(), d_end_bias.as<double>(), a, w_hi);
-        HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(k_sum_bias, dim3(n_chunks), dim3(kBiasBlock), 0, st, s.dev, d_params.as<BiasParam>(), d_chunk_param.as<uint32_t>(), d_chunk_ptr.as<uint32_t>(),
-                           d_start_bias.as<double>(), d_end_bias.as<double>(), a, d_sum.as<double>(), d_max.as<double>(), a, b);
-        HIP_CHECK(hipGetLastError());
-    }
-    lap("track and sum kernels");
-    HIP_CHECK(hipMemcpyAsync(h_sum.data(), d_sum.as<double>(), h_sum.size() * 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(h_max.data(), d_max.as<double>(), h_max.size() * 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    lap("download");
-}
-static void bias_normalization(rsq_sim &s, hipStream_t st) {
-    const BiasPlan plan = plan_bias_normalization(s, s.up);
-    std::vector<double> h_sum, h_max;
-    bias_partials(s, st, plan, 0, UINT64_MAX, h_sum, h_max);
-    normalization_from_partials(s, s.up, plan, h_sum.data(), h_max.data());
-}
-
-static void prepare(rsq_sim &s, uint64_t seed, uint64_t num_read_pairs, double coverage, int ref_bias_mode, const char *base_identifier, hipStream_t st) {
-    HIP_CHECK(hipSetDevice(s.device));
-    const bool trace = s.opt.trace_prepare != 0;                // stage times of the pre-pass on stderr
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto lap = [&](const char *what, std::chrono::steady_clock::time_point &t0) {
-        if (trace) fprintf(stderr, "prepare: %-28s %8.3f s\n", what, std::chrono::duration<double>(now() - t0).count());
-        t0 = now();
-    };
-    auto t0 = now();
-    plan_simulation(s, s.up, seed, num_read_pairs, coverage, ref_bias_mode, base_identifier);
-    lap("plan", t0);
-    s.planned = false;
-    if (s.has_ref) {
-        bias_normalization(s, st);
-        lap("bias normalisation", t0);
-    }
-    s.passes = run_sys_chains(s, st, s.has_ref ? kChainsSimulation : kChainsAdapters);
-    HIP_CHECK(hipStreamSynchronize(st));
-    lap("systematic-error chains", t0);
-    if (s.has_variants && s.chain_run.valid) variant_sys_errors_from_run(s, st);      // -V: the variants' bases, from the finished chains
-    lap("variants' systematic errors", t0);
-    s.prepared = true;
-    s.prepared_lo = 1;
-    s.prepared_hi = s.total_blocks + 1;
-    // the read kernel for this profile (rsq_spec.h), so that no compilation falls into the first rsq_sim_pairs
-    if (s.has_ref) (void)spec_kernel(s, SpecKind::kReads, effective_fill_mask(s.dev.lds.mask, s.force_fill_mode), s.has_variants, fill_is_binned(s));
-    lap("read kernel for the profile", t0);
-}
-
-// Simulator::CreateSystematicErrorProfile (Simulator.cpp:2597-2653): both strands of every sequence, reverse first, as FASTQ.
-// The reference reads sys_gc_range_ uninitialised in this mode (it is only set in Simulate, :2782); here it has that value.
-static void create_sys_error_profile(rsq_sim &s, uint64_t seed, const char *path, hipStream_t st) {
-    if (!s.has_ref) throw Error("a reference is needed to draw a systematic error profile");
-    HIP_CHECK(hipSetDevice(s.device));
-    s.dev.seed = seed;
-    set_sys_gc_range(s);
-    run_sys_chains(s, st, kChainsProfile);
-    s.prepared = false;                                             // the simulation tracks were overwritten: prepare again before simulating
-    std::string text;
-    std::vector<uint16_t> track;
-    std::vector<uint8_t> dom, rate;
-    for (uint32_t i = 0; i < s.dev.n_seqs; ++i)
-        for (uint32_t strand = 2; strand--;) {
-            const uint32_t L = s.seq_len[i];
-            track.resize(L);
-            dom.resize(L);
-            rate.resize(L);
-            HIP_CHECK(hipMemcpy(track.data(), (strand ? s.sys_rev : s.sys_fwd) + s.seq_base_off[i], (size_t)L * 2, hipMemcpyDeviceToHost));
-            for (uint32_t k = 0; k < L; ++k) {
-                dom[k] = (uint8_t)(track[k] & 0xFF);
-                rate[k] = (uint8_t)(track[k] >> 8);
-            }
-            text += sys_error_fastq_record(s.ref_ids[i] + (strand ? " reverse" : " forward"), dom.data(), rate.data(), L);
+    // The chain state in front of every variant comes from the device (k_variant_chain_states: 8 bytes per variant come back instead of the tracks' 4 bytes per
+    // reference position), the pass over the variants' bases runs on the host's threads.
+    void variant_sys_errors(const ChainRun &run) override {
+        const uint32_t n_variants = (uint32_t)s.variants.size();
+        if (!s.has_variants || !n_variants) return;
+        std::vector<ChainSpan> span((size_t)s.dev.n_seqs * 2, ChainSpan{-1, 0});
+        for (size_t c = 0; c < run.chains.size(); ++c) {
+            const Chain &ch = run.chains[c];
+            if (ch.kind > 1u) continue;
+            span[(size_t)ch.id * 2 + ch.kind] = ChainSpan{(int32_t)c, (c + 1 < run.chains.size() ? run.chains[c + 1].first_chunk : run.n_chunks) - ch.first_chunk};
         }
-    write_text_file(path, text);
-}
+        DevBuf d_span, d_states;
+        d_span.upload(span);
+        d_states.reserve((size_t)n_variants * 8);
+        hipLaunchKernelGGL(k_variant_chain_states, dim3(cdiv(n_variants, 256), 2), dim3(256), 0, st, s.dev, s.chain_bufs.chains.as<Chain>(), d_span.as<ChainSpan>(),
+                           s.chain_bufs.used.as<uint32_t>(), s.chain_chunk, n_variants, d_states.as<uint32_t>());
+        HIP_CHECK(hipGetLastError());
+        std::vector<uint32_t> states((size_t)n_variants * 2);
+        HIP_CHECK(hipMemcpyAsync(states.data(), d_states.as<uint32_t>(), states.size() * 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        const std::vector<StrandTask> windows = strand_tasks(s.opt, run.chains, run.n_chunks, s.chain_chunk, [](uint32_t) { return 0u; });      // the windows' entering states are not needed
+        build_variant_sys_errors(s, s.up, &windows, states.data(), states.data() + n_variants);
+    }
+    // the read kernel for this profile (rsq_spec.h), so that no compilation falls into the first rsq_sim_pairs
+    void ready_to_simulate() override {
+        if (s.has_ref) (void)spec_kernel(s, SpecKind::kReads, effective_fill_mask(s.dev.lds.mask, s.force_fill_mode), s.has_variants, fill_is_binned(s));
+    }
+};
 
 // --------------------------------------------------------------------------------------------- hot path
 // out[i] = *init + in[0] + ... + in[i-1] for i = 0 .. n (init nullptr: 0); the total also goes to *total_out if given
@@ -1215,7 +1140,7 @@ int rsq_partition_blocks(uint32_t total_blocks, uint32_t workers, const double *
     return RSQ_OK;
 }
 int rsq_sim_block_weights(const rsq_sim *s, double *weights, size_t cap, uint32_t *n_blocks) {
-    REQUIRE(s && n_blocks && (s->prepared || s->planned) && s->has_ref, "a simulator with a reference after rsq_sim_prepare or rsq_sim_prepare_plan");
+    REQUIRE(s && n_blocks && (s->prepared || s->pre.planned) && s->has_ref, "a simulator with a reference after rsq_sim_prepare or rsq_sim_prepare_plan");
     *n_blocks = s->total_blocks;
     if (!weights) return RSQ_OK;
     if (cap < s->total_blocks) {
@@ -1487,106 +1412,58 @@ void rsq_sim_free(rsq_sim *s) {
 int rsq_sim_prepare(rsq_sim *s, uint64_t seed, uint64_t num_read_pairs, double coverage, int ref_bias_mode, const char *record_base_identifier, void *stream) {
     REQUIRE(s, "null simulator");
     return guard([&] {
-        prepare(*s, seed, num_read_pairs, coverage, ref_bias_mode, record_base_identifier, (hipStream_t)stream);
+        HIP_CHECK(hipSetDevice(s->device));
+        DevicePrepass be(*s, stream);
+        prepare(*s, s->up, be, seed, num_read_pairs, coverage, ref_bias_mode, record_base_identifier);
         return RSQ_OK;
     });
 }
 
+// the sharded pre-pass: the drivers of rsq_prepass.h refuse calls made out of order
 int rsq_sim_prepare_plan(rsq_sim *s, uint64_t seed, uint64_t num_read_pairs, double coverage, int ref_bias_mode, const char *record_base_identifier) {
     REQUIRE(s, "null argument");
-    REQUIRE(s->has_ref, "the sharded pre-pass needs a reference");
     return guard([&] {
         HIP_CHECK(hipSetDevice(s->device));
-        s->prepared = false;
-        s->normalized = false;
-        s->chain_run.valid = false;
-        plan_simulation(*s, s->up, seed, num_read_pairs, coverage, ref_bias_mode, record_base_identifier);
-        s->bias_plan = plan_bias_normalization(*s, s->up);
-        s->planned = true;
+        prepare_plan(*s, s->up, seed, num_read_pairs, coverage, ref_bias_mode, record_base_identifier);
         return RSQ_OK;
     });
 }
 int rsq_sim_bias_partials(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, double *sums, double *maxes, size_t cap, size_t *n, void *stream) {
     REQUIRE(s && n, "null argument");
-    REQUIRE(s->planned, "rsq_sim_prepare_plan must run first");
-    *n = (size_t)bias_chunks(s->bias_plan);
+    REQUIRE(s->pre.planned, "rsq_sim_prepare_plan must run first");
+    *n = (size_t)bias_chunks(s->pre.bias_plan);
     if (!sums && !maxes && !cap) return RSQ_OK;                     // the size query
     REQUIRE(sums && maxes && cap >= *n, "arrays too small");
     return guard([&] {
         HIP_CHECK(hipSetDevice(s->device));
-        const ShardRange r = shard_range(*s, block_lo, block_hi);
-        std::vector<double> h_sum, h_max;
-        if (r.g_lo < r.g_hi) bias_partials(*s, (hipStream_t)stream, s->bias_plan, r.g_lo, r.g_hi, h_sum, h_max);
-        else {
-            h_sum.assign(*n, 0.0);
-            h_max.assign(*n, 0.0);
-        }
-        memcpy(sums, h_sum.data(), *n * 8);
-        memcpy(maxes, h_max.data(), *n * 8);
+        DevicePrepass be(*s, stream);
+        prepare_bias_partials(*s, be, block_lo, block_hi, sums, maxes);
         return RSQ_OK;
     });
 }
 int rsq_sim_prepare_normalization(rsq_sim *s, const double *sums, const double *maxes, size_t n) {
     REQUIRE(s && sums && maxes, "null argument");
-    REQUIRE(s->planned, "rsq_sim_prepare_plan must run first");
-    REQUIRE(n == (size_t)bias_chunks(s->bias_plan), "wrong number of partial sums");
     return guard([&] {
         HIP_CHECK(hipSetDevice(s->device));
-        normalization_from_partials(*s, s->up, s->bias_plan, sums, maxes);
-        s->normalized = true;
+        prepare_normalization(*s, s->up, sums, maxes, n);
         return RSQ_OK;
     });
 }
 int rsq_sim_prepare_sys_errors(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, const uint32_t in_state[2], uint32_t out_state[2], void *stream) {
     REQUIRE(s && in_state && out_state, "null argument");
-    REQUIRE(s->planned, "rsq_sim_prepare_plan must run first");
     return guard([&] {
-        hipStream_t st = (hipStream_t)stream;
         HIP_CHECK(hipSetDevice(s->device));
-        out_state[0] = in_state[0];                                 // a rank without blocks passes the states on
-        out_state[1] = in_state[1];
-        rsq_sim::ChainRun &run = s->chain_run;
-        if (!(run.valid && run.block_lo == block_lo && run.block_hi == block_hi)) {
-            const ShardRange r = shard_range(*s, block_lo, block_hi);
-            s->passes = run_sys_chains(*s, st, kChainsSimulation, &r);
-            run.block_lo = block_lo;
-            run.block_hi = block_hi;
-            run.pass_through = r.first_seq < 0;
-            run.valid = true;
-        }
-        if (run.pass_through || !run.n_chunks) return RSQ_OK;
-        bool replaced = false;
-        const int in_chain[2] = {run.edges.fwd_in_chain, run.edges.rev_in_chain};
-        for (int k = 0; k < 2; ++k)
-            if (in_chain[k] >= 0 && run.chains[(size_t)in_chain[k]].in_state != in_state[k]) {
-                run.chains[(size_t)in_chain[k]].in_state = in_state[k];
-                replaced = true;
-            }
-        if (replaced) {
-            run.d_chains.upload(run.chains);
-            iterate_sys_chains(*s, run, st, run.passes);            // only the chunks behind a changed state run again
-            s->passes = run.passes;
-        }
-        const int64_t out_chunk[2] = {run.edges.fwd_out_chunk, run.edges.rev_out_chunk};
-        for (int k = 0; k < 2; ++k) {
-            out_state[k] = 0;
-            if (out_chunk[k] >= 0)
-                HIP_CHECK(hipMemcpy(&out_state[k], run.d_out[(run.passes - 1) & 1].as<uint32_t>() + out_chunk[k], 4, hipMemcpyDeviceToHost));
-        }
+        DevicePrepass be(*s, stream);
+        prepare_sys_errors(*s, be, block_lo, block_hi, in_state, out_state);
         return RSQ_OK;
     });
 }
 int rsq_sim_prepare_finish(rsq_sim *s) {
     REQUIRE(s, "null argument");
-    REQUIRE(s->planned && s->chain_run.valid, "the sharded pre-pass has not run");
-    REQUIRE(s->normalized, "rsq_sim_prepare_normalization must run before rsq_sim_prepare_finish (the thresholds of the sieve come from it)");
     return guard([&] {
         HIP_CHECK(hipSetDevice(s->device));
-        s->prepared_lo = s->chain_run.block_lo;                     // only these blocks' tracks are finished
-        s->prepared_hi = s->chain_run.block_hi;
-        if (s->has_variants) variant_sys_errors_from_run(*s, nullptr);      // -V: the variants' bases inside the rank's strand windows, from the finished chains
-        s->prepared = true;
-        (void)spec_kernel(*s, SpecKind::kReads, effective_fill_mask(s->dev.lds.mask, s->force_fill_mode), s->has_variants, fill_is_binned(*s));
+        DevicePrepass be(*s, nullptr);
+        prepare_finish(*s, be);
         return RSQ_OK;
     });
 }
@@ -1761,7 +1638,7 @@ int rsq_sim_get_fill_plan(const rsq_sim *s, uint32_t *quality_quads, uint32_t *i
     return RSQ_OK;
 }
 int rsq_sim_get_info(const rsq_sim *s, rsq_sim_info *out) {
-    REQUIRE(s && out && (s->prepared || s->planned), "simulator not prepared");      // the counts are known from rsq_sim_prepare_plan on
+    REQUIRE(s && out && (s->prepared || s->pre.planned), "simulator not prepared");      // the counts are known from rsq_sim_prepare_plan on
     out->total_pairs = s->total_pairs;
     out->adapter_only_pairs = s->adapter_only_pairs;
     out->total_blocks = s->total_blocks;
@@ -1794,12 +1671,7 @@ int rsq_sim_set_normalization(rsq_sim *s, double bias_normalization, const doubl
 static int download_sys(const rsq_sim *s, const uint16_t *src, uint8_t *dom_out, uint8_t *rate_out, uint32_t len) {
     return guard([&] {
         HIP_CHECK(hipSetDevice(s->device));
-        std::vector<uint16_t> tmp(len);
-        HIP_CHECK(hipMemcpy(tmp.data(), src, (size_t)len * 2, hipMemcpyDeviceToHost));
-        for (uint32_t i = 0; i < len; ++i) {
-            dom_out[i] = (uint8_t)(tmp[i] & 0xFF);
-            rate_out[i] = (uint8_t)(tmp[i] >> 8);
-        }
+        read_sys_track(const_cast<rsq_sim *>(s)->up, src, len, dom_out, rate_out);      // reading changes nothing of the simulator
         return RSQ_OK;
     });
 }
@@ -1813,7 +1685,9 @@ int rsq_sim_get_sys_errors(const rsq_sim *s, int reverse_strand, uint32_t seq, u
 int rsq_sim_create_sys_error_profile(rsq_sim *s, uint64_t seed, const char *path, void *stream) {
     REQUIRE(s && path, "null argument");
     return guard([&] {
-        create_sys_error_profile(*s, seed, path, (hipStream_t)stream);
+        HIP_CHECK(hipSetDevice(s->device));
+        DevicePrepass be(*s, stream);
+        create_sys_error_profile(*s, s->up, be, seed, path);
         return RSQ_OK;
     });
 }
@@ -1842,7 +1716,7 @@ int rsq_sim_set_ref_bias_file(rsq_sim *s, const char *path) {
     return RSQ_OK;
 }
 int rsq_sim_get_ref_seq_bias(const rsq_sim *s, double *out, size_t n) {
-    REQUIRE(s && out && (s->prepared || s->planned) && n == s->ref_seq_bias.size(), "bad arguments");
+    REQUIRE(s && out && (s->prepared || s->pre.planned) && n == s->ref_seq_bias.size(), "bad arguments");
     memcpy(out, s->ref_seq_bias.data(), n * sizeof(double));
     return RSQ_OK;
 }

@@ -2,8 +2,8 @@
 //
 // The shipped library (reseq_amd/libreseq_amd.so) has no CPU path.  This file builds a separate test artefact
 // (tests/hostemu/libhostemu.so, g++) that instantiates the very same __host__ __device__ functions the HIP
-// kernels call (rsq_core.h and the stages' headers) and the same packing code (rsq_pack.h) with the arrays kept in host
-// memory, and walks them with plain loops in place of the grid.  `pytest -m "not gpu"` compares it with the
+// kernels call (rsq_core.h and the stages' headers), the same packing code (rsq_pack.h) and the same pre-pass drivers (rsq_prepass.h) with the arrays kept in host
+// memory, and walks them with plain loops in place of the grid: of the pre-passes only HostPrepass below, the loops that stand in for the kernels, is this file's own.  `pytest -m "not gpu"` compares it with the
 // oracle so that state-machine, packing and counter-layout mistakes are caught in a container without a GPU.
 // Nothing in reseq_amd/ links to or loads this file.
 #include <stdint.h>
@@ -23,6 +23,7 @@ static uint32_t g_ring_lag = 0;                    // emu_set_ring_lag
 #include "../../reseq_amd/csrc/rsq_text.h"
 #include "../../reseq_amd/csrc/rsq_reads.h"
 #include "../../reseq_amd/csrc/rsq_pack.h"
+#include "../../reseq_amd/csrc/rsq_prepass.h"
 
 using namespace rsq;
 
@@ -52,18 +53,10 @@ struct HostUploader : Uploader {
     }
 };
 
-// the chunks of a chain run and what lives between the calls of the sharded pre-pass (rsq_sim::ChainRun)
-struct ChainRun {
-    std::vector<Chain> chains;
-    std::vector<uint32_t> chunk_chain, used, out[2];
-    ShardEdges edges;
-    uint32_t passes = 0, block_lo = 0, block_hi = 0;
-    bool valid = false, pass_through = false;
-};
-struct Emu : SimState {
+struct Emu : PrepassSim {
     HostUploader up;
-    BiasPlan bias_plan;                         // the sharded pre-pass: what lives between its calls
-    ChainRun chain_run;
+    // the chunks of the chain run PrepassSim::pre.run (HostPrepass): the chain of every chunk, the state it was entered with, its outgoing states of two passes
+    std::vector<uint32_t> chunk_chain, used, out[2];
     std::vector<FragmentVar> fvars;             // of the last emu_sieve call (variants of any kind), parallel to its fragments
     int fill_mode = -1;                         // -1: screened draws on the LDS image when the plan has one (as the product does); 0: double precision only
     std::map<uint32_t, std::vector<float>> lds; // host stand-in for the LDS images, by image_qbase: one per template segment, or per (segment, tile)
@@ -169,62 +162,48 @@ void sum_bias_like_kernel(const Emu &s, const BiasParam &p, uint32_t gx, uint64_
         maxes[b] = lm[0];
     }
 }
-void bias_partials(const Emu &s, const BiasPlan &plan, uint64_t g_lo, uint64_t g_hi, std::vector<double> &h_sum, std::vector<double> &h_max) {
-    h_sum.assign(bias_chunks(plan), 0.0);
-    h_max.assign(h_sum.size(), 0.0);
-    for (size_t i = 0; i < plan.params.size(); ++i)
-        if (plan.chunk_ptr[i + 1] > plan.chunk_ptr[i])
-            sum_bias_like_kernel(s, plan.params[i], plan.chunk_ptr[i + 1] - plan.chunk_ptr[i], g_lo, g_hi, &h_sum[plan.chunk_ptr[i]], &h_max[plan.chunk_ptr[i]]);
-}
 
-void iterate_chains(Emu &s, ChainRun &run, uint32_t first_pass) {
-    const uint32_t n = (uint32_t)run.chunk_chain.size();
-    uint32_t pass = first_pass;
-    for (;; ++pass) {                                      // same pass structure as k_sys_chain + iterate_sys_chains
-        bool changed = false;
-        const std::vector<uint32_t> &prev = run.out[(pass + 1) & 1];
-        std::vector<uint32_t> &cur = run.out[pass & 1];
-        for (uint32_t c = 0; c < n; ++c) {
-            const Chain &ch = run.chains[run.chunk_chain[c]];
-            const uint32_t local = c - ch.first_chunk;
-            uint32_t want = local == 0 ? ch.in_state : 0u;
-            if (pass > 0) {
-                if (local) want = prev[c - 1];
-                if (want == run.used[c]) {
-                    cur[c] = prev[c];
-                    continue;
-                }
-                changed = true;
-            }
-            run.used[c] = want;
-            ChainAcc acc{s.dev.ref_words, ch.kind, ch.len, ch.kind < 2 ? s.seq_word_off[ch.id] : 0,
-                         ch.kind == 2 ? s.dev.adapters[ch.seg].seqs + s.dev.adapters[ch.seg].seq_ptr[ch.id] : nullptr};
-            uint32_t dist = want & 0xFFFFFFu, start_rate = want >> 24;
-            const uint32_t lo = (ch.chunk_lo + local) * s.chain_chunk, hi = std::min(lo + s.chain_chunk, ch.len), warmup = chain_warmup_len(s.chain_chunk, s.opt);
-            const uint32_t from = pass == 0 && local ? lo - std::min(warmup, lo) : lo;      // k_sys_chain: the guess of pass 0 is the end of a run-up
-            sys_chain_chunk(s.dev, acc, ch.c1, ch.c2, from, hi, ch.initial_dom, dist, start_rate, ch.out, lo, &run.used[c]);
-            cur[c] = dist | (start_rate << 24);
-        }
-        if (pass > 0 && !changed) break;
+// what the drivers of rsq_prepass.h run in place of the kernels
+struct HostPrepass : PrepassBackend {
+    Emu &s;
+    explicit HostPrepass(Emu &emu) : s(emu) {}
+    void bias_partials(const BiasPlan &plan, uint64_t g_lo, uint64_t g_hi, std::vector<double> &sums, std::vector<double> &maxes) override {
+        for (size_t i = 0; i < plan.params.size(); ++i)
+            if (plan.chunk_ptr[i + 1] > plan.chunk_ptr[i])
+                sum_bias_like_kernel(s, plan.params[i], plan.chunk_ptr[i + 1] - plan.chunk_ptr[i], g_lo, g_hi, &sums[plan.chunk_ptr[i]], &maxes[plan.chunk_ptr[i]]);
     }
-    run.passes = pass + 1;
-}
-uint32_t run_chains(Emu &s, ChainSet set, ChainRun &run, const ShardRange *range = nullptr) {
-    run = ChainRun{};
-    s.chain_chunk = chain_chunk_len(s.total_ref_size, s.opt);
-    build_chains(s, set, run.chains, run.chunk_chain, range, &run.edges);
-    const uint32_t n = (uint32_t)run.chunk_chain.size();
-    if (!n) return 0;
-    run.used.assign(n, 0);
-    run.out[0].assign(n, 0);
-    run.out[1].assign(n, 0);
-    iterate_chains(s, run, 0);
-    return run.passes;
-}
-uint32_t run_chains(Emu &s, ChainSet set) {
-    ChainRun run;
-    return run_chains(s, set, run);
-}
+    void begin_run(const ChainRun &run, const std::vector<uint32_t> &chunk_chain) override {
+        s.chunk_chain = chunk_chain;
+        s.used.assign(run.n_chunks, 0);
+        s.out[0].assign(run.n_chunks, 0);
+        s.out[1].assign(run.n_chunks, 0);
+    }
+    void publish_chains(const ChainRun &) override {}          // the loop below reads the run's own list
+    uint32_t run_pass(const ChainRun &run, uint32_t pass, int prev, int cur) override {      // k_sys_chain_select + k_sys_chain, a chunk at a time
+        const uint32_t warmup = chain_warmup_len(s.chain_chunk, s.opt);
+        uint32_t n_run = 0;
+        for (uint32_t c = 0; c < run.n_chunks; ++c) {
+            const Chain &ch = run.chains[s.chunk_chain[c]];
+            if (pass > 0 && chain_incoming(ch, c, s.out[prev].data(), (int)pass) == s.used[c]) {
+                s.out[cur][c] = s.out[prev][c];
+                continue;
+            }
+            ++n_run;
+            const ChunkEntry e = chain_chunk_entry(s.dev, ch, c, s.out[prev].data(), (int)pass, s.chain_chunk, warmup);
+            uint32_t dist = e.want & 0xFFFFFFu, start_rate = e.want >> 24;
+            s.used[c] = e.want;
+            sys_chain_chunk(s.dev, e.acc, ch.c1, ch.c2, e.from, e.hi, ch.initial_dom, dist, start_rate, ch.out, e.lo, &s.used[c]);
+            s.out[cur][c] = dist | (start_rate << 24);
+        }
+        return n_run;
+    }
+    uint32_t out_state(const ChainRun &, int cur, size_t chunk) override { return s.out[cur][chunk]; }
+    void variant_sys_errors(const ChainRun &run) override {    // the variants' bases in windows of the strands, each entered with the state its first chunk was
+        const std::vector<StrandTask> windows = strand_tasks(s.opt, run.chains, run.n_chunks, s.chain_chunk, [&](uint32_t c) { return s.used[c]; });
+        build_variant_sys_errors(s, s.up, &windows);
+    }
+    void ready_to_simulate() override { s.build_lds(); }
+};
 
 struct Raw {                              // one read alone: word columns of pitch 1
     std::vector<uint32_t> seq, qual, ops;
@@ -306,97 +285,42 @@ long long emu_get_option(const char *name) {                                    
 int emu_image_tiles(void *h) { return (int)static_cast<Emu *>(h)->dev.lds.img_tiles; }
 int emu_plan_mask(void *h) { return (int)static_cast<Emu *>(h)->dev.lds.mask; }
 
+// rsq_sim_prepare and the sharded pre-pass rsq_sim_prepare_plan ... rsq_sim_prepare_finish: the drivers of rsq_prepass.h
 int emu_prepare(void *h, uint64_t seed, uint64_t num_pairs, double coverage, int ref_bias_mode, const char *base_identifier) {
     Emu &s = *static_cast<Emu *>(h);
     return guard([&] {
-        plan_simulation(s, s.up, seed, num_pairs, coverage, ref_bias_mode, base_identifier);
-        if (s.has_ref) {
-            const BiasPlan plan = plan_bias_normalization(s, s.up);
-            std::vector<double> h_sum, h_max;
-            bias_partials(s, plan, 0, UINT64_MAX, h_sum, h_max);
-            normalization_from_partials(s, s.up, plan, h_sum.data(), h_max.data());
-        }
-        s.passes = run_chains(s, s.has_ref ? kChainsSimulation : kChainsAdapters, s.chain_run);
-        if (s.has_variants) {                                  // as rsq_sim.hip's prepare: the variants' bases in windows of the strands
-            const std::vector<StrandTask> windows = strand_tasks(s.opt, s.chain_run.chains, (uint32_t)s.chain_run.chunk_chain.size(), s.chain_chunk, [&](uint32_t c) { return s.chain_run.used[c]; });
-            build_variant_sys_errors(s, s.up, &windows);
-        }
-        s.chain_run.valid = false;
-        s.build_lds();
-        s.prepared = true;
+        HostPrepass be(s);
+        prepare(s, s.up, be, seed, num_pairs, coverage, ref_bias_mode, base_identifier);
     });
 }
-
-// the sharded pre-pass: host mirror of rsq_sim_prepare_plan / rsq_sim_bias_partials / rsq_sim_prepare_normalization / rsq_sim_prepare_sys_errors /
-// rsq_sim_prepare_finish (rsq_sim.hip), same shared host code (shard_range, build_chains with a range, normalization_from_partials)
 int emu_prepare_plan(void *h, uint64_t seed, uint64_t num_pairs, double coverage, int ref_bias_mode, const char *base_identifier) {
     Emu &s = *static_cast<Emu *>(h);
-    return guard([&] {
-        if (!s.has_ref) throw Error("the sharded pre-pass needs a reference");
-        s.prepared = false;
-        plan_simulation(s, s.up, seed, num_pairs, coverage, ref_bias_mode, base_identifier);
-        s.bias_plan = plan_bias_normalization(s, s.up);
-        s.chain_run = ChainRun{};
-    });
+    return guard([&] { prepare_plan(s, s.up, seed, num_pairs, coverage, ref_bias_mode, base_identifier); });
 }
-uint64_t emu_bias_partials_size(void *h) {
-    Emu &s = *static_cast<Emu *>(h);
-    return (uint64_t)bias_chunks(s.bias_plan);
-}
+uint64_t emu_bias_partials_size(void *h) { return (uint64_t)bias_chunks(static_cast<Emu *>(h)->pre.bias_plan); }
 int emu_bias_partials(void *h, uint32_t block_lo, uint32_t block_hi, double *sums, double *maxes) {
     Emu &s = *static_cast<Emu *>(h);
     return guard([&] {
-        const ShardRange r = shard_range(s, block_lo, block_hi);
-        std::vector<double> h_sum, h_max;
-        bias_partials(s, s.bias_plan, r.g_lo, r.g_lo < r.g_hi ? r.g_hi : r.g_lo, h_sum, h_max);
-        memcpy(sums, h_sum.data(), h_sum.size() * 8);
-        memcpy(maxes, h_max.data(), h_max.size() * 8);
+        HostPrepass be(s);
+        prepare_bias_partials(s, be, block_lo, block_hi, sums, maxes);
     });
 }
-int emu_prepare_normalization(void *h, const double *sums, const double *maxes) {
+int emu_prepare_normalization(void *h, const double *sums, const double *maxes) {       // as many values as emu_bias_partials_size says
     Emu &s = *static_cast<Emu *>(h);
-    return guard([&] { normalization_from_partials(s, s.up, s.bias_plan, sums, maxes); });
+    return guard([&] { prepare_normalization(s, s.up, sums, maxes, (size_t)bias_chunks(s.pre.bias_plan)); });
 }
 int emu_prepare_sys_errors(void *h, uint32_t block_lo, uint32_t block_hi, const uint32_t *in_state, uint32_t *out_state) {
     Emu &s = *static_cast<Emu *>(h);
     return guard([&] {
-        out_state[0] = in_state[0];
-        out_state[1] = in_state[1];
-        ChainRun &run = s.chain_run;
-        if (!(run.valid && run.block_lo == block_lo && run.block_hi == block_hi)) {
-            const ShardRange r = shard_range(s, block_lo, block_hi);
-            s.passes = run_chains(s, kChainsSimulation, run, &r);
-            run.block_lo = block_lo;
-            run.block_hi = block_hi;
-            run.pass_through = r.first_seq < 0;
-            run.valid = true;
-        }
-        if (run.pass_through || run.chunk_chain.empty()) return;
-        bool replaced = false;
-        const int in_chain[2] = {run.edges.fwd_in_chain, run.edges.rev_in_chain};
-        for (int k = 0; k < 2; ++k)
-            if (in_chain[k] >= 0 && run.chains[(size_t)in_chain[k]].in_state != in_state[k]) {
-                run.chains[(size_t)in_chain[k]].in_state = in_state[k];
-                replaced = true;
-            }
-        if (replaced) {
-            iterate_chains(s, run, run.passes);
-            s.passes = run.passes;
-        }
-        const int64_t out_chunk[2] = {run.edges.fwd_out_chunk, run.edges.rev_out_chunk};
-        for (int k = 0; k < 2; ++k) out_state[k] = out_chunk[k] >= 0 ? run.out[(run.passes - 1) & 1][(size_t)out_chunk[k]] : 0u;
+        HostPrepass be(s);
+        prepare_sys_errors(s, be, block_lo, block_hi, in_state, out_state);
     });
 }
 int emu_prepare_finish(void *h) {
     Emu &s = *static_cast<Emu *>(h);
     return guard([&] {
-        if (!s.chain_run.valid) throw Error("the sharded pre-pass has not run");
-        if (s.has_variants) {
-            const std::vector<StrandTask> windows = strand_tasks(s.opt, s.chain_run.chains, (uint32_t)s.chain_run.chunk_chain.size(), s.chain_chunk, [&](uint32_t c) { return s.chain_run.used[c]; });
-            build_variant_sys_errors(s, s.up, &windows);
-        }
-        s.build_lds();
-        s.prepared = true;
+        HostPrepass be(s);
+        prepare_finish(s, be);
     });
 }
 
@@ -431,30 +355,12 @@ int emu_set_normalization(void *h, double bias_normalization, const double *thr,
         upload_normalization(s, s.up);
     });
 }
-// the host mirror of rsq_sim_create_sys_error_profile / rsq_sim_read_sys_errors / rsq_sim_set_ref_bias_file (rsq_sim.hip)
+// rsq_sim_create_sys_error_profile / rsq_sim_read_sys_errors / rsq_sim_set_ref_bias_file
 int emu_create_sys_error_profile(void *h, uint64_t seed, const char *path) {
+    Emu &s = *static_cast<Emu *>(h);
     return guard([&] {
-        Emu &s = *static_cast<Emu *>(h);
-        s.dev.seed = seed;
-        set_sys_gc_range(s);
-        run_chains(s, kChainsProfile);
-        s.prepared = false;
-        std::string text;
-        std::vector<uint8_t> dom, rate;
-        for (uint32_t i = 0; i < s.dev.n_seqs; ++i)
-            for (uint32_t strand = 2; strand--;) {
-                const uint32_t L = s.seq_len[i];
-                const uint16_t *track = (strand ? s.sys_rev : s.sys_fwd) + s.seq_base_off[i];
-                dom.resize(L);
-                rate.resize(L);
-                for (uint32_t k = 0; k < L; ++k) {
-                    dom[k] = (uint8_t)(track[k] & 0xFF);
-                    rate[k] = (uint8_t)(track[k] >> 8);
-                }
-                text += sys_error_fastq_record(s.ref_ids[i] + (strand ? " reverse" : " forward"), dom.data(), rate.data(), L);
-            }
-        write_text_file(path, text);
-        return 0;
+        HostPrepass be(s);
+        create_sys_error_profile(s, s.up, be, seed, path);
     });
 }
 int emu_read_sys_errors(void *h, const char *path) {
@@ -537,11 +443,7 @@ void emu_get_ref_seq_bias(void *h, double *out) {
 
 void emu_get_sys(void *h, int reverse, uint32_t seq, uint8_t *dom, uint8_t *rate) {
     Emu &s = *static_cast<Emu *>(h);
-    const uint16_t *src = (reverse ? s.sys_rev : s.sys_fwd) + s.seq_base_off[seq];
-    for (uint32_t i = 0; i < s.seq_len[seq]; ++i) {
-        dom[i] = (uint8_t)(src[i] & 0xFF);
-        rate[i] = (uint8_t)(src[i] >> 8);
-    }
+    read_sys_track(s.up, (reverse ? s.sys_rev : s.sys_fwd) + s.seq_base_off[seq], s.seq_len[seq], dom, rate);
 }
 // var_errors_ of one variant on one strand after the pre-pass (dom | rate << 8 per base in the strand's drawing order); returns its length
 uint32_t emu_get_variant_sys(void *h, uint32_t seq, uint32_t var_id, int reverse, uint16_t *out, uint32_t cap) {
@@ -554,10 +456,7 @@ uint32_t emu_get_variant_sys(void *h, uint32_t seq, uint32_t var_id, int reverse
 void emu_get_adapter_sys(void *h, int seg, uint32_t id, uint8_t *dom, uint8_t *rate) {
     Emu &s = *static_cast<Emu *>(h);
     const HostAdapters &a = s.prof.adapters[seg];
-    for (uint32_t i = 0; i < a.seq_ptr[id + 1] - a.seq_ptr[id]; ++i) {
-        dom[i] = (uint8_t)(s.adapter_sys[seg][a.seq_ptr[id] + i] & 0xFF);
-        rate[i] = (uint8_t)(s.adapter_sys[seg][a.seq_ptr[id] + i] >> 8);
-    }
+    read_sys_track(s.up, s.adapter_sys[seg] + a.seq_ptr[id], a.seq_ptr[id + 1] - a.seq_ptr[id], dom, rate);
 }
 void emu_get_codes(void *h, uint32_t seq, uint8_t *out) {            // unpacks the 2-bit reference again
     Emu &s = *static_cast<Emu *>(h);

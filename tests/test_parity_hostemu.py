@@ -216,6 +216,46 @@ def test_sharded_pre_passes_with_variants(workdir):
     P.case_sharded_prepare(EmuBackend, workdir, world=4, variants=True)
 
 
+def test_sharded_pre_passes_refuse_calls_out_of_order(workdir):
+    """the order of the sharded pre-pass is kept by the drivers the library runs (rsq_prepass.h), so the emulation refuses what rsq_sim_* refuses, in the same
+    words: bias sums, normalisation and systematic errors before the plan; finish before the chains have run, and before the normalisation; any of them after
+    a whole pre-pass, which takes the plan back.  In order, the same calls go through."""
+    ppath, fpath, _ = P.make_inputs(workdir, "shardorder", P.synth.TINY, [5200, 90, 3100])
+    b = EmuBackend(ppath, fpath)
+    try:
+        def refused(call, words):
+            with pytest.raises(RuntimeError) as e:
+                call()
+            assert words in str(e.value), str(e.value)
+
+        def before_the_plan():
+            refused(lambda: b.prepare_normalization(np.zeros(4), np.zeros(4)), "rsq_sim_prepare_plan must run first")
+            refused(lambda: b.prepare_sys_errors(1, 2, [0, 0]), "rsq_sim_prepare_plan must run first")
+            refused(lambda: b.bias_partials(1, 2), "rsq_sim_prepare_plan must run first")
+            refused(b.prepare_finish, "the sharded pre-pass has not run")
+
+        before_the_plan()
+        b.prepare(5, num_pairs=3000)                       # a whole pre-pass is no plan of the sharded one
+        before_the_plan()
+        hi = b.prepare_plan(5, num_pairs=3000)["total_blocks"] + 1
+        refused(b.prepare_finish, "the sharded pre-pass has not run")
+        assert b.prepare_sys_errors(1, hi, [0, 0]) == [0, 0]      # the only rank: no neighbour needs a state
+        refused(b.prepare_finish, "rsq_sim_prepare_normalization must run before rsq_sim_prepare_finish")
+        b.prepare_normalization(*b.bias_partials(1, hi))
+        b.prepare_finish()
+        whole = EmuBackend(ppath, fpath)
+        try:
+            whole.prepare(5, num_pairs=3000)
+            assert np.array_equal(b.thresholds(), whole.thresholds())
+            assert b.pairs(1, hi)[1:] == whole.pairs(1, hi)[1:]
+        finally:
+            whole.close()
+        b.prepare_plan(5, num_pairs=3000)                  # a new plan: the run and the normalisation of the last one do not count
+        refused(b.prepare_finish, "the sharded pre-pass has not run")
+    finally:
+        b.close()
+
+
 def test_draws_without_the_bounds_on_the_random_word(workdir, rsq_options):
     """option no_indel_skip: every indel draw of the reads and every error-rate draw of the chains reads its rows (normally the random word alone decides most of
     them, rsq_pack.h certain_column / chain_sure); the results are the same"""
