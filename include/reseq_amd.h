@@ -99,6 +99,10 @@ int rsq_ref_num_sequences(const rsq_ref *r, uint32_t *out);
 int rsq_ref_sequence_length(const rsq_ref *r, uint32_t seq, uint32_t *out);
 /* ReferenceIdFirstPart (reseq/Reference.cpp:476-480): the id up to the first blank, NUL-terminated */
 int rsq_ref_sequence_name(const rsq_ref *r, uint32_t seq, char *out, size_t cap);
+/* The header of the truth alignments (rsq_sim_pairs_sam): "@HD VN:1.6 SO:unsorted GO:query", one "@SQ SN:<ReferenceIdFirstPart> LN:<length>" per sequence in order,
+ * "@PG ID:reseq_amd PN:reseq_amd" (tab-separated).  Host code, no device.  *need = its bytes; written (NUL-terminated when cap is larger) if cap >= *need, else
+ * RSQ_ENOSPC. */
+int rsq_ref_sam_header(const rsq_ref *r, char *out, size_t cap, size_t *need);
 /* Reference::WriteFasta (reseq/Reference.cpp:896-916; `reseq replaceN` writes the reference after ReplaceN): FASTA, gzip when the
  * name ends in .gz */
 int rsq_ref_write_fasta(const rsq_ref *r, const char *path);
@@ -296,6 +300,26 @@ int rsq_sim_pairs(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev
 /* Simulator::SimulateAdapterOnlyPairs (reseq/Simulator.cpp:2359-2382): pairs [first, first+n) of the adapter-only share */
 int rsq_sim_adapter_only_pairs(rsq_sim *s, uint64_t first, uint64_t n, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len,
                                void *stream);
+
+/* Truth alignments: the two calls above, and in the same call the SAM text of the same pairs -- where every read really came from -- written on the device from the
+ * arrays the FASTQ text is written from (reseq_amd/csrc/rsq_sam.h; the reference keeps this in the read id only, Simulator.cpp:596-632).  Two records per pair in
+ * the FASTQ files' pair order, the mate of file 1 first, one line each, tab-separated:
+ *   QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL XC:Z:<cigar> XE:i:<errors>
+ * QNAME = the id line up to its first blank, without '@'; XC / XE = the CIGAR and the error count exactly as the id prints them.  The SAM CIGAR is the template part
+ * of ReSeq's (its M / D / I elements; zero-length elements dropped, equal neighbours merged, D at either end dropped and POS moved behind a dropped D at the
+ * reference's left end) and ONE S element for everything behind it (adapter, tail).  The mate with segment == strand reads forward: POS = start + 1 (+ dropped D);
+ * the other is reverse (flag 0x10): POS = end - template bases + 1 (+ dropped D), CIGAR from the last element down with the clip first, SEQ reverse-complemented,
+ * QUAL reversed.  QUAL is Phred+33 whatever the profile's offset.  MAPQ 60, RNEXT "=", PNEXT the mate's POS, TLEN from the leftmost POS to the rightmost
+ * aligned base, positive for the mate with the smaller POS (segment 0 on a tie); flags 99 / 147 (strand 0), 83 / 163 (strand 1).  Adapter-only pairs (fragment
+ * length 0, and all pairs of rsq_sim_adapter_only_pairs_sam) are unmapped: flags 77 / 141, "*" / 0 fields, SEQ and QUAL as in the FASTQ.
+ * rsq_ref_sam_header gives the header.  RSQ_ENOSPC: all three needed sizes are reported; the SAM text is written only if all three texts fit, each FASTQ text as by
+ * rsq_sim_pairs.  A simulator whose reference has variants (rsq_ref_read_variants) is refused with RSQ_EINVAL: coordinates through an allele's insertions and
+ * deletions are not worked out.  Methylation is fine (only bases change).  Kernel times: "sam_sizes", "sam_write".  rsq_sim_pairs, rsq_sim_adapter_only_pairs and
+ * the job calls launch neither. */
+int rsq_sim_pairs_sam(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len,
+                      char *sam_dev, size_t sam_cap, size_t *sam_len, uint64_t *n_pairs, rsq_fragment *frags_dev, size_t frags_cap, void *stream);
+int rsq_sim_adapter_only_pairs_sam(rsq_sim *s, uint64_t first, uint64_t n, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len,
+                                   char *sam_dev, size_t sam_cap, size_t *sam_len, void *stream);
 
 /* Simulator::ApplyErrorsAndQualityToFastaInput with the FASTA header already parsed (reseq/Simulator.cpp:2403-2512):
  * n records of `read_len` template bases each.  Inputs (device): seqs[n][read_len] base codes 0..3, seg[n] template

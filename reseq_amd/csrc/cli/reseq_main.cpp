@@ -585,6 +585,20 @@ int illumina_pe(const Args &a) {
         return 1;
     }
     const std::string out1 = a.get("firstReadsOut", "reseq-R1.fq"), out2 = a.get("secondReadsOut", "reseq-R2.fq");      // main.cpp:404,412
+    // --truthSam: where every read really came from, as SAM records written on the device beside the FASTQ text (rsq_sim_pairs_sam); plain or .gz
+    const std::string truth = a.get("truthSam", "");
+    if (a.has("truthSam") && truth.empty()) {
+        ERR("--truthSam needs a file name");
+        return 1;
+    }
+    if (!truth.empty() && rsq::textio::has_suffix(truth, ".bz2")) {
+        ERR("--truthSam: bzip2 output is not supported (write .gz or plain SAM)");
+        return 1;
+    }
+    if (!truth.empty() && !vcf_path.empty()) {
+        ERR("--truthSam: truth alignments are not available for a reference with variants (-V)");
+        return 1;
+    }
     rsq_profile *prof = nullptr;
     rsq_ref *ref = nullptr;
     rsq_sim *sim = nullptr;
@@ -615,6 +629,15 @@ int illumina_pe(const Args &a) {
             ok = false;
         }
         if (ok) n_workers = a.has("gpus") ? (int)asked : (int)std::min<uint64_t>(std::max<uint64_t>(asked, 1), (uint64_t)n_devices);
+        if (ok && n_workers > 1 && !truth.empty()) {
+            if (a.has("gpus")) {
+                ERR("--truthSam: truth alignments are written by one worker only (run without --gpus, or with --gpus 1)");
+                ok = false;
+            } else {
+                WARN("-j: truth alignments (--truthSam) are written by one worker only; one worker runs");
+                n_workers = 1;
+            }
+        }
     }
     if (ok && n_workers > 1) {
         const bool gz = rsq::textio::has_suffix(out1, ".gz");
@@ -678,23 +701,30 @@ int illumina_pe(const Args &a) {
     }
     if (ok && !sys_read.empty()) ok = check(rsq_sim_read_sys_errors(sim, sys_read.c_str()), "Could not read systematic error profile");
     trace.at("prepared");
-    AsyncOut f1, f2;
+    AsyncOut f1, f2, f3;                                         // f3: the truth alignments
     // .gz outputs: the text of every call becomes gzip members on the device (rsq_sim_gzip_device) -- a third of the bytes cross the link and the writer threads
     // only write (--rsqOption host_gzip:1: zlib on host threads behind the writers, as before)
     int64_t host_gzip = 0;
     rsq_get_option("host_gzip", &host_gzip);
     const bool gz1 = !host_gzip && rsq::textio::has_suffix(out1, ".gz"), gz2 = !host_gzip && rsq::textio::has_suffix(out2, ".gz");
-    if (ok && (gz1 || gz2)) rsq_sim_gzip_keep_code(sim, 1);      // one Huffman code for the run: the first batch's sample
+    const bool gz3 = !host_gzip && rsq::textio::has_suffix(truth, ".gz");
+    // one Huffman code for the run: the first batch's sample (FASTQ text alone: SAM text is another kind, its calls take their own code)
+    if (ok && (gz1 || gz2) && !gz3) rsq_sim_gzip_keep_code(sim, 1);
     {                                                            // files of device-made members (BGZF blocks) end with BGZF's end-of-file member
         char eof[32];
         const size_t n = rsq_gzip_eof_member(eof, sizeof eof);
         if (gz1) f1.tail.assign(eof, n);
         if (gz2) f2.tail.assign(eof, n);
+        if (gz3) f3.tail.assign(eof, n);
     }
     if (ok) {
         const bool o1 = f1.open(out1, gz1), o2 = f2.open(out2, gz2);
         if (!o1 || !o2) {
             ERR("Could not open '" << (o1 ? out2 : out1) << "' for writing.");
+            ok = false;
+        }
+        if (ok && !truth.empty() && !f3.open(truth, gz3)) {
+            ERR("Could not open '" << truth << "' for writing.");
             ok = false;
         }
     }
@@ -703,8 +733,8 @@ int illumina_pe(const Args &a) {
         rsq_sim_get_info(sim, &info);
         INFO("Aiming for " << info.total_pairs + info.adapter_only_pairs << " read pairs");
         INFO("Starting read generation");
-        DevBuffer d1, d2, g1, g2;
-        d1.device = d2.device = g1.device = g2.device = (int)device;
+        DevBuffer d1, d2, g1, g2, d3, g3;
+        d1.device = d2.device = g1.device = g2.device = d3.device = g3.device = (int)device;
         uint64_t written = 0;
         // a call's text of one file as members in `g`: true and the members' size, or false
         auto members = [&](bool gz, DevBuffer &d, size_t &len, DevBuffer &g) {
@@ -716,6 +746,16 @@ int illumina_pe(const Args &a) {
             len = packed;
             return check(rc, "Compressing the output failed");
         };
+        const bool sam = !truth.empty();
+        if (ok && sam) {                                         // the header, through the same route as the records
+            size_t need = 0, l3 = 0;
+            rsq_ref_sam_header(ref, nullptr, 0, &need);
+            std::string header(need, '\0');
+            ok = check(rsq_ref_sam_header(ref, &header[0], need, &need), "SAM header") && d3.ensure(need + 4096) &&
+                 check(rsq_dev_upload((int)device, d3.p, header.data(), need), "upload");
+            l3 = need;
+            ok = ok && members(gz3, d3, l3, g3) && f3.push(gz3 ? g3 : d3, l3);
+        }
         // about 12 M pairs per call: large launches keep the persistent read kernel's tail short (one call of 14.5 M pairs runs at 179 M pairs/s, calls of 2.4 M at
         // 154 M), and sparse coverage needs long block ranges
         const double pairs_per_block = (double)info.total_pairs / std::max<uint32_t>(1u, info.total_blocks);
@@ -724,31 +764,44 @@ int illumina_pe(const Args &a) {
             const uint32_t hi = std::min(info.total_blocks + 1, lo + step);
             size_t l1 = 0, l2 = 0;
             uint64_t n = 0;
-            int rc = rsq_sim_pairs(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, &n, nullptr, 0, nullptr);
+            size_t l3 = 0;
+            auto call = [&] {
+                return sam ? rsq_sim_pairs_sam(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)d3.p, d3.cap, &l3, &n, nullptr, 0, nullptr)
+                           : rsq_sim_pairs(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, &n, nullptr, 0, nullptr);
+            };
+            int rc = call();
             if (rc == RSQ_ENOSPC) {
-                ok = d1.ensure(l1 + l1 / 8 + 4096) && d2.ensure(l2 + l2 / 8 + 4096);
-                if (ok) rc = rsq_sim_pairs(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, &n, nullptr, 0, nullptr);
+                ok = d1.ensure(l1 + l1 / 8 + 4096) && d2.ensure(l2 + l2 / 8 + 4096) && (!sam || d3.ensure(l3 + l3 / 8 + 4096));
+                if (ok) rc = call();
             }
             ok = ok && check(rc, "Simulation failed") && (n == 0 || (members(gz1, d1, l1, g1) && members(gz2, d2, l2, g2) && flush_pair(gz1 ? g1 : d1, l1, gz2 ? g2 : d2, l2, f1, f2)));
+            ok = ok && (!sam || n == 0 || (members(gz3, d3, l3, g3) && f3.push(gz3 ? g3 : d3, l3)));
             written += n;
             if (ok && n) INFO("Generated " << written << " read pairs (" << (info.total_pairs ? (written * 100 + info.total_pairs / 2) / info.total_pairs : 0) << "%).");
         }
         for (uint64_t first = 0; ok && first < info.adapter_only_pairs; first += 100000) {       // Simulator.cpp:2359-2382
             const uint64_t n = std::min<uint64_t>(100000, info.adapter_only_pairs - first);
             size_t l1 = 0, l2 = 0;
-            int rc = rsq_sim_adapter_only_pairs(sim, first, n, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, nullptr);
+            size_t l3 = 0;
+            auto call = [&] {
+                return sam ? rsq_sim_adapter_only_pairs_sam(sim, first, n, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)d3.p, d3.cap, &l3, nullptr)
+                           : rsq_sim_adapter_only_pairs(sim, first, n, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, nullptr);
+            };
+            int rc = call();
             if (rc == RSQ_ENOSPC) {
-                ok = d1.ensure(l1 + 4096) && d2.ensure(l2 + 4096);
-                if (ok) rc = rsq_sim_adapter_only_pairs(sim, first, n, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, nullptr);
+                ok = d1.ensure(l1 + 4096) && d2.ensure(l2 + 4096) && (!sam || d3.ensure(l3 + 4096));
+                if (ok) rc = call();
             }
             ok = ok && check(rc, "Simulation of adapter-only pairs failed") && members(gz1, d1, l1, g1) && members(gz2, d2, l2, g2) && flush_pair(gz1 ? g1 : d1, l1, gz2 ? g2 : d2, l2, f1, f2);
+            ok = ok && (!sam || (members(gz3, d3, l3, g3) && f3.push(gz3 ? g3 : d3, l3)));
         }
     }
     trace.at("last text handed to the writers");
     f1.close();
     f2.close();
+    f3.close();
     trace.at("files closed");
-    ok = ok && f1.good() && f2.good();
+    ok = ok && f1.good() && f2.good() && f3.good();
     rsq_sim_free(sim);
     rsq_ref_free(ref);
     rsq_profile_free(prof);
@@ -757,6 +810,7 @@ int illumina_pe(const Args &a) {
         ERR("An error occurred in the process: Terminating simulation");
         remove(out1.c_str());
         remove(out2.c_str());
+        if (!truth.empty()) remove(truth.c_str());
         return 1;
     }
     INFO("Simulation finished succesfully");
@@ -976,6 +1030,7 @@ const char *kUsage =
     "Usage:  reseq <command> [options]\n"
     "Commands:\n"
     "  illuminaPE\t\tsimulates illumina paired-end data from a fitted profile (-s) and a reference (-R)\n"
+    "                 \t--truthSam truth.sam[.gz]: where every read really came from, as SAM records (header, two records per pair in the files' order; not with -V, one worker)\n"
     "  seqToIllumina\t\tapplies illumina quality and error model to input sequences (alias: replaceQuals)\n"
     "                 \t-i in.fa[.gz|.bz2] (stdin) -o out.fq[.gz|.bz2] (stdout) -s profile; --readThreads N, --traceStages;\n"
     "                 \t--inputFrom / --inputTo BYTE, --firstRecord K: a share of a plain input (python -m reseq_amd.simulate seqToIllumina works them out)\n"

@@ -1,0 +1,411 @@
+// rsq_sam.h -- truth alignments: one SAM record per simulated read, written on the device from the arrays the FASTQ text is written from (the raw rows of the
+// read kernel, rsq_reads.h RawLayout, and the fragment list).  ReSeq keeps a read's origin only in its id ("...:{start}:{ref}:{end}:... {CIGAR} E{n}",
+// Simulator.cpp:596-632) -- with a CIGAR that is not SAM's (0M / 0S elements, I and D inside the adapter part, H for bases that are in the read), in read
+// orientation and with an end coordinate for the reverse mate; ART, Mason and dwgsim write a truth SAM beside their reads for that reason.
+//
+// The record (DESIGN.md "Truth alignments" states the rules): two per pair, the mate of template segment 0 first, tab-separated
+//   QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL XC:Z:<the id's CIGAR> XE:i:<the id's error count>
+// Only the template part of a read (ReadMeta::n_iter_m iterations, ops M / D / I) is alignment: q read bases (M, I) over t template bases (M, D); everything
+// behind it -- adapter, tail -- is ONE S element of read_len - q bases.  Elements of equal op merge, D at either end of the template part is dropped (dL at the
+// reference's left end moves POS).  A forward mate (segment == strand) covers [start, start + t), a reverse mate [end - t, end): its CIGAR is replayed from the
+// last op down, its bases are the reverse complement, its qualities reversed.  Adapter-only pairs are unmapped (flags 77 / 141).
+//
+// Per lane, host and device (tests/hostemu/sam_trial.cpp runs them on the CPU): sam_walk, sam_align, sam_cigar, sam_line, sam_record_size, sam_record.
+// Kernels: k_sam_sizes (one lane per pair: both mates' walks into a side array, the pair's bytes), k_sam_write (one wave per 16 pairs, four lanes a pair, through
+// an LDS image of the wave's byte range like k_format_write, rsq_format.h).  Not part of what hiprtc compiles for a profile (rsq_spec.h): nothing of the read
+// kernel's text includes this file.
+#pragma once
+#include "rsq_text.h"
+#include "rsq_reads.h"
+
+namespace rsq {
+
+// what the ops of one mate's template part come to (k_sam_sizes keeps it so that the writer does not walk them again)
+struct SamMate {
+    uint16_t q, t;             // read bases (M + I) and template bases (M + D) of the template part
+    uint16_t lead, trail;      // D iterations at its first and last end in READ order: dropped from the CIGAR
+    uint16_t cigar_chars;      // length of the SAM CIGAR
+    uint16_t pad;
+    uint32_t bytes;            // of the mate's record
+};
+static_assert(sizeof(SamMate) == 16, "two mates are one 32-byte load");
+struct SamPair {
+    SamMate mate[2];
+};
+
+RSQ_HD uint32_t sam_op_at(const WordColumn &ops, uint32_t it) { return (ops.at(it >> 4) >> ((it & 15u) * 2u)) & 3u; }      // 0 M, 1 D, 2 I (fill_read_part, rsq_core.h)
+
+RSQ_HD SamMate sam_walk(const WordColumn &ops, const ReadMeta &m) {
+    SamMate w{};
+    const uint32_t n = m.n_iter_m;
+    uint32_t chars = 0;
+    if (m.plain) {
+        w.q = w.t = (uint16_t)n;
+        if (n) chars = digits_u32(n) + 1u;
+    } else {
+        uint32_t q = 0, t = 0, run = 0, cur = 3u, runs = 0;
+        auto flush = [&](bool last) {                                   // the run that ends here
+            if (!run) return;
+            if (cur == 1u && runs == 1u) w.lead = (uint16_t)run;       // (a template part of D alone is all lead)
+            else if (cur == 1u && last) w.trail = (uint16_t)run;
+            else chars += digits_u32(run) + 1u;
+        };
+        for (uint32_t it = 0; it < n; ++it) {
+            if (!(it & 15u) && it + 16u <= n && !ops.at(it >> 4)) {     // 16 plain iterations at once
+                if (cur != 0u) {
+                    flush(false);
+                    cur = 0u;
+                    run = 0;
+                    ++runs;
+                }
+                run += 16u;
+                q += 16u;
+                t += 16u;
+                it += 15u;
+                continue;
+            }
+            const uint32_t c = sam_op_at(ops, it);
+            if (c != cur) {
+                flush(false);
+                cur = c;
+                run = 0;
+                ++runs;
+            }
+            ++run;
+            q += c != 1u;
+            t += c != 2u;
+        }
+        flush(true);
+        w.q = (uint16_t)q;
+        w.t = (uint16_t)t;
+    }
+    const uint32_t clip = (uint32_t)m.read_len - w.q;
+    if (clip) chars += digits_u32(clip) + 1u;
+    w.cigar_chars = (uint16_t)(chars ? chars : 1u);                     // nothing left: "*"
+    return w;
+}
+
+// The CIGAR: the template part's elements in read order and the clip behind them, or (reverse) the clip and the elements from the last op down
+template <class Sink>
+RSQ_HD void sam_cigar(const WordColumn &ops, const ReadMeta &m, const SamMate &w, bool reverse, Sink &t) {
+    const uint32_t clip = (uint32_t)m.read_len - w.q;
+    bool any = false;
+    if (reverse && clip) {
+        t.element('S', clip);
+        any = true;
+    }
+    if (m.plain) {
+        if (m.n_iter_m) {
+            t.element('M', m.n_iter_m);
+            any = true;
+        }
+    } else {
+        const uint32_t lo = w.lead, hi = (uint32_t)m.n_iter_m - w.trail;
+        uint32_t cur = 3u, run = 0;
+        for (uint32_t i = lo; i < hi; ++i) {
+            const uint32_t it = reverse ? hi - 1u - (i - lo) : i;
+            // 16 plain iterations at once: the word that holds `it` lies inside the range, and the replay stands at its first (reverse: last) op
+            if ((reverse ? (it & 15u) == 15u && it >= lo + 15u : !(it & 15u) && it + 16u <= hi) && (cur == 0u || !run) && !ops.at(it >> 4)) {
+                cur = 0u;
+                run += 16u;
+                i += 15u;
+                continue;
+            }
+            const uint32_t c = sam_op_at(ops, it);
+            if (c != cur) {
+                if (run) t.element(cur == 0u ? 'M' : cur == 1u ? 'D' : 'I', run);
+                cur = c;
+                run = 0;
+            }
+            ++run;
+        }
+        if (run) {
+            t.element(cur == 0u ? 'M' : cur == 1u ? 'D' : 'I', run);
+            any = true;
+        }
+    }
+    if (!reverse && clip) {
+        t.element('S', clip);
+        any = true;
+    }
+    if (!any) t.ch('*');
+}
+
+// Where a mate aligns, from the fragment and both mates' walks
+struct SamAlign {
+    uint32_t flag, pos, pnext;
+    int32_t tlen;
+    uint32_t mapped, reverse;
+};
+RSQ_HD SamAlign sam_align(bool has_f, const Fragment &f, uint32_t seg, const SamMate &w0, const SamMate &w1) {
+    SamAlign a{};
+    if (!has_f || !f.len) {                                             // adapter-only: unmapped
+        a.flag = seg ? 141u : 77u;
+        return a;
+    }
+    const uint32_t end = f.start + f.len;
+    int32_t pos[2], last[2];
+    for (uint32_t s = 0; s < 2u; ++s) {
+        const SamMate &w = s ? w1 : w0;
+        const bool rev = s != f.strand;                                 // fragment_src (rsq_reads.h): src.reverse = seg != f.strand
+        const uint32_t d_left = rev ? w.trail : w.lead, d_right = rev ? w.lead : w.trail;
+        pos[s] = (int32_t)((rev ? end - w.t : f.start) + 1u + d_left);
+        last[s] = pos[s] + (int32_t)((uint32_t)w.t - d_left - d_right) - 1;
+    }
+    const uint32_t o = seg ^ 1u;
+    const bool rev = seg != f.strand;
+    a.mapped = 1u;
+    a.reverse = rev ? 1u : 0u;
+    a.flag = 0x1u | 0x2u | (rev ? 0x10u : 0x20u) | (seg ? 0x80u : 0x40u);      // (the mates of a pair read opposite strands)
+    a.pos = (uint32_t)pos[seg];
+    a.pnext = (uint32_t)pos[o];
+    const int32_t span = (last[0] > last[1] ? last[0] : last[1]) - (pos[0] < pos[1] ? pos[0] : pos[1]) + 1;
+    const bool leftmost = pos[seg] < pos[o] || (pos[seg] == pos[o] && seg == 0u);
+    a.tlen = leftmost ? span : -span;
+    return a;
+}
+
+// QNAME: the id line of format_header (rsq_text.h) without '@', up to its first blank
+template <class Sink>
+RSQ_HD void sam_qname(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, Sink &t) {
+    t.str(names.base_identifier, names.base_len);
+    if (has_f) {
+        const uint32_t end = f.start + f.len;
+        t.num(f.block);
+        t.ch('_');
+        t.num(f.number);
+        t.ch(':');
+        t.num(f.strand ? end : f.start + 1u);
+        t.ch(':');
+        t.str(names.names + names.name_ptr[f.seq], names.name_ptr[f.seq + 1] - names.name_ptr[f.seq]);
+        t.ch(':');
+        t.num(f.strand ? f.start + 1u : end);
+    } else {
+        t.ch('0');
+        t.ch('_');
+        t.num(adapter_only_number);
+        t.str(":0:Adapter:0", 12);
+    }
+    t.ch(':');
+    t.num((uint32_t)S.tiles[m.tile_id]);
+    t.str(":1337:1337", 10);
+}
+RSQ_HD uint32_t sam_qname_size(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m) {
+    uint32_t n = names.base_len + 1u + digits_u32(S.tiles[m.tile_id]) + 10u;
+    if (has_f) {
+        const uint32_t end = f.start + f.len;
+        n += digits_u32(f.block) + 1u + digits_u32(f.number) + 1u + digits_u32(f.start + 1u) + 1u + (names.name_ptr[f.seq + 1] - names.name_ptr[f.seq]) + 1u + digits_u32(end);
+    } else n += 2u + digits_u64(adapter_only_number) + 12u;
+    return n;
+}
+RSQ_HD uint32_t sam_tlen_chars(int32_t v) { return v < 0 ? 1u + digits_u32((uint32_t)-(int64_t)v) : digits_u32((uint32_t)v); }
+
+// the record's three stretches: everything in front of SEQ (with its tab) ...
+template <class Sink>
+RSQ_HD void sam_head(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &ops, const SamMate &w,
+                     const SamAlign &a, Sink &t) {
+    sam_qname(S, names, has_f, f, adapter_only_number, m, t);
+    t.ch('\t');
+    t.num(a.flag);
+    t.ch('\t');
+    if (a.mapped) {
+        t.str(names.names + names.name_ptr[f.seq], names.name_ptr[f.seq + 1] - names.name_ptr[f.seq]);
+        t.ch('\t');
+        t.num(a.pos);
+        t.str("\t60\t", 4);
+        sam_cigar(ops, m, w, a.reverse != 0u, t);
+        t.str("\t=\t", 3);
+        t.num(a.pnext);
+        t.ch('\t');
+        if (a.tlen < 0) {
+            t.ch('-');
+            t.num((uint32_t)-(int64_t)a.tlen);
+        } else t.num((uint32_t)a.tlen);
+        t.ch('\t');
+    } else t.str("*\t0\t0\t*\t*\t0\t0\t", 14);
+}
+RSQ_HD uint32_t sam_head_size(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, const SamMate &w, const SamAlign &a) {
+    uint32_t n = sam_qname_size(S, names, has_f, f, adapter_only_number, m) + 1u + digits_u32(a.flag) + 1u;
+    if (a.mapped)
+        n += (names.name_ptr[f.seq + 1] - names.name_ptr[f.seq]) + 1u + digits_u32(a.pos) + 4u + w.cigar_chars + 3u + digits_u32(a.pnext) + 1u + sam_tlen_chars(a.tlen) + 1u;
+    else n += 14u;
+    return n;
+}
+// ... SEQ or QUAL (no tab, no line end): the row's words as they lie, or from the last one down -- a read length that is no multiple of four takes every output
+// word from two neighbours --, bytes reversed; bases as letters (reverse: the complement's), qualities moved from the profile's offset to Phred+33
+RSQ_HD uint32_t sam_byte_reverse(uint32_t w) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(0u, w, 0x00010203u);
+#else
+    return (w >> 24) | ((w >> 8) & 0xFF00u) | ((w << 8) & 0xFF0000u) | (w << 24);
+#endif
+}
+RSQ_HD uint32_t sam_complement_letters(uint32_t codes) {                // bytes 0..3 -> "TGCA" (3 - code), 4 -> 'N'
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(0x4E4E4E4Eu, 0x41434754u, codes);
+#else
+    uint32_t out = 0;
+    for (uint32_t k = 0; k < 4u; ++k) {
+        const uint32_t b = (codes >> (8u * k)) & 0xFFu;
+        out |= (uint32_t)("TGCAN"[b < 4u ? b : 4u]) << (8u * k);
+    }
+    return out;
+#endif
+}
+RSQ_HD uint32_t sam_funnel(uint32_t hi, uint32_t lo, uint32_t bytes) {   // (hi:lo) >> 8 * bytes, bytes < 4
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_alignbyte(hi, lo, bytes);
+#else
+    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8u * bytes));
+#endif
+}
+template <class Sink>
+RSQ_HD void sam_line(const WordColumn &row, uint32_t read_len, bool is_qual, bool reverse, uint32_t phred_offset, Sink &t) {
+    const uint32_t words = (read_len + 3u) >> 2, odd = read_len & 3u;
+    const uint32_t shift = ((phred_offset - 33u) & 0xFFu) * 0x01010101u;      // one packed subtract: no character is below the offset, so no byte borrows from a character
+    constexpr uint32_t kAhead = 10u;                                     // loads in flight
+    for (uint32_t i = 0; i < words; i += kAhead) {
+        uint32_t w[kAhead + 1u];
+#pragma unroll
+        for (uint32_t k = 0; k <= kAhead; ++k) {
+            const uint32_t j = i + k;                                    // output word j reads row word j, or (reverse) words - 1 - j and the one below it
+            w[k] = j < words && (k < kAhead || (reverse && odd)) ? row.at(reverse ? words - 1u - j : j) : 0u;
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kAhead; ++k) {
+            if (i + k >= words) break;
+            uint32_t v = w[k];
+            if (reverse) v = sam_byte_reverse(odd ? sam_funnel(w[k], w[k + 1u], odd) : v);
+            const uint32_t text = is_qual ? v - shift : reverse ? sam_complement_letters(v) : base_letters(v), left = read_len - 4u * (i + k);
+            t.bytes(text, left < 4u ? left : 4u);
+        }
+    }
+}
+// ... and the two tags with the line end
+template <class Sink>
+RSQ_HD void sam_tags(const ReadMeta &m, const WordColumn &ops, Sink &t) {
+    t.str("\tXC:Z:", 6);
+    cigar_replay(ops, m, t);
+    t.str("\tXE:i:", 6);
+    t.num((uint32_t)m.num_errors);
+    t.ch('\n');
+}
+RSQ_HD uint32_t sam_tags_size(const ReadMeta &m) { return 6u + m.cigar_chars + 6u + digits_u32(m.num_errors) + 1u; }
+
+// length of a record without producing it
+RSQ_HD uint32_t sam_record_size(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, const SamMate &w,
+                                const SamAlign &a) {
+    return sam_head_size(S, names, has_f, f, adapter_only_number, m, w, a) + 2u * m.read_len + 1u + sam_tags_size(m);
+}
+// the whole record at dst; returns its length
+template <class P>
+RSQ_HD uint32_t sam_record(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &seq,
+                           const WordColumn &qual, const WordColumn &ops, const SamMate &w, const SamAlign &a, P dst) {
+    WordSinkT<P> t(dst);
+    sam_head(S, names, has_f, f, adapter_only_number, m, ops, w, a, t);
+    sam_line(seq, m.read_len, false, a.reverse != 0u, S.phred_offset, t);
+    t.ch('\t');
+    sam_line(qual, m.read_len, true, a.reverse != 0u, S.phred_offset, t);
+    sam_tags(m, ops, t);
+    t.finish();
+    return t.n;
+}
+
+#if RSQ_DEVICE_BUILD
+// One lane per raw row pair (row i of both segments: the two mates of pair perm[i], or of pair i): the walks into side[row], the pair's bytes into sizes[pair]
+__global__ void __launch_bounds__(256) k_sam_sizes(DevSim S, NameTable names, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_only_first, RawLayout raw, const uint32_t *perm,
+                                                   SamPair *side, uint32_t *sizes) {
+    const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= n_pairs) return;
+    const uint64_t pair = perm ? perm[row] : row;
+    Fragment f{};
+    if (frags) f = frags[pair];
+    const ReadMeta m0 = raw.meta[row], m1 = raw.meta[n_pairs + row];
+    SamPair p;
+    p.mate[0] = sam_walk(raw.ops_of(row), m0);
+    p.mate[1] = sam_walk(raw.ops_of(n_pairs + row), m1);
+    const uint64_t ao_number = adapter_only_first + pair + 1u;
+    p.mate[0].bytes = sam_record_size(S, names, frags != nullptr, f, ao_number, m0, p.mate[0], sam_align(frags != nullptr, f, 0u, p.mate[0], p.mate[1]));
+    p.mate[1].bytes = sam_record_size(S, names, frags != nullptr, f, ao_number, m1, p.mate[1], sam_align(frags != nullptr, f, 1u, p.mate[0], p.mate[1]));
+    side[row] = p;
+    sizes[pair] = p.mate[0].bytes + p.mate[1].bytes;
+}
+
+// One wave per 16 consecutive raw rows = 16 pairs, four lanes a pair: lanes 0-15 write mate 0's record up to and with the tab behind SEQ, lanes 16-31 its QUAL and
+// tags, lanes 32-47 and 48-63 the same of mate 1.  As in k_format_write (rsq_format.h) the wave's 32 records are one contiguous byte range of the output: they are
+// formatted into an LDS image of that range with the destination's alignment modulo 16 and stored out in aligned 16-byte stores; PERM (the read kernel ran
+// binned by tile): the rows' pairs lie anywhere in the output, every pair has a slot of the image and its four lanes store it.  A wave whose text does not fit
+// the image writes it straight to HBM.  Nothing is written when any of the call's three texts exceeds its capacity so far (fastq_end: the FASTQ offsets' last
+// entries).
+constexpr uint32_t kSamPairs = 16, kSamLdsMax = 32u * 1024u, kSamLdsMin = 2048u;
+RSQ_HD uint32_t sam_lds_bytes(uint64_t pair_bytes, bool slots) {        // the image for pairs of at most pair_bytes; slots: each its own alignment
+    const uint64_t want = (kSamPairs * (pair_bytes + (slots ? 16u : 0u)) + 16u + 127u) & ~(uint64_t)127u;
+    return (uint32_t)(want < kSamLdsMin ? kSamLdsMin : want > kSamLdsMax ? kSamLdsMax : want);
+}
+template <bool PERM>
+__global__ void __launch_bounds__(64) k_sam_write(DevSim S, NameTable names, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_only_first, RawLayout raw, const SamPair *side,
+                                                 const uint64_t *offsets, char *dst, uint64_t cap, const uint64_t *fastq_end0, const uint64_t *fastq_end1, uint64_t fastq_cap0,
+                                                 uint64_t fastq_cap1, const uint32_t *perm, uint32_t lds_bytes) {
+    extern __shared__ __attribute__((aligned(16))) char s_sam[];
+    const uint32_t lane = threadIdx.x, pr = lane & (kSamPairs - 1u), part = lane / kSamPairs, seg = part >> 1, half = part & 1u;
+    const uint64_t first = (uint64_t)blockIdx.x * kSamPairs;
+    if (first >= n_pairs) return;
+    if (offsets[n_pairs] > cap || *fastq_end0 > fastq_cap0 || *fastq_end1 > fastq_cap1) return;      // a buffer of the call is too small: write nothing (RSQ_ENOSPC)
+    const uint64_t last = first + kSamPairs < n_pairs ? first + kSamPairs : n_pairs;
+    const uint64_t row = first + pr;
+    const bool active = row < last;
+    const uint64_t pair = PERM ? (active ? perm[row] : 0u) : row;
+    const uint64_t g_begin = PERM ? (active ? offsets[pair] : 0u) : offsets[first], g_end = PERM ? (active ? offsets[pair + 1u] : 0u) : offsets[last];
+    const uint32_t skew = (uint32_t)((uint64_t)(uintptr_t)(dst + g_begin) & 15u), bytes = (uint32_t)(g_end - g_begin);
+    const uint32_t kSlot = (lds_bytes / kSamPairs) & ~15u;
+    const bool through_lds = PERM ? __all(skew + bytes <= kSlot) != 0 : skew + bytes <= lds_bytes;      // wave-uniform
+    ReadMeta m{};
+    Fragment f{};
+    SamPair p{};
+    uint64_t r = 0;
+    if (active) {
+        r = (uint64_t)seg * n_pairs + row;
+        m = raw.meta[r];
+        p = side[row];
+        if (frags) f = frags[pair];
+    }
+    const bool has_f = frags != nullptr;
+    const WordColumn seq = raw.seq_of(r), qual = raw.qual_of(r), ops = raw.ops_of(r);
+    const uint64_t ao_number = adapter_only_first + pair + 1u;
+    const SamMate w = seg ? p.mate[1] : p.mate[0];
+    const SamAlign a = sam_align(has_f, f, seg, p.mate[0], p.mate[1]);
+    const uint32_t rec_at = seg ? p.mate[0].bytes : 0u;                // of the record within its pair's text
+    if (!through_lds) {
+        if (active && half == 0u) sam_record(S, names, has_f, f, ao_number, m, seq, qual, ops, w, a, dst + offsets[pair] + rec_at);
+        return;
+    }
+    const uint32_t slot_at = PERM ? pr * kSlot : 0u;
+    if (active) {
+        RSQ_LDS char *rec_text = (RSQ_LDS char *)s_sam + slot_at + skew + (PERM ? 0u : (uint32_t)(offsets[pair] - g_begin)) + rec_at;
+        const uint32_t qual_at = w.bytes - sam_tags_size(m) - m.read_len;
+        WordSinkT<RSQ_LDS char *> t(rec_text + (half ? qual_at : 0u));
+        if (half == 0u) {
+            sam_head(S, names, has_f, f, ao_number, m, ops, w, a, t);
+            sam_line(seq, m.read_len, false, a.reverse != 0u, S.phred_offset, t);
+            t.ch('\t');
+        } else {
+            sam_line(qual, m.read_len, true, a.reverse != 0u, S.phred_offset, t);
+            sam_tags(m, ops, t);
+        }
+        t.finish();
+    }
+    __syncthreads();
+    const uint32_t lo = skew, hi = skew + bytes;                                   // LDS byte range (within the slot) holding text
+    char *g_chunk0 = dst + g_begin - skew;                                         // 16-byte aligned
+    const char *s_from = s_sam + slot_at;
+    for (uint32_t c = (PERM ? part : lane) * 16u; c < hi; c += (PERM ? 64u / kSamPairs : 64u) * 16u) {
+        if (c >= lo && c + 16u <= hi) {
+            *reinterpret_cast<uint4 *>(g_chunk0 + c) = *reinterpret_cast<const uint4 *>(s_from + c);
+        } else {
+            for (uint32_t b = c < lo ? lo : c; b < c + 16u && b < hi; ++b) g_chunk0[b] = s_from[b];
+        }
+    }
+}
+#endif
+
+}  // namespace rsq

@@ -27,6 +27,7 @@
 #include "rsq_text.h"
 #include "rsq_reads.h"
 #include "rsq_format.h"
+#include "rsq_sam.h"
 #include "rsq_pack.h"
 #include "rsq_prepass.h"
 #include "rsq_spec.h"
@@ -202,6 +203,7 @@ struct rsq_sim : PrepassSim {
         DevBuf counts, offsets, tile_sums, scan_total, frags, raw_seq, raw_qual, raw_ops, raw_meta, sizes, off_r1, off_r2, fill_counters, hits, hit_count, cands, pairs_of, pair_off, templates, rec_flags, rec_index, rec_count;
         DevBuf bin_keys, bin_small, bin_perm, bin_frags, bin_fvars;      // reads binned by tile: key per item; histogram, bins, counters (one small buffer); the sorted items
         DevBuf fa_counts, fa_first, fa_at, fa_len, fa_id_len, fa_frag_len, fa_seg, fa_codes, fa_summary;      // rsq_sim_error_model_fasta (rsq_fasta.h)
+        DevBuf sam_sizes, sam_side, off_sam;      // truth alignments (rsq_sam.h): bytes per pair, both mates' walks per raw row, the pairs' offsets in the SAM text
         DevBuf cell_info;              // the sieve without variants: per candidate the first strand's count and the two strands (k_sieve_finish<0> -> k_sieve_emit<0>)
         hipEvent_t text_done = nullptr;      // the text stage that last read this set's arrays
     } ws[2];
@@ -238,6 +240,8 @@ struct rsq_sim : PrepassSim {
     uint64_t *mailbox = nullptr;   // pinned host words the hot path's few device-to-host scalars land in
     uint64_t format_record_bytes = 480;      // the longest FASTQ record of the last rsq_sim_pairs call and a few bytes (text_stage sizes the formatter's LDS image with it)
     DevBuf longest_record;                   // where a call's text stages leave it
+    DevBuf sam_totals, sam_longest;          // rsq_sim_pairs_sam: [sub-ranges + 1] bytes of SAM text in front of a sub-range; the call's longest pair of records
+    uint64_t sam_pair_bytes = 1100;          // that of the last call and a few bytes (sam_stage sizes the writer's LDS image with it)
     uint64_t record_text_bytes = 480;        // the same for the seqToIllumina records' text (error_model_text)
     int force_fill_mode = -1;      // RSQ_FILL_MODE=0: every draw in double precision from HBM (tests run both paths)
     // read kernels compiled for this simulator's profile (rsq_spec.h); `specialize`: option specialize when the simulator was created
@@ -646,6 +650,61 @@ static void text_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint
     s.timers["format_write"].stop(st);
     HIP_CHECK(hipGetLastError());
 }
+// What a call that also writes the truth alignments hands down: the caller's SAM buffer.  nullptr: the call launches neither kernel of rsq_sam.h.
+struct SamOut {
+    char *dst;
+    size_t cap;
+    size_t *len;
+};
+// SAM text of the pairs of reads_stage, behind their text_stage on the same stream (it reads the FASTQ offsets' totals: nothing is written unless all three texts
+// fit so far).  Offsets continue at sam_totals[part]; where the part ends goes to sam_totals[part + 1].
+static void sam_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_first, const ReadsDone &rd, char *r1, size_t r1_cap, char *r2, size_t r2_cap, const SamOut &sam,
+                      uint32_t part, hipStream_t st) {
+    rsq_sim::Workspace &w = *s.cur;
+    w.sam_sizes.reserve(n_pairs * 4 + 16);
+    w.sam_side.reserve(n_pairs * sizeof(SamPair) + 16);
+    w.off_sam.reserve((n_pairs + 1) * 8);
+    uint64_t *totals = s.sam_totals.as<uint64_t>();
+    s.timers["sam_sizes"].start(st);
+    hipLaunchKernelGGL(k_sam_sizes, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw, rd.row_order, w.sam_side.as<SamPair>(),
+                       w.sam_sizes.as<uint32_t>());
+    s.timers["sam_sizes"].stop(st);
+    exclusive_scan(s, w.sam_sizes.as<uint32_t>(), n_pairs, w.off_sam.as<uint64_t>(), st, totals + part, totals + part + 1);
+    hipLaunchKernelGGL(k_max_size, dim3(std::min<uint64_t>(1024, cdiv(n_pairs, 256))), dim3(256), 0, st, w.sam_sizes.as<uint32_t>(), n_pairs, s.sam_longest.as<uint32_t>());
+    const dim3 grid(cdiv(n_pairs, kSamPairs)), block(64);
+    const uint32_t lds = sam_lds_bytes(s.sam_pair_bytes, rd.row_order != nullptr);
+    const uint64_t cap = sam.dst ? sam.cap : 0, cap1 = r1 ? r1_cap : 0, cap2 = r2 ? r2_cap : 0;
+    s.timers["sam_write"].start(st);
+    if (rd.row_order)
+        hipLaunchKernelGGL(k_sam_write<true>, grid, block, lds, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw, w.sam_side.as<SamPair>(), w.off_sam.as<uint64_t>(), sam.dst, cap,
+                           w.off_r1.as<uint64_t>() + n_pairs, w.off_r2.as<uint64_t>() + n_pairs, cap1, cap2, rd.row_order, lds);
+    else
+        hipLaunchKernelGGL(k_sam_write<false>, grid, block, lds, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw, w.sam_side.as<SamPair>(), w.off_sam.as<uint64_t>(), sam.dst, cap,
+                           w.off_r1.as<uint64_t>() + n_pairs, w.off_r2.as<uint64_t>() + n_pairs, cap1, cap2, (const uint32_t *)nullptr, lds);
+    s.timers["sam_write"].stop(st);
+    HIP_CHECK(hipGetLastError());
+}
+static void begin_sam_totals(rsq_sim &s, uint32_t parts, hipStream_t st) {
+    s.sam_totals.reserve((size_t)(parts + 1) * 8 + 16);
+    s.sam_longest.reserve(8);
+    HIP_CHECK(hipMemsetAsync(s.sam_totals.as<uint64_t>(), 0, 8, st));
+    HIP_CHECK(hipMemsetAsync(s.sam_longest.as<uint32_t>(), 0, 4, st));
+}
+// the SAM side of finish_call: its copies are enqueued in front of it (finish_call waits for the stream), the result read behind it
+static void enqueue_sam_total(rsq_sim &s, uint32_t parts, hipStream_t text_stream) {
+    HIP_CHECK(hipMemcpyAsync(&s.mailbox[6], s.sam_totals.as<uint64_t>() + parts, 8, hipMemcpyDeviceToHost, text_stream));
+    s.mailbox[7] = 0;
+    HIP_CHECK(hipMemcpyAsync(&s.mailbox[7], s.sam_longest.as<uint32_t>(), 4, hipMemcpyDeviceToHost, text_stream));
+}
+static int finish_sam(rsq_sim &s, int rc, const SamOut &sam, size_t r1_len, size_t r2_len) {
+    *sam.len = s.mailbox[6];
+    if ((uint32_t)s.mailbox[7]) s.sam_pair_bytes = (uint32_t)s.mailbox[7] + 16u;
+    if (rc == RSQ_ENOSPC || (rc == RSQ_OK && (*sam.len > sam.cap || !sam.dst))) {
+        g_last_error = "output buffers too small: need " + std::to_string(r1_len) + " and " + std::to_string(r2_len) + " bytes of FASTQ text and " + std::to_string(*sam.len) + " of SAM text";
+        return RSQ_ENOSPC;
+    }
+    return rc;
+}
 static void reset_call_timers(rsq_sim &s) {
     for (auto &t : s.timers) t.second.reset();
 }
@@ -678,15 +737,23 @@ static void begin_totals(rsq_sim &s, uint32_t parts, hipStream_t st) {
 }
 
 // reads + FASTQ text of adapter-only pairs (Simulator::SimulateAdapterOnlyPairs, Simulator.cpp:2359-2382): one part on the caller's stream
-static int adapter_only_pairs(rsq_sim &s, uint64_t n_pairs, uint64_t adapter_first, char *r1, size_t r1_cap, size_t *r1_len, char *r2, size_t r2_cap, size_t *r2_len, hipStream_t st) {
+static int adapter_only_pairs(rsq_sim &s, uint64_t n_pairs, uint64_t adapter_first, char *r1, size_t r1_cap, size_t *r1_len, char *r2, size_t r2_cap, size_t *r2_len, hipStream_t st,
+                              const SamOut *sam = nullptr) {
     *r1_len = *r2_len = 0;
+    if (sam) *sam->len = 0;
     if (!n_pairs) return RSQ_OK;
     reset_call_timers(s);
     s.cur = &s.ws[0];
     begin_totals(s, 1, st);
+    if (sam) begin_sam_totals(s, 1, st);
     const ReadsDone rd = reads_stage(s, nullptr, n_pairs, adapter_first, st, nullptr);
     text_stage(s, nullptr, n_pairs, adapter_first, rd, r1, r1_cap, r2, r2_cap, 0, st, nullptr);
-    return finish_call(s, 1, false, r1, r1_cap, r1_len, r2, r2_cap, r2_len, st);
+    if (sam) {
+        sam_stage(s, nullptr, n_pairs, adapter_first, rd, r1, r1_cap, r2, r2_cap, *sam, 0, st);
+        enqueue_sam_total(s, 1, st);
+    }
+    const int rc = finish_call(s, 1, false, r1, r1_cap, r1_len, r2, r2_cap, r2_len, st);
+    return sam ? finish_sam(s, rc, *sam, *r1_len, *r2_len) : rc;
 }
 
 // The sieve of one block range on the current workspace: attempt 0 is launched without waiting; collect() waits for it, and if a list overflowed
@@ -849,11 +916,12 @@ static int check_block_range(const rsq_sim &s, uint32_t block_lo, uint32_t block
     return RSQ_OK;
 }
 static int sim_pairs(rsq_sim &s, uint32_t block_lo, uint32_t block_hi, char *r1, size_t r1_cap, size_t *r1_len, char *r2, size_t r2_cap, size_t *r2_len, uint64_t *n_pairs,
-                     rsq_fragment *frags_out, size_t frags_cap, hipStream_t st) {
+                     rsq_fragment *frags_out, size_t frags_cap, hipStream_t st, const SamOut *sam = nullptr) {
     if (const int rc = check_block_range(s, block_lo, block_hi)) return rc;
     HIP_CHECK(hipSetDevice(s.device));
     *n_pairs = 0;
     *r1_len = *r2_len = 0;
+    if (sam) *sam->len = 0;
     if (block_lo == block_hi) return RSQ_OK;
     reset_call_timers(s);
     const int vm = s.variants_mode;
@@ -866,6 +934,7 @@ static int sim_pairs(rsq_sim &s, uint32_t block_lo, uint32_t block_hi, char *r1,
         HIP_CHECK(hipStreamWaitEvent(s_text, s.ev_call, 0));
     }
     begin_totals(s, parts, s_text);
+    if (sam) begin_sam_totals(s, parts, s_text);
     struct Abort {                                                   // an error in the middle: nothing of the call may still run when it returns
         rsq_sim &s;
         bool armed = true;
@@ -914,8 +983,10 @@ static int sim_pairs(rsq_sim &s, uint32_t block_lo, uint32_t block_hi, char *r1,
                 HIP_CHECK(hipStreamWaitEvent(s_text, s.ev_fill, 0));
             }
             text_stage(s, frags, n, 0, rd, r1, r1_cap, r2, r2_cap, k, s_text, fvars);
+            if (sam) sam_stage(s, frags, n, 0, rd, r1, r1_cap, r2, r2_cap, *sam, k, s_text);
         } else {                                                     // no pairs in this part: its text ends where it begins
             HIP_CHECK(hipMemcpyAsync(s.totals.as<uint64_t>() + 2 * (k + 1), s.totals.as<uint64_t>() + 2 * k, 16, hipMemcpyDeviceToDevice, s_text));
+            if (sam) HIP_CHECK(hipMemcpyAsync(s.sam_totals.as<uint64_t>() + k + 1, s.sam_totals.as<uint64_t>() + k, 8, hipMemcpyDeviceToDevice, s_text));
         }
         if (parts > 1) HIP_CHECK(hipEventRecord(s.cur->text_done, s_text));
         total_pairs += n;
@@ -927,7 +998,9 @@ static int sim_pairs(rsq_sim &s, uint32_t block_lo, uint32_t block_hi, char *r1,
         }
     }
     *n_pairs = total_pairs;
-    const int rc = total_pairs ? finish_call(s, parts, s.has_variants, r1, r1_cap, r1_len, r2, r2_cap, r2_len, s_text) : (int)RSQ_OK;
+    if (sam && total_pairs) enqueue_sam_total(s, parts, s_text);
+    int rc = total_pairs ? finish_call(s, parts, s.has_variants, r1, r1_cap, r1_len, r2, r2_cap, r2_len, s_text) : (int)RSQ_OK;
+    if (sam && total_pairs) rc = finish_sam(s, rc, *sam, *r1_len, *r2_len);
     if (total_pairs && (rc == RSQ_OK || rc == RSQ_ENOSPC) && (uint32_t)s.mailbox[5]) s.format_record_bytes = (uint32_t)s.mailbox[5] + 8u;      // for the next call's text stage
     if (parts > 1) {                                                 // the caller's stream continues behind the whole call
         HIP_CHECK(hipStreamSynchronize(s_sieve));
@@ -1263,6 +1336,22 @@ int rsq_ref_sequence_name(const rsq_ref *r, uint32_t seq, char *out, size_t cap)
     const std::string name = r->r.first_part(seq);
     if (name.size() + 1 > cap) return RSQ_ENOSPC;
     memcpy(out, name.c_str(), name.size() + 1);
+    return RSQ_OK;
+}
+
+// the header of the truth alignments (rsq_sim_pairs_sam): host code
+int rsq_ref_sam_header(const rsq_ref *r, char *out, size_t cap, size_t *need) {
+    REQUIRE(r && need, "null argument");
+    std::string text = "@HD\tVN:1.6\tSO:unsorted\tGO:query\n";
+    for (uint32_t seq = 0; seq < r->r.codes.size(); ++seq) text += "@SQ\tSN:" + r->r.first_part(seq) + "\tLN:" + std::to_string(r->r.codes[seq].size()) + "\n";
+    text += "@PG\tID:reseq_amd\tPN:reseq_amd\n";
+    *need = text.size();
+    if (!out || cap < text.size()) {
+        g_last_error = "header buffer too small: need " + std::to_string(text.size()) + " bytes";
+        return RSQ_ENOSPC;
+    }
+    memcpy(out, text.data(), text.size());
+    if (cap > text.size()) out[text.size()] = 0;
     return RSQ_OK;
 }
 
@@ -1732,6 +1821,15 @@ int rsq_sim_pairs(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev
     REQUIRE(s && r1_len && r2_len && n_pairs, "null argument");
     return guard([&] { return sim_pairs(*s, block_lo, block_hi, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, n_pairs, frags_dev, frags_cap, (hipStream_t)stream); });
 }
+// truth alignments: coordinates through an allele's insertions and deletions are not worked out
+#define REQUIRE_NO_VARIANTS(s) REQUIRE(!(s)->has_variants, "truth alignments (SAM) are not available for a reference with variants (rsq_ref_read_variants)")
+int rsq_sim_pairs_sam(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len, char *sam_dev,
+                      size_t sam_cap, size_t *sam_len, uint64_t *n_pairs, rsq_fragment *frags_dev, size_t frags_cap, void *stream) {
+    REQUIRE(s && r1_len && r2_len && sam_len && n_pairs, "null argument");
+    REQUIRE_NO_VARIANTS(s);
+    const SamOut sam{sam_dev, sam_cap, sam_len};
+    return guard([&] { return sim_pairs(*s, block_lo, block_hi, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, n_pairs, frags_dev, frags_cap, (hipStream_t)stream, &sam); });
+}
 
 // ---- a rank's share, generated once and kept (include/reseq_amd.h rsq_sim_job_*)
 constexpr size_t kJobChunkBytes = (size_t)2 << 30, kJobSliceBytes = (size_t)32 << 20;
@@ -2175,6 +2273,16 @@ int rsq_sim_adapter_only_pairs(rsq_sim *s, uint64_t first, uint64_t n, char *r1_
     return guard([&] {
         HIP_CHECK(hipSetDevice(s->device));
         return adapter_only_pairs(*s, n, first, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, (hipStream_t)stream);
+    });
+}
+int rsq_sim_adapter_only_pairs_sam(rsq_sim *s, uint64_t first, uint64_t n, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len, char *sam_dev,
+                                   size_t sam_cap, size_t *sam_len, void *stream) {
+    REQUIRE(s && r1_len && r2_len && sam_len && s->prepared, "simulator not prepared");
+    REQUIRE_NO_VARIANTS(s);
+    const SamOut sam{sam_dev, sam_cap, sam_len};
+    return guard([&] {
+        HIP_CHECK(hipSetDevice(s->device));
+        return adapter_only_pairs(*s, n, first, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, (hipStream_t)stream, &sam);
     });
 }
 

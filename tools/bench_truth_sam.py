@@ -1,0 +1,64 @@
+#!/usr/bin/env python3
+"""What the truth alignments cost: python tools/bench_truth_sam.py [pairs] [steps] -- bench.py's headline workload (E. coli-sized reference, P0, 10 M pairs per
+step, one call per step) through rsq_sim_pairs and through rsq_sim_pairs_sam: pairs/s of both, kernel ms and launches of format_write, sam_sizes and sam_write
+(of the last step), the bytes of the three texts and the two writers' bytes/s.  One JSON line."""
+import json
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from reseq_amd import api, synth, workloads  # noqa: E402
+
+pairs = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
+steps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+tmp = tempfile.mkdtemp(prefix="rsq_sam_")
+ppath, fpath = os.path.join(tmp, "p0.rsqp"), os.path.join(tmp, "ref.fa")
+workloads.p0_profile(ppath)
+genome = max(200_000, int(4_641_652 * pairs / 10_000_000))
+synth.write_fasta(fpath, synth.make_reference(2, [genome], gc=0.508, names=[f"synthEcoli0 len={genome}"]))
+prof, ref = api.Profile(ppath), api.Reference(fpath, 11)
+sim = api.Simulator(prof, ref, 0)
+info = sim.prepare(11, pairs)
+lo, hi = 1, info.total_blocks + 1
+n, l1, l2, ls, rc = sim.pairs_sam_device(lo, hi, None, None, None)
+assert rc == api.RSQ_ENOSPC, rc
+r1, r2, sam = api.DeviceArray(0, l1 + 4096), api.DeviceArray(0, l2 + 4096), api.DeviceArray(0, ls + 4096)
+
+
+def sync():
+    api.lib().rsq_dev_download(0, (api.C.c_char * 8)(), r1.ptr, 8)      # a copy on the null stream: waits for the device
+
+
+def timed(call):
+    call()                                                             # warm-up: workspaces grown, the writers' images sized from this call's longest record
+    call()
+    sync()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        out = call()
+        assert out[-1] == api.RSQ_OK, out
+    sync()
+    return (time.perf_counter() - t0) / steps
+
+
+kernels = lambda names: {k: {"ms": round(sim.last_kernel_ms(k), 3), "launches": sim.last_kernel_launches(k)} for k in names}
+plain_s = timed(lambda: sim.pairs_device(lo, hi, r1, r2))
+plain_kernels = kernels(("format_write", "sam_sizes", "sam_write"))
+sam_s = timed(lambda: sim.pairs_sam_device(lo, hi, r1, r2, sam))
+sam_kernels = kernels(("fill_reads", "format_write", "sam_sizes", "sam_write"))
+gbps = lambda nbytes, ms: round(nbytes / ms / 1e6, 1) if ms else None
+print(json.dumps({
+    "workload": f"P0, one sequence of {genome} bases, {n} pairs per call", "steps": steps,
+    "pairs_per_s": {"rsq_sim_pairs": round(n / plain_s), "rsq_sim_pairs_sam": round(n / sam_s)},
+    "ms_per_call": {"rsq_sim_pairs": round(plain_s * 1e3, 2), "rsq_sim_pairs_sam": round(sam_s * 1e3, 2)},
+    "kernels_of_a_plain_call": plain_kernels, "kernels_of_a_sam_call": sam_kernels,
+    "bytes": {"fastq1": l1, "fastq2": l2, "sam": ls},
+    "GB_per_s": {"format_write": gbps(l1 + l2, sam_kernels["format_write"]["ms"]), "sam_write": gbps(ls, sam_kernels["sam_write"]["ms"])},
+}))
+for d in (r1, r2, sam):
+    d.free()
+sim.close()
