@@ -683,8 +683,9 @@ class Simulator:
             for d in ins + outs:
                 d.free()
 
-    def error_model_fastq(self, rec, ids, first_index=0, stream=None):
-        """the same records as FASTQ text formatted on the device: "@{id} {CIGAR} E{errors}" (Simulator.cpp:2497-2504); ids: list of bytes"""
+    def error_model_fastq(self, rec, ids, first_index=0, stream=None, text_len=None):
+        """the same records as FASTQ text formatted on the device: "@{id} {CIGAR} E{errors}" (Simulator.cpp:2497-2504); ids: list of bytes.
+        text_len: the text's length where the caller knows it (no call for the size in front)"""
         n, rl = rec["seqs"].shape
         dev = self.device
         ins = [DeviceArray.from_numpy(dev, np.ascontiguousarray(rec[k], dt)) for k, dt in
@@ -694,13 +695,14 @@ class Simulator:
         off[1:] = np.cumsum([len(x) for x in ids])
         ins.append(DeviceArray.from_numpy(dev, np.frombuffer(blob + b"\0", np.uint8)))
         ins.append(DeviceArray.from_numpy(dev, off))
-        need = C.c_size_t(0)
+        need = C.c_size_t(text_len or 0)
         text = None
         try:
-            rc = lib().rsq_sim_error_model_fastq(self.h, first_index, n, rl, ins[0].ptr, ins[1].ptr, ins[2].ptr, ins[3].ptr, ins[4].ptr, ins[5].ptr, ins[6].ptr,
-                                                 None, 0, C.byref(need), stream)
-            if rc != RSQ_ENOSPC:
-                _check(rc)
+            if text_len is None:
+                rc = lib().rsq_sim_error_model_fastq(self.h, first_index, n, rl, ins[0].ptr, ins[1].ptr, ins[2].ptr, ins[3].ptr, ins[4].ptr, ins[5].ptr, ins[6].ptr,
+                                                     None, 0, C.byref(need), stream)
+                if rc != RSQ_ENOSPC:
+                    _check(rc)
             text = DeviceArray(dev, need.value + 16)
             _check(lib().rsq_sim_error_model_fastq(self.h, first_index, n, rl, ins[0].ptr, ins[1].ptr, ins[2].ptr, ins[3].ptr, ins[4].ptr, ins[5].ptr, ins[6].ptr,
                                                    text.ptr, need.value + 16, C.byref(need), stream))

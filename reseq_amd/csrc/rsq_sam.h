@@ -12,11 +12,10 @@
 //
 // Per lane, host and device (tests/hostemu/sam_trial.cpp runs them on the CPU): sam_walk, sam_align, sam_cigar, sam_line, sam_record_size, sam_record.
 // Kernels: k_sam_sizes (one lane per pair: both mates' walks into a side array, the pair's bytes), k_sam_write (one wave per 16 pairs, four lanes a pair, through
-// an LDS image of the wave's byte range like k_format_write, rsq_format.h).  Not part of what hiprtc compiles for a profile (rsq_spec.h): nothing of the read
+// the wave's LDS image, WaveImage in rsq_format.h).  Not part of what hiprtc compiles for a profile (rsq_spec.h): nothing of the read
 // kernel's text includes this file.
 #pragma once
-#include "rsq_text.h"
-#include "rsq_reads.h"
+#include "rsq_format.h"
 
 namespace rsq {
 
@@ -331,12 +330,10 @@ __global__ void __launch_bounds__(256) k_sam_sizes(DevSim S, NameTable names, co
     sizes[pair] = p.mate[0].bytes + p.mate[1].bytes;
 }
 
-// One wave per 16 consecutive raw rows = 16 pairs, four lanes a pair: lanes 0-15 write mate 0's record up to and with the tab behind SEQ, lanes 16-31 its QUAL and
-// tags, lanes 32-47 and 48-63 the same of mate 1.  As in k_format_write (rsq_format.h) the wave's 32 records are one contiguous byte range of the output: they are
-// formatted into an LDS image of that range with the destination's alignment modulo 16 and stored out in aligned 16-byte stores; PERM (the read kernel ran
-// binned by tile): the rows' pairs lie anywhere in the output, every pair has a slot of the image and its four lanes store it.  A wave whose text does not fit
-// the image writes it straight to HBM.  Nothing is written when any of the call's three texts exceeds its capacity so far (fastq_end: the FASTQ offsets' last
-// entries).
+// One wave per 16 consecutive raw rows = 16 pairs, four lanes a pair, through the wave's image (WaveImage, rsq_format.h; the wave's 32 records are one
+// contiguous byte range of the output, PERM: a slot per pair): lanes 0-15 write mate 0's record up to and with the tab behind SEQ, lanes 16-31 its QUAL and
+// tags, lanes 32-47 and 48-63 the same of mate 1.  Nothing is written when any of the call's three texts exceeds its capacity so far (fastq_end: the FASTQ
+// offsets' last entries).
 constexpr uint32_t kSamPairs = 16, kSamLdsMax = 32u * 1024u, kSamLdsMin = 2048u;
 RSQ_HD uint32_t sam_lds_bytes(uint64_t pair_bytes, bool slots) {        // the image for pairs of at most pair_bytes; slots: each its own alignment
     const uint64_t want = (kSamPairs * (pair_bytes + (slots ? 16u : 0u)) + 16u + 127u) & ~(uint64_t)127u;
@@ -347,26 +344,20 @@ __global__ void __launch_bounds__(64) k_sam_write(DevSim S, NameTable names, con
                                                  const uint64_t *offsets, char *dst, uint64_t cap, const uint64_t *fastq_end0, const uint64_t *fastq_end1, uint64_t fastq_cap0,
                                                  uint64_t fastq_cap1, const uint32_t *perm, uint32_t lds_bytes) {
     extern __shared__ __attribute__((aligned(16))) char s_sam[];
-    const uint32_t lane = threadIdx.x, pr = lane & (kSamPairs - 1u), part = lane / kSamPairs, seg = part >> 1, half = part & 1u;
-    const uint64_t first = (uint64_t)blockIdx.x * kSamPairs;
-    if (first >= n_pairs) return;
+    using Image = WaveImage<PERM, kSamPairs>;
+    const uint32_t lane = threadIdx.x, part = lane / kSamPairs, seg = part >> 1, half = part & 1u;
+    if (Image::first() >= n_pairs) return;
     if (offsets[n_pairs] > cap || *fastq_end0 > fastq_cap0 || *fastq_end1 > fastq_cap1) return;      // a buffer of the call is too small: write nothing (RSQ_ENOSPC)
-    const uint64_t last = first + kSamPairs < n_pairs ? first + kSamPairs : n_pairs;
-    const uint64_t row = first + pr;
-    const bool active = row < last;
-    const uint64_t pair = PERM ? (active ? perm[row] : 0u) : row;
-    const uint64_t g_begin = PERM ? (active ? offsets[pair] : 0u) : offsets[first], g_end = PERM ? (active ? offsets[pair + 1u] : 0u) : offsets[last];
-    const uint32_t skew = (uint32_t)((uint64_t)(uintptr_t)(dst + g_begin) & 15u), bytes = (uint32_t)(g_end - g_begin);
-    const uint32_t kSlot = (lds_bytes / kSamPairs) & ~15u;
-    const bool through_lds = PERM ? __all(skew + bytes <= kSlot) != 0 : skew + bytes <= lds_bytes;      // wave-uniform
+    const Image im(offsets, n_pairs, dst, lds_bytes, perm, lane);
+    const uint64_t pair = im.item;
     ReadMeta m{};
     Fragment f{};
     SamPair p{};
     uint64_t r = 0;
-    if (active) {
-        r = (uint64_t)seg * n_pairs + row;
+    if (im.active) {
+        r = (uint64_t)seg * n_pairs + im.row;
         m = raw.meta[r];
-        p = side[row];
+        p = side[im.row];
         if (frags) f = frags[pair];
     }
     const bool has_f = frags != nullptr;
@@ -375,15 +366,13 @@ __global__ void __launch_bounds__(64) k_sam_write(DevSim S, NameTable names, con
     const SamMate w = seg ? p.mate[1] : p.mate[0];
     const SamAlign a = sam_align(has_f, f, seg, p.mate[0], p.mate[1]);
     const uint32_t rec_at = seg ? p.mate[0].bytes : 0u;                // of the record within its pair's text
-    if (!through_lds) {
-        if (active && half == 0u) sam_record(S, names, has_f, f, ao_number, m, seq, qual, ops, w, a, dst + offsets[pair] + rec_at);
+    if (!im.through_lds) {
+        if (im.active && half == 0u) sam_record(S, names, has_f, f, ao_number, m, seq, qual, ops, w, a, dst + offsets[pair] + rec_at);
         return;
     }
-    const uint32_t slot_at = PERM ? pr * kSlot : 0u;
-    if (active) {
-        RSQ_LDS char *rec_text = (RSQ_LDS char *)s_sam + slot_at + skew + (PERM ? 0u : (uint32_t)(offsets[pair] - g_begin)) + rec_at;
+    if (im.active) {
         const uint32_t qual_at = w.bytes - sam_tags_size(m) - m.read_len;
-        WordSinkT<RSQ_LDS char *> t(rec_text + (half ? qual_at : 0u));
+        WordSinkT<RSQ_LDS char *> t(im.item_text(s_sam) + rec_at + (half ? qual_at : 0u));
         if (half == 0u) {
             sam_head(S, names, has_f, f, ao_number, m, ops, w, a, t);
             sam_line(seq, m.read_len, false, a.reverse != 0u, S.phred_offset, t);
@@ -394,17 +383,7 @@ __global__ void __launch_bounds__(64) k_sam_write(DevSim S, NameTable names, con
         }
         t.finish();
     }
-    __syncthreads();
-    const uint32_t lo = skew, hi = skew + bytes;                                   // LDS byte range (within the slot) holding text
-    char *g_chunk0 = dst + g_begin - skew;                                         // 16-byte aligned
-    const char *s_from = s_sam + slot_at;
-    for (uint32_t c = (PERM ? part : lane) * 16u; c < hi; c += (PERM ? 64u / kSamPairs : 64u) * 16u) {
-        if (c >= lo && c + 16u <= hi) {
-            *reinterpret_cast<uint4 *>(g_chunk0 + c) = *reinterpret_cast<const uint4 *>(s_from + c);
-        } else {
-            for (uint32_t b = c < lo ? lo : c; b < c + 16u && b < hi; ++b) g_chunk0[b] = s_from[b];
-        }
-    }
+    im.store_out(s_sam);
 }
 #endif
 

@@ -595,6 +595,12 @@ static const uint32_t *launch_fill_records(rsq_sim &s, const RecordJob &job, con
     return with_fill_mask(s, "k_fill_records", [&](auto q) { return launch_records_mask<decltype(q)::value>(s, job, seg_dev, n, raw, st); });
 }
 
+// a text writer (one wave of 64 lanes per workgroup, rsq_format.h WaveImage): K<true> when the raw rows have an order (binned by tile), else K<false>
+template <class K, class... A>
+static void launch_text_waves(K with_order, K in_order, const uint32_t *row_order, dim3 grid, uint32_t lds, hipStream_t st, A... args) {
+    hipLaunchKernelGGL(row_order ? with_order : in_order, grid, dim3(64), lds, st, args...);
+}
+
 // ---- the stages of one (sub-)range; they work on the simulator's current workspace (s.cur)
 // reads of n_pairs pairs into the raw arrays (fragments on the device, or adapter-only pairs when frags == nullptr) and their record sizes
 struct ReadsDone {
@@ -635,18 +641,13 @@ static void text_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint
     exclusive_scan(s, w.sizes.as<uint32_t>(), n_pairs, w.off_r1.as<uint64_t>(), st, totals + 2 * part, totals + 2 * (part + 1));
     exclusive_scan(s, w.sizes.as<uint32_t>() + n_pairs, n_pairs, w.off_r2.as<uint64_t>(), st, totals + 2 * part + 1, totals + 2 * (part + 1) + 1);
     s.timers["scan"].stop(st);
-    const dim3 grid(cdiv(n_pairs, kFormatRecords), 2), block(64);
     // the wave's LDS image: sized by the longest record of the call before (the first call takes room for records of 480 bytes); binned rows have a slot per
     // record, each with its own alignment.  This call's longest record goes to totals' last word for the next one.
-    const uint32_t lds = rd.row_order ? std::min(kFormatLdsMax, format_lds_bytes(s.format_record_bytes) + 16u * kFormatRecords) : format_lds_bytes(s.format_record_bytes);
+    const uint32_t lds = format_lds_bytes(s.format_record_bytes, rd.row_order != nullptr);
     hipLaunchKernelGGL(k_max_size, dim3(std::min<uint64_t>(1024, cdiv(2 * n_pairs, 256))), dim3(256), 0, st, w.sizes.as<uint32_t>(), 2 * n_pairs, s.longest_record.as<uint32_t>());
     s.timers["format_write"].start(st);
-    if (rd.row_order)
-        hipLaunchKernelGGL(k_format_write<true>, grid, block, lds, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw, w.off_r1.as<uint64_t>(), w.off_r2.as<uint64_t>(), r1, r2,
-                           (uint64_t)(r1 ? r1_cap : 0), (uint64_t)(r2 ? r2_cap : 0), fvars, rd.row_order, lds);
-    else
-        hipLaunchKernelGGL(k_format_write<false>, grid, block, lds, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw, w.off_r1.as<uint64_t>(), w.off_r2.as<uint64_t>(), r1, r2,
-                           (uint64_t)(r1 ? r1_cap : 0), (uint64_t)(r2 ? r2_cap : 0), fvars, (const uint32_t *)nullptr, lds);
+    launch_text_waves(k_format_write<true>, k_format_write<false>, rd.row_order, dim3(cdiv(n_pairs, kFormatRecords), 2), lds, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw,
+                      w.off_r1.as<uint64_t>(), w.off_r2.as<uint64_t>(), r1, r2, (uint64_t)(r1 ? r1_cap : 0), (uint64_t)(r2 ? r2_cap : 0), fvars, rd.row_order, lds);
     s.timers["format_write"].stop(st);
     HIP_CHECK(hipGetLastError());
 }
@@ -671,16 +672,11 @@ static void sam_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint6
     s.timers["sam_sizes"].stop(st);
     exclusive_scan(s, w.sam_sizes.as<uint32_t>(), n_pairs, w.off_sam.as<uint64_t>(), st, totals + part, totals + part + 1);
     hipLaunchKernelGGL(k_max_size, dim3(std::min<uint64_t>(1024, cdiv(n_pairs, 256))), dim3(256), 0, st, w.sam_sizes.as<uint32_t>(), n_pairs, s.sam_longest.as<uint32_t>());
-    const dim3 grid(cdiv(n_pairs, kSamPairs)), block(64);
     const uint32_t lds = sam_lds_bytes(s.sam_pair_bytes, rd.row_order != nullptr);
     const uint64_t cap = sam.dst ? sam.cap : 0, cap1 = r1 ? r1_cap : 0, cap2 = r2 ? r2_cap : 0;
     s.timers["sam_write"].start(st);
-    if (rd.row_order)
-        hipLaunchKernelGGL(k_sam_write<true>, grid, block, lds, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw, w.sam_side.as<SamPair>(), w.off_sam.as<uint64_t>(), sam.dst, cap,
-                           w.off_r1.as<uint64_t>() + n_pairs, w.off_r2.as<uint64_t>() + n_pairs, cap1, cap2, rd.row_order, lds);
-    else
-        hipLaunchKernelGGL(k_sam_write<false>, grid, block, lds, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw, w.sam_side.as<SamPair>(), w.off_sam.as<uint64_t>(), sam.dst, cap,
-                           w.off_r1.as<uint64_t>() + n_pairs, w.off_r2.as<uint64_t>() + n_pairs, cap1, cap2, (const uint32_t *)nullptr, lds);
+    launch_text_waves(k_sam_write<true>, k_sam_write<false>, rd.row_order, dim3(cdiv(n_pairs, kSamPairs)), lds, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw,
+                      w.sam_side.as<SamPair>(), w.off_sam.as<uint64_t>(), sam.dst, cap, w.off_r1.as<uint64_t>() + n_pairs, w.off_r2.as<uint64_t>() + n_pairs, cap1, cap2, rd.row_order, lds);
     s.timers["sam_write"].stop(st);
     HIP_CHECK(hipGetLastError());
 }
@@ -1009,86 +1005,6 @@ static int sim_pairs(rsq_sim &s, uint32_t block_lo, uint32_t block_hi, char *r1,
     } else HIP_CHECK(hipStreamSynchronize(st));
     abort_guard.armed = false;
     return rc;
-}
-
-// seqToIllumina's FASTQ text on the device (Simulator.cpp:2497-2504: "@{id} {CIGAR} E{errors}", bases, "+", qualities): sizes, then the
-// records at the offsets of their exclusive scan; one lane per record, word-granular stores
-RSQ_HD uint32_t error_model_record_size(const ReadMeta &m, uint32_t id_len) { return 1u + id_len + 1u + m.cigar_chars + 2u + digits_u32(m.num_errors) + 1u + 2u * m.read_len + 4u; }
-// the records' ids: packed one after the other (off: n + 1 offsets) or where they stand in the FASTA text (at: offset of the record's '>', len: the id's length)
-struct RecordIds {
-    const char *chars;
-    const uint64_t *off;
-    const uint32_t *at, *len;
-    RSQ_HD const char *begin(uint64_t i) const { return chars + (off ? off[i] : (uint64_t)at[i] + 1u); }
-    RSQ_HD uint32_t length(uint64_t i) const { return off ? (uint32_t)(off[i + 1] - off[i]) : len[i]; }
-};
-__global__ void __launch_bounds__(256) k_record_text_sizes(RawLayout raw, uint64_t n, RecordIds ids, uint32_t *sizes) {
-    const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= n) return;
-    const uint64_t i = raw.item_of(row);
-    sizes[i] = error_model_record_size(raw.meta[row], ids.length(i));
-}
-// The text by waves, as k_format_write writes the pairs' (rsq_format.h): a wave takes 16 consecutive raw rows, four lanes per record (the header and the first
-// half of the bases, the second half, the two halves of the qualities), formats them into an LDS image of their contiguous stretch of the output and copies
-// the image out in aligned 16-byte stores; PERM (rows binned by tile): a slot of the image per record.  (One lane per record with word-granular stores, the
-// kernel of rounds 2-4, wrote 0.3 TB/s: 8.3 ms per 8 M records.)  A wave whose records do not fit the image writes them lane by lane.
-template <bool PERM>
-__global__ void __launch_bounds__(64) k_record_text_waves(RawLayout raw, uint64_t n, RecordIds ids, const uint64_t *offsets, char *dst, uint64_t cap, uint32_t lds_bytes) {
-    extern __shared__ __attribute__((aligned(16))) char s_text[];
-    constexpr uint32_t kLineParts = 32u / kFormatRecords;
-    const uint32_t lane = threadIdx.x, rec = lane & (kFormatRecords - 1u), part = lane / kFormatRecords, sub = part % kLineParts;
-    const bool is_qual = part >= kLineParts;
-    const uint64_t first = (uint64_t)blockIdx.x * kFormatRecords;
-    if (first >= n || offsets[n] > cap) return;                                      // (the caller's buffer is too small: write nothing, RSQ_ENOSPC)
-    const uint64_t last = first + kFormatRecords < n ? first + kFormatRecords : n, row = first + rec;
-    const bool active = row < last;
-    const uint64_t item = PERM ? (active ? raw.order[row] : 0u) : row;
-    const uint64_t g_begin = PERM ? (active ? offsets[item] : 0u) : offsets[first], g_end = PERM ? (active ? offsets[item + 1u] : 0u) : offsets[last];
-    const uint32_t skew = (uint32_t)((uint64_t)(uintptr_t)(dst + g_begin) & 15u), bytes = (uint32_t)(g_end - g_begin);
-    const uint32_t slot = (lds_bytes / kFormatRecords) & ~15u;
-    const bool through_lds = PERM ? __all(skew + bytes <= slot) != 0 : skew + bytes <= lds_bytes;      // wave-uniform
-    ReadMeta m{};
-    if (active) m = raw.meta[row];
-    const WordColumn seq = raw.seq_of(active ? row : 0u), qual = raw.qual_of(active ? row : 0u), ops = raw.ops_of(active ? row : 0u);
-    auto header = [&](auto &t) {
-        t.ch('@');
-        t.str(ids.begin(item), ids.length(item));
-        t.ch(' ');
-        cigar_replay(ops, m, t);
-        t.str(" E", 2);
-        t.num((uint32_t)m.num_errors);
-        t.ch('\n');
-    };
-    if (!through_lds) {
-        if (active && part == 0u) {
-            WordSinkT<char *> t(dst + offsets[item]);
-            header(t);
-            format_line(seq, m.read_len, false, t);
-            format_line(qual, m.read_len, true, t);
-            t.finish();
-        }
-        return;
-    }
-    const uint32_t slot_at = PERM ? rec * slot : 0u;
-    if (active) {
-        RSQ_LDS char *rec_text = (RSQ_LDS char *)s_text + slot_at + skew + (PERM ? 0u : (uint32_t)(offsets[item] - g_begin));
-        const uint32_t head = (uint32_t)(offsets[item + 1u] - offsets[item]) - 2u * m.read_len - 4u;
-        const uint32_t all_words = (m.read_len + 3u) >> 2, per = (all_words + kLineParts - 1u) / kLineParts, first_word = sub * per;
-        const uint32_t line_at = head + (is_qual ? m.read_len + 3u : 0u), part_at = part == 0u ? 0u : line_at + (4u * first_word < m.read_len ? 4u * first_word : m.read_len);
-        WordSinkT<RSQ_LDS char *> t(rec_text + part_at);
-        if (part == 0u) header(t);
-        format_line_part(is_qual ? qual : seq, m.read_len, is_qual, first_word, per, sub == kLineParts - 1u, t);
-        t.finish();
-    }
-    __syncthreads();
-    const uint32_t lo = skew, hi = skew + bytes;
-    char *g_chunk0 = dst + g_begin - skew;                                           // 16-byte aligned
-    const char *s_from = s_text + slot_at;
-    for (uint32_t c = (PERM ? part : lane) * 16u; c < hi; c += (PERM ? 64u / kFormatRecords : 64u) * 16u) {
-        if (c >= lo && c + 16u <= hi) *reinterpret_cast<uint4 *>(g_chunk0 + c) = *reinterpret_cast<const uint4 *>(s_from + c);
-        else
-            for (uint32_t b = c < lo ? lo : c; b < c + 16u && b < hi; ++b) g_chunk0[b] = s_from[b];
-    }
 }
 
 // The reads' bases and qualities as rows of out_stride bytes (word-aligned): sixteen lanes copy a row, a word each per step -- 64 bytes of a row in one store
@@ -2391,11 +2307,9 @@ static int error_model_text(rsq_sim *s, const RawLayout &raw, uint64_t n, const 
     s->longest_record.reserve(8);
     HIP_CHECK(hipMemsetAsync(s->longest_record.as<uint32_t>(), 0, 4, st));
     hipLaunchKernelGGL(k_max_size, dim3(std::min<uint64_t>(1024, cdiv(n, 256))), dim3(256), 0, st, s->cur->sizes.as<uint32_t>(), n, s->longest_record.as<uint32_t>());
-    const uint32_t lds = raw.order ? std::min(kFormatLdsMax, format_lds_bytes(s->record_text_bytes) + 16u * kFormatRecords) : format_lds_bytes(s->record_text_bytes);
-    if (raw.order)
-        hipLaunchKernelGGL(k_record_text_waves<true>, dim3(cdiv(n, kFormatRecords)), dim3(64), lds, st, raw, n, ids, s->cur->off_r1.as<uint64_t>(), text_dev, (uint64_t)text_cap, lds);
-    else
-        hipLaunchKernelGGL(k_record_text_waves<false>, dim3(cdiv(n, kFormatRecords)), dim3(64), lds, st, raw, n, ids, s->cur->off_r1.as<uint64_t>(), text_dev, (uint64_t)text_cap, lds);
+    const uint32_t lds = format_lds_bytes(s->record_text_bytes, raw.order != nullptr);
+    launch_text_waves(k_record_text_waves<true>, k_record_text_waves<false>, raw.order, dim3(cdiv(n, kFormatRecords)), lds, st, raw, n, ids, s->cur->off_r1.as<uint64_t>(), text_dev,
+                      (uint64_t)text_cap, lds);
     s->timers["format_write"].stop(st);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(&s->mailbox[2], s->cur->off_r1.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));

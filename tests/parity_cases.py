@@ -13,12 +13,12 @@ from reseq_amd import synth
 NORM_RTOL = 1e-11      # a14: device tree-reduction vs sequential sum of ~1e6 positive doubles
 
 
-def make_inputs(workdir, tag, cfg, ref_lengths, prof_seed=5, ref_seed=1, gc=0.5):
+def make_inputs(workdir, tag, cfg, ref_lengths, prof_seed=5, ref_seed=1, gc=0.5, names=None):
     ppath = workdir / f"{tag}.rsqp"
     fpath = workdir / f"{tag}.fa"
     if not ppath.exists():
         synth.write_profile(ppath, synth.make_profile(cfg, seed=prof_seed, n_ref_seqs=len(ref_lengths)))
-    seqs = synth.make_reference(ref_seed, ref_lengths, gc=gc)
+    seqs = synth.make_reference(ref_seed, ref_lengths, gc=gc, names=names)
     if not fpath.exists():
         synth.write_fasta(fpath, seqs)
     return str(ppath), str(fpath), seqs

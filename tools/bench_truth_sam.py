@@ -45,7 +45,11 @@ def timed(call):
     return (time.perf_counter() - t0) / steps
 
 
-kernels = lambda names: {k: {"ms": round(sim.last_kernel_ms(k), 3), "launches": sim.last_kernel_launches(k)} for k in names}
+def kernels(names):                                                    # (a kernel the last call did not launch has no time)
+    launches = {k: sim.last_kernel_launches(k) for k in names}
+    return {k: {"ms": round(sim.last_kernel_ms(k), 3) if launches[k] else None, "launches": launches[k]} for k in names}
+
+
 plain_s = timed(lambda: sim.pairs_device(lo, hi, r1, r2))
 plain_kernels = kernels(("format_write", "sam_sizes", "sam_write"))
 sam_s = timed(lambda: sim.pairs_sam_device(lo, hi, r1, r2, sam))
