@@ -370,9 +370,10 @@ __global__ void __launch_bounds__(64) k_sam_write(DevSim S, NameTable names, con
         if (im.active && half == 0u) sam_record(S, names, has_f, f, ao_number, m, seq, qual, ops, w, a, dst + offsets[pair] + rec_at);
         return;
     }
+    im.clear(s_sam, lds_bytes);
     if (im.active) {
         const uint32_t qual_at = w.bytes - sam_tags_size(m) - m.read_len;
-        WordSinkT<RSQ_LDS char *> t(im.item_text(s_sam) + rec_at + (half ? qual_at : 0u));
+        ImageSink t(im.item_text(s_sam) + rec_at + (half ? qual_at : 0u));
         if (half == 0u) {
             sam_head(S, names, has_f, f, ao_number, m, ops, w, a, t);
             sam_line(seq, m.read_len, false, a.reverse != 0u, S.phred_offset, t);
