@@ -103,6 +103,9 @@ int rsq_ref_sequence_name(const rsq_ref *r, uint32_t seq, char *out, size_t cap)
  * "@PG ID:reseq_amd PN:reseq_amd" (tab-separated).  Host code, no device.  *need = its bytes; written (NUL-terminated when cap is larger) if cap >= *need, else
  * RSQ_ENOSPC. */
 int rsq_ref_sam_header(const rsq_ref *r, char *out, size_t cap, size_t *need);
+/* The header of the truth alignments as BAM (rsq_sim_pairs_bam): "BAM\1", l_text, that text, n_ref, and per sequence l_name (with its NUL), the name, l_ref;
+ * uncompressed.  The same contract: *need = its bytes; written if cap >= *need, else RSQ_ENOSPC. */
+int rsq_ref_bam_header(const rsq_ref *r, char *out, size_t cap, size_t *need);
 /* Reference::WriteFasta (reseq/Reference.cpp:896-916; `reseq replaceN` writes the reference after ReplaceN): FASTA, gzip when the
  * name ends in .gz */
 int rsq_ref_write_fasta(const rsq_ref *r, const char *path);
@@ -320,6 +323,22 @@ int rsq_sim_pairs_sam(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1
                       char *sam_dev, size_t sam_cap, size_t *sam_len, uint64_t *n_pairs, rsq_fragment *frags_dev, size_t frags_cap, void *stream);
 int rsq_sim_adapter_only_pairs_sam(rsq_sim *s, uint64_t first, uint64_t n, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len,
                                    char *sam_dev, size_t sam_cap, size_t *sam_len, void *stream);
+
+/* The same truth alignments as BAM records (reseq_amd/csrc/rsq_bam.h; SAM specification 4.2): every record is the re-encoding of the SAM line the calls above
+ * write for the same read -- block_size, refID (the sequence's index), pos = POS - 1, l_read_name, mapq, bin = reg2bin(pos, pos + max(reference bases, 1)),
+ * n_cigar_op, flag, l_seq, next_refID, next_pos, tlen, read_name NUL, cigar (len << 4 | op), seq (4 bits per base, the first base in the high nibble; a reverse
+ * mate the reverse complement), qual (the character minus the profile's Phred offset, reversed for a reverse mate), the tags XC:Z and XE:S (a u16).  Unmapped
+ * records: refID = next_refID = pos = next_pos = -1, mapq 0, bin 4680, no CIGAR.  The bytes are uncompressed records without the file's header: rsq_ref_bam_header
+ * gives that ("BAM\1", l_text, the text of rsq_ref_sam_header, n_ref, then l_name, name NUL, l_ref per sequence; the `need` / RSQ_ENOSPC contract of
+ * rsq_ref_sam_header), and rsq_sim_gzip_device makes the BGZF blocks of a .bam file from header and records as one byte stream (rsq_gzip_eof_member ends it).
+ * RSQ_ENOSPC as above: all three sizes are reported, the records are written only if all three buffers fit.  Refused with RSQ_EINVAL before anything is launched:
+ * a reference with variants; a reference name and base identifier with which a read name could exceed 254 characters (l_read_name is a byte); a sequence of more
+ * than 2^29 bases (the bins' range).  Kernel times: "bam_sizes", "bam_write"; the plain calls and the _sam calls launch neither, these launch neither of the
+ * _sam calls' kernels. */
+int rsq_sim_pairs_bam(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len,
+                      char *bam_dev, size_t bam_cap, size_t *bam_len, uint64_t *n_pairs, rsq_fragment *frags_dev, size_t frags_cap, void *stream);
+int rsq_sim_adapter_only_pairs_bam(rsq_sim *s, uint64_t first, uint64_t n, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len,
+                                   char *bam_dev, size_t bam_cap, size_t *bam_len, void *stream);
 
 /* Simulator::ApplyErrorsAndQualityToFastaInput with the FASTA header already parsed (reseq/Simulator.cpp:2403-2512):
  * n records of `read_len` template bases each.  Inputs (device): seqs[n][read_len] base codes 0..3, seg[n] template

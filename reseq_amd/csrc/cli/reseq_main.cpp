@@ -599,6 +599,26 @@ int illumina_pe(const Args &a) {
         ERR("--truthSam: truth alignments are not available for a reference with variants (-V)");
         return 1;
     }
+    // --truthBam: the same records as BAM (rsq_sim_pairs_bam): header and records are one byte stream that becomes BGZF blocks on the device, whatever the file's name
+    const std::string truth_bam = a.get("truthBam", "");
+    if (a.has("truthBam") && truth_bam.empty()) {
+        ERR("--truthBam needs a file name");
+        return 1;
+    }
+    if (!truth_bam.empty() && !vcf_path.empty()) {
+        ERR("--truthBam: truth alignments are not available for a reference with variants (-V)");
+        return 1;
+    }
+    if (!truth_bam.empty() && a.has("hostGzip")) {
+        ERR("--truthBam: a BAM file is made of BGZF blocks, which the zlib members of --hostGzip are not (run without --hostGzip)");
+        return 1;
+    }
+    if (!truth_bam.empty() && truth_bam == truth) {
+        ERR("--truthBam and --truthSam name the same file");
+        return 1;
+    }
+    const bool any_truth = !truth.empty() || !truth_bam.empty();
+    const char *truth_option = !truth.empty() ? "--truthSam" : "--truthBam";
     rsq_profile *prof = nullptr;
     rsq_ref *ref = nullptr;
     rsq_sim *sim = nullptr;
@@ -629,12 +649,12 @@ int illumina_pe(const Args &a) {
             ok = false;
         }
         if (ok) n_workers = a.has("gpus") ? (int)asked : (int)std::min<uint64_t>(std::max<uint64_t>(asked, 1), (uint64_t)n_devices);
-        if (ok && n_workers > 1 && !truth.empty()) {
+        if (ok && n_workers > 1 && any_truth) {
             if (a.has("gpus")) {
-                ERR("--truthSam: truth alignments are written by one worker only (run without --gpus, or with --gpus 1)");
+                ERR(truth_option << ": truth alignments are written by one worker only (run without --gpus, or with --gpus 1)");
                 ok = false;
             } else {
-                WARN("-j: truth alignments (--truthSam) are written by one worker only; one worker runs");
+                WARN("-j: truth alignments (" << truth_option << ") are written by one worker only; one worker runs");
                 n_workers = 1;
             }
         }
@@ -701,15 +721,20 @@ int illumina_pe(const Args &a) {
     }
     if (ok && !sys_read.empty()) ok = check(rsq_sim_read_sys_errors(sim, sys_read.c_str()), "Could not read systematic error profile");
     trace.at("prepared");
-    AsyncOut f1, f2, f3;                                         // f3: the truth alignments
+    AsyncOut f1, f2, f3, f4;                                     // f3, f4: the truth alignments as SAM and as BAM
     // .gz outputs: the text of every call becomes gzip members on the device (rsq_sim_gzip_device) -- a third of the bytes cross the link and the writer threads
     // only write (--rsqOption host_gzip:1: zlib on host threads behind the writers, as before)
     int64_t host_gzip = 0;
     rsq_get_option("host_gzip", &host_gzip);
     const bool gz1 = !host_gzip && rsq::textio::has_suffix(out1, ".gz"), gz2 = !host_gzip && rsq::textio::has_suffix(out2, ".gz");
     const bool gz3 = !host_gzip && rsq::textio::has_suffix(truth, ".gz");
+    const bool bam = !truth_bam.empty();
+    if (ok && bam && host_gzip) {                                // (the option set some other way than by --hostGzip)
+        ERR("--truthBam: a BAM file is made of BGZF blocks, which host zlib members are not (run without host_gzip)");
+        ok = false;
+    }
     // one Huffman code for the run: the first batch's sample (FASTQ text alone: SAM text is another kind, its calls take their own code)
-    if (ok && (gz1 || gz2) && !gz3) rsq_sim_gzip_keep_code(sim, 1);
+    if (ok && (gz1 || gz2) && !gz3 && !bam) rsq_sim_gzip_keep_code(sim, 1);
     {                                                            // files of device-made members (BGZF blocks) end with BGZF's end-of-file member
         char eof[32];
         const size_t n = rsq_gzip_eof_member(eof, sizeof eof);
@@ -727,14 +752,22 @@ int illumina_pe(const Args &a) {
             ERR("Could not open '" << truth << "' for writing.");
             ok = false;
         }
+        if (ok && bam && !f4.open(truth_bam, true)) {
+            ERR("Could not open '" << truth_bam << "' for writing.");
+            ok = false;
+        }
+        if (ok && bam) {                                         // (behind a successful open: a file that was never opened must not send its tail to stdout)
+            char eof[32];
+            f4.tail.assign(eof, rsq_gzip_eof_member(eof, sizeof eof));
+        }
     }
     if (ok) {
         rsq_sim_info info;
         rsq_sim_get_info(sim, &info);
         INFO("Aiming for " << info.total_pairs + info.adapter_only_pairs << " read pairs");
         INFO("Starting read generation");
-        DevBuffer d1, d2, g1, g2, d3, g3;
-        d1.device = d2.device = g1.device = g2.device = d3.device = g3.device = (int)device;
+        DevBuffer d1, d2, g1, g2, d3, g3, d4, g4;
+        d1.device = d2.device = g1.device = g2.device = d3.device = g3.device = d4.device = g4.device = (int)device;
         uint64_t written = 0;
         // a call's text of one file as members in `g`: true and the members' size, or false
         auto members = [&](bool gz, DevBuffer &d, size_t &len, DevBuffer &g) {
@@ -756,6 +789,20 @@ int illumina_pe(const Args &a) {
             l3 = need;
             ok = ok && members(gz3, d3, l3, g3) && f3.push(gz3 ? g3 : d3, l3);
         }
+        if (ok && bam) {                                         // the BAM header: the first bytes of the stream the records continue
+            size_t need = 0, l4 = 0;
+            rsq_ref_bam_header(ref, nullptr, 0, &need);
+            std::string header(need, '\0');
+            ok = check(rsq_ref_bam_header(ref, &header[0], need, &need), "BAM header") && d4.ensure(need + 4096) && check(rsq_dev_upload((int)device, d4.p, header.data(), need), "upload");
+            l4 = need;
+            ok = ok && members(true, d4, l4, g4) && f4.push(g4, l4);
+        }
+        // a call per output kind: with both --truthSam and --truthBam a batch is simulated once for each (the calls write the same FASTQ text into the same buffers)
+        auto both = [](int rc_sam, int rc_bam) {
+            if (rc_sam != RSQ_OK && rc_sam != RSQ_ENOSPC) return rc_sam;
+            if (rc_bam != RSQ_OK && rc_bam != RSQ_ENOSPC) return rc_bam;
+            return rc_sam == RSQ_ENOSPC || rc_bam == RSQ_ENOSPC ? (int)RSQ_ENOSPC : (int)RSQ_OK;
+        };
         // about 12 M pairs per call: large launches keep the persistent read kernel's tail short (one call of 14.5 M pairs runs at 179 M pairs/s, calls of 2.4 M at
         // 154 M), and sparse coverage needs long block ranges
         const double pairs_per_block = (double)info.total_pairs / std::max<uint32_t>(1u, info.total_blocks);
@@ -764,44 +811,53 @@ int illumina_pe(const Args &a) {
             const uint32_t hi = std::min(info.total_blocks + 1, lo + step);
             size_t l1 = 0, l2 = 0;
             uint64_t n = 0;
-            size_t l3 = 0;
+            size_t l3 = 0, l4 = 0;
             auto call = [&] {
-                return sam ? rsq_sim_pairs_sam(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)d3.p, d3.cap, &l3, &n, nullptr, 0, nullptr)
-                           : rsq_sim_pairs(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, &n, nullptr, 0, nullptr);
+                const int rc = sam   ? rsq_sim_pairs_sam(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)d3.p, d3.cap, &l3, &n, nullptr, 0, nullptr)
+                               : bam ? (int)RSQ_OK
+                                     : rsq_sim_pairs(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, &n, nullptr, 0, nullptr);
+                if (!bam || (rc != RSQ_OK && rc != RSQ_ENOSPC)) return rc;
+                return both(rc, rsq_sim_pairs_bam(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)d4.p, d4.cap, &l4, &n, nullptr, 0, nullptr));
             };
             int rc = call();
             if (rc == RSQ_ENOSPC) {
-                ok = d1.ensure(l1 + l1 / 8 + 4096) && d2.ensure(l2 + l2 / 8 + 4096) && (!sam || d3.ensure(l3 + l3 / 8 + 4096));
+                ok = d1.ensure(l1 + l1 / 8 + 4096) && d2.ensure(l2 + l2 / 8 + 4096) && (!sam || d3.ensure(l3 + l3 / 8 + 4096)) && (!bam || d4.ensure(l4 + l4 / 8 + 4096));
                 if (ok) rc = call();
             }
             ok = ok && check(rc, "Simulation failed") && (n == 0 || (members(gz1, d1, l1, g1) && members(gz2, d2, l2, g2) && flush_pair(gz1 ? g1 : d1, l1, gz2 ? g2 : d2, l2, f1, f2)));
             ok = ok && (!sam || n == 0 || (members(gz3, d3, l3, g3) && f3.push(gz3 ? g3 : d3, l3)));
+            ok = ok && (!bam || n == 0 || (members(true, d4, l4, g4) && f4.push(g4, l4)));
             written += n;
             if (ok && n) INFO("Generated " << written << " read pairs (" << (info.total_pairs ? (written * 100 + info.total_pairs / 2) / info.total_pairs : 0) << "%).");
         }
         for (uint64_t first = 0; ok && first < info.adapter_only_pairs; first += 100000) {       // Simulator.cpp:2359-2382
             const uint64_t n = std::min<uint64_t>(100000, info.adapter_only_pairs - first);
             size_t l1 = 0, l2 = 0;
-            size_t l3 = 0;
+            size_t l3 = 0, l4 = 0;
             auto call = [&] {
-                return sam ? rsq_sim_adapter_only_pairs_sam(sim, first, n, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)d3.p, d3.cap, &l3, nullptr)
-                           : rsq_sim_adapter_only_pairs(sim, first, n, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, nullptr);
+                const int rc = sam   ? rsq_sim_adapter_only_pairs_sam(sim, first, n, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)d3.p, d3.cap, &l3, nullptr)
+                               : bam ? (int)RSQ_OK
+                                     : rsq_sim_adapter_only_pairs(sim, first, n, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, nullptr);
+                if (!bam || (rc != RSQ_OK && rc != RSQ_ENOSPC)) return rc;
+                return both(rc, rsq_sim_adapter_only_pairs_bam(sim, first, n, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)d4.p, d4.cap, &l4, nullptr));
             };
             int rc = call();
             if (rc == RSQ_ENOSPC) {
-                ok = d1.ensure(l1 + 4096) && d2.ensure(l2 + 4096) && (!sam || d3.ensure(l3 + 4096));
+                ok = d1.ensure(l1 + 4096) && d2.ensure(l2 + 4096) && (!sam || d3.ensure(l3 + 4096)) && (!bam || d4.ensure(l4 + 4096));
                 if (ok) rc = call();
             }
             ok = ok && check(rc, "Simulation of adapter-only pairs failed") && members(gz1, d1, l1, g1) && members(gz2, d2, l2, g2) && flush_pair(gz1 ? g1 : d1, l1, gz2 ? g2 : d2, l2, f1, f2);
             ok = ok && (!sam || (members(gz3, d3, l3, g3) && f3.push(gz3 ? g3 : d3, l3)));
+            ok = ok && (!bam || (members(true, d4, l4, g4) && f4.push(g4, l4)));
         }
     }
     trace.at("last text handed to the writers");
     f1.close();
     f2.close();
     f3.close();
+    f4.close();
     trace.at("files closed");
-    ok = ok && f1.good() && f2.good() && f3.good();
+    ok = ok && f1.good() && f2.good() && f3.good() && f4.good();
     rsq_sim_free(sim);
     rsq_ref_free(ref);
     rsq_profile_free(prof);
@@ -811,6 +867,7 @@ int illumina_pe(const Args &a) {
         remove(out1.c_str());
         remove(out2.c_str());
         if (!truth.empty()) remove(truth.c_str());
+        if (!truth_bam.empty()) remove(truth_bam.c_str());
         return 1;
     }
     INFO("Simulation finished succesfully");
@@ -1030,6 +1087,7 @@ const char *kUsage =
     "Usage:  reseq <command> [options]\n"
     "Commands:\n"
     "  illuminaPE\t\tsimulates illumina paired-end data from a fitted profile (-s) and a reference (-R)\n"
+    "                 \t--truthBam truth.bam: the same records as BAM (BGZF blocks made on the device; unsorted, no index; may be given beside --truthSam; not with -V or --hostGzip, one worker)\n"
     "                 \t--truthSam truth.sam[.gz]: where every read really came from, as SAM records (header, two records per pair in the files' order; not with -V, one worker)\n"
     "  seqToIllumina\t\tapplies illumina quality and error model to input sequences (alias: replaceQuals)\n"
     "                 \t-i in.fa[.gz|.bz2] (stdin) -o out.fq[.gz|.bz2] (stdout) -s profile; --readThreads N, --traceStages;\n"

@@ -1,0 +1,268 @@
+// rsq_bam.h -- truth alignments as BAM: the records of rsq_sam.h, one per simulated read, in BAM's binary layout (SAM specification 4.2), written on the device from
+// the same raw rows and the same fragment list.  A BAM record is a pure re-encoding of its SAM line: the walk (sam_walk), the alignment (sam_align), the QNAME
+// (sam_qname), the CIGAR's elements (sam_cigar) and the XC tag (cigar_replay) are rsq_sam.h's own, called with other sinks; this file adds what is BAM's.
+//
+// The record, little-endian, no padding:
+//   block_size i32 (the bytes behind it) | refID i32 | pos i32 (POS - 1) | l_read_name u8 | mapq u8 | bin u16 | n_cigar_op u16 | flag u16 | l_seq u32 |
+//   next_refID i32 | next_pos i32 | tlen i32 | read_name NUL | cigar u32[n] (len << 4 | op; M 0, I 1, D 2, S 4) | seq u8[(l_seq + 1) / 2] | qual u8[l_seq] |
+//   "XC" 'Z' <the id's CIGAR> NUL | "XE" 'S' u16
+// bin = reg2bin(pos, pos + max(span, 1)), span the reference bases of the cleaned CIGAR (t - dL - dR).  Unmapped records (adapter-only pairs, fragment length 0):
+// refID = next_refID = pos = next_pos = -1, mapq 0, bin 4680 (reg2bin(-1, 0)), no CIGAR, tlen 0, flags 77 / 141, SEQ and QUAL as in the FASTQ.
+// SEQ holds 4-bit codes (A 1, C 2, G 4, T 8, N 15), the earlier base in the high nibble; a reverse mate (0x10) stores the reverse complement -- on these codes the
+// complement is the nibble's bit reversal, N stays 15 -- and its qualities reversed.  QUAL is the character minus the profile's Phred offset.
+//
+// bam_seq is the part with a shape of its own: a row word holds four base codes, one byte each; one byte permute turns them into four nibbles (the table of the
+// forward or of the complemented codes), a shift-or puts neighbouring nibbles into one byte, and a second permute gathers the four bytes of two row words into one
+// output word.  The reversed line takes the row from its last word down through the byte funnel of sam_line (a read length that is no multiple of four takes every
+// word from two neighbours), so the words arrive in OUTPUT order and the pairing of nibbles is always (0, 1), (2, 3), ... of the output, whatever read_len & 1:
+// an odd length leaves the last low nibble 0 in either orientation.
+//
+// Per lane, host and device (tests/hostemu/bam_trial.cpp runs them on the CPU): bam_record_size, bam_fixed, bam_cigar, bam_seq, bam_qual, bam_tags, bam_record.
+// Kernels: k_bam_sizes (one lane per raw row pair: both mates' walks, CIGAR element counts and name lengths into a side array of its own, the pair's bytes),
+// k_bam_write (one wave per 16 pairs, four lanes a pair, through the wave's LDS image: WaveImage and ImageSink of rsq_format.h -- records are not word-aligned,
+// the frame handles that as it does for text).  Not part of what hiprtc compiles for a profile (rsq_spec.h): nothing of the read kernel's text includes this file.
+#pragma once
+#include "rsq_sam.h"
+
+namespace rsq {
+
+// a mate's walk and what its BAM record needs beside it (k_bam_sizes keeps them so that the writer neither walks the ops nor counts again)
+struct BamMate {
+    SamMate w;                 // w.bytes: of the mate's BAM record, its block_size field included
+    uint16_t n_cigar;          // elements of the CIGAR (0: unmapped, or "*")
+    uint16_t l_read_name;      // QNAME length + 1
+    uint32_t pad;
+};
+static_assert(sizeof(BamMate) == 24, "the side array's entry");
+struct BamPair {
+    BamMate mate[2];
+};
+
+constexpr uint32_t kBamMaxQname = 254;                                  // l_read_name is a byte and counts the NUL
+constexpr uint32_t kBamMaxRefLen = 1u << 29;                            // what the binning scheme covers
+constexpr uint32_t kBamUnmappedBin = 4680;                              // reg2bin(-1, 0)
+
+// SAM specification 5.3: the smallest bin that holds [beg, end), 0-based, end > beg
+RSQ_HD uint32_t bam_reg2bin(uint32_t beg, uint32_t end) {
+    --end;
+    if (beg >> 14 == end >> 14) return ((1u << 15) - 1u) / 7u + (beg >> 14);
+    if (beg >> 17 == end >> 17) return ((1u << 12) - 1u) / 7u + (beg >> 17);
+    if (beg >> 20 == end >> 20) return ((1u << 9) - 1u) / 7u + (beg >> 20);
+    if (beg >> 23 == end >> 23) return ((1u << 6) - 1u) / 7u + (beg >> 23);
+    if (beg >> 26 == end >> 26) return ((1u << 3) - 1u) / 7u + (beg >> 26);
+    return 0u;
+}
+
+// sam_cigar's elements, counted and as BAM's words (its "*" is no element)
+struct BamCigarCount {
+    uint32_t n = 0;
+    RSQ_HD void element(char, uint32_t) { ++n; }
+    RSQ_HD void ch(char) {}
+};
+template <class Sink>
+struct BamCigarWords {
+    Sink &t;
+    RSQ_HD void element(char op, uint32_t count) { t.bytes((count << 4) | (op == 'M' ? 0u : op == 'I' ? 1u : op == 'D' ? 2u : 4u), 4u); }
+    RSQ_HD void ch(char) {}
+};
+RSQ_HD uint32_t bam_cigar_ops(const WordColumn &ops, const ReadMeta &m, const SamMate &w, const SamAlign &a) {
+    if (!a.mapped) return 0u;
+    BamCigarCount c;
+    sam_cigar(ops, m, w, a.reverse != 0u, c);
+    return c.n;
+}
+template <class Sink>
+RSQ_HD void bam_cigar(const WordColumn &ops, const ReadMeta &m, const SamMate &w, const SamAlign &a, Sink &t) {
+    if (!a.mapped) return;
+    BamCigarWords<Sink> c{t};
+    sam_cigar(ops, m, w, a.reverse != 0u, c);
+}
+
+RSQ_HD uint32_t bam_tags_size(const ReadMeta &m) { return 3u + m.cigar_chars + 1u + 5u; }
+// length of a record (with its block_size field) without producing it
+RSQ_HD uint32_t bam_record_size(const ReadMeta &m, uint32_t l_read_name, uint32_t n_cigar) {
+    return 36u + l_read_name + 4u * n_cigar + (((uint32_t)m.read_len + 1u) >> 1) + m.read_len + bam_tags_size(m);
+}
+
+// block_size and the 32 bytes of fixed fields: nine words
+template <class Sink>
+RSQ_HD void bam_fixed(const Fragment &f, const ReadMeta &m, const SamMate &w, const SamAlign &a, uint32_t l_read_name, uint32_t n_cigar, uint32_t block_size, Sink &t) {
+    const uint32_t none = 0xFFFFFFFFu, span = (uint32_t)w.t - w.lead - w.trail;
+    const uint32_t ref_id = a.mapped ? f.seq : none, pos = a.mapped ? a.pos - 1u : none, pnext = a.mapped ? a.pnext - 1u : none;
+    const uint32_t bin = a.mapped ? bam_reg2bin(pos, pos + (span ? span : 1u)) : kBamUnmappedBin, mapq = a.mapped ? 60u : 0u;
+    t.bytes(block_size, 4u);
+    t.bytes(ref_id, 4u);
+    t.bytes(pos, 4u);
+    t.bytes(l_read_name | (mapq << 8) | (bin << 16), 4u);
+    t.bytes(n_cigar | (a.flag << 16), 4u);
+    t.bytes((uint32_t)m.read_len, 4u);
+    t.bytes(ref_id, 4u);
+    t.bytes(pnext, 4u);
+    t.bytes((uint32_t)a.tlen, 4u);
+}
+
+// four base codes, one per byte (0..3 ACGT, 4 N) -> their 4-bit codes, one per byte; complement: of the complementary bases
+RSQ_HD uint32_t bam_nibbles(uint32_t codes, bool complement) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(0x0F0F0F0Fu, complement ? 0x01020408u : 0x08040201u, codes);      // selector 0-3: the table's bytes, 4-7: N
+#else
+    uint32_t out = 0;
+    for (uint32_t k = 0; k < 4u; ++k) {
+        const uint32_t b = (codes >> (8u * k)) & 0xFFu;
+        out |= (b < 4u ? (complement ? 8u >> b : 1u << b) : 15u) << (8u * k);
+    }
+    return out;
+#endif
+}
+// eight 4-bit codes, one per byte of (n1 : n0) -> four bytes, the earlier code of a pair in the high nibble
+RSQ_HD uint32_t bam_pack(uint32_t n0, uint32_t n1) {
+    const uint32_t x0 = (n0 << 4) | (n0 >> 8), x1 = (n1 << 4) | (n1 >> 8);      // bytes 0 and 2 hold the pairs (0, 1) and (2, 3)
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(x1, x0, 0x06040200u);
+#else
+    return (x0 & 0xFFu) | ((x0 >> 8) & 0xFF00u) | ((x1 & 0xFFu) << 16) | ((x1 << 8) & 0xFF000000u);
+#endif
+}
+// SEQ: the row's words in output order (sam_line's walk: as they lie, or from the last one down, funnelled and byte-reversed), two of them an output word.  What
+// lies behind the row's last code becomes nibble 0.
+template <class Sink>
+RSQ_HD void bam_seq(const WordColumn &row, uint32_t read_len, bool reverse, Sink &t) {
+    const uint32_t words = (read_len + 3u) >> 2, odd = read_len & 3u;
+    constexpr uint32_t kAhead = 10u;                                     // loads in flight (even: an output word never spans two rounds)
+    for (uint32_t i = 0; i < words; i += kAhead) {
+        uint32_t w[kAhead + 1u], nib[kAhead];
+#pragma unroll
+        for (uint32_t k = 0; k <= kAhead; ++k) {
+            const uint32_t j = i + k;                                    // code word j reads row word j, or (reverse) words - 1 - j and the one below it
+            w[k] = j < words && (k < kAhead || (reverse && odd)) ? row.at(reverse ? words - 1u - j : j) : 0u;
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kAhead; ++k) {
+            uint32_t v = w[k];
+            if (reverse) v = sam_byte_reverse(odd ? sam_funnel(w[k], w[k + 1u], odd) : v);
+            const uint32_t at = 4u * (i + k), left = at < read_len ? read_len - at : 0u;
+            nib[k] = bam_nibbles(v, reverse) & (left >= 4u ? 0xFFFFFFFFu : (1u << (8u * left)) - 1u);
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kAhead; k += 2u) {
+            if (i + k >= words) break;
+            const uint32_t left = read_len - 4u * (i + k);
+            t.bytes(bam_pack(nib[k], nib[k + 1u]), left >= 8u ? 4u : (left + 1u) >> 1);
+        }
+    }
+}
+// QUAL: sam_line's qualities with the whole offset taken off (it subtracts its offset argument - 33)
+template <class Sink>
+RSQ_HD void bam_qual(const WordColumn &row, uint32_t read_len, bool reverse, uint32_t phred_offset, Sink &t) {
+    sam_line(row, read_len, true, reverse, phred_offset + 33u, t);
+}
+template <class Sink>
+RSQ_HD void bam_tags(const ReadMeta &m, const WordColumn &ops, Sink &t) {
+    t.bytes(chars4('X', 'C', 'Z'), 3u);
+    cigar_replay(ops, m, t);
+    t.bytes(chars4(0, 'X', 'E', 'S'), 4u);
+    t.bytes((uint32_t)m.num_errors, 2u);
+}
+// the record's first stretch: everything in front of QUAL
+template <class Sink>
+RSQ_HD void bam_head(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &seq, const WordColumn &ops,
+                     const BamMate &b, const SamAlign &a, Sink &t) {
+    bam_fixed(f, m, b.w, a, b.l_read_name, b.n_cigar, b.w.bytes - 4u, t);
+    sam_qname(S, names, has_f, f, adapter_only_number, m, t);
+    t.ch(0);
+    bam_cigar(ops, m, b.w, a, t);
+    bam_seq(seq, m.read_len, a.reverse != 0u, t);
+}
+// the whole record at dst; returns its length
+template <class P>
+RSQ_HD uint32_t bam_record(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &seq,
+                           const WordColumn &qual, const WordColumn &ops, const BamMate &b, const SamAlign &a, P dst) {
+    WordSinkT<P> t(dst);
+    bam_head(S, names, has_f, f, adapter_only_number, m, seq, ops, b, a, t);
+    bam_qual(qual, m.read_len, a.reverse != 0u, S.phred_offset, t);
+    bam_tags(m, ops, t);
+    t.finish();
+    return t.n;
+}
+// a mate's side entry from its walk
+RSQ_HD BamMate bam_mate(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &ops, const SamMate &w,
+                        const SamAlign &a) {
+    BamMate b{};
+    b.w = w;
+    b.n_cigar = (uint16_t)bam_cigar_ops(ops, m, w, a);
+    b.l_read_name = (uint16_t)(sam_qname_size(S, names, has_f, f, adapter_only_number, m) + 1u);
+    b.w.bytes = bam_record_size(m, b.l_read_name, b.n_cigar);
+    return b;
+}
+
+#if RSQ_DEVICE_BUILD
+// One lane per raw row pair, as k_sam_sizes: both mates' entries into side[row], the pair's bytes into sizes[pair]
+__global__ void __launch_bounds__(256) k_bam_sizes(DevSim S, NameTable names, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_only_first, RawLayout raw, const uint32_t *perm,
+                                                   BamPair *side, uint32_t *sizes) {
+    const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= n_pairs) return;
+    const uint64_t pair = perm ? perm[row] : row;
+    Fragment f{};
+    if (frags) f = frags[pair];
+    const bool has_f = frags != nullptr;
+    const ReadMeta m0 = raw.meta[row], m1 = raw.meta[n_pairs + row];
+    const WordColumn ops0 = raw.ops_of(row), ops1 = raw.ops_of(n_pairs + row);
+    const SamMate w0 = sam_walk(ops0, m0), w1 = sam_walk(ops1, m1);
+    const uint64_t ao_number = adapter_only_first + pair + 1u;
+    BamPair p;
+    p.mate[0] = bam_mate(S, names, has_f, f, ao_number, m0, ops0, w0, sam_align(has_f, f, 0u, w0, w1));
+    p.mate[1] = bam_mate(S, names, has_f, f, ao_number, m1, ops1, w1, sam_align(has_f, f, 1u, w0, w1));
+    side[row] = p;
+    sizes[pair] = p.mate[0].w.bytes + p.mate[1].w.bytes;
+}
+
+// One wave per 16 consecutive raw rows = 16 pairs, four lanes a pair, through the wave's image, with k_sam_write's frame, capacity checks and fallback: lanes 0-15
+// write mate 0's record up to and with its packed SEQ, lanes 16-31 its QUAL and tags, lanes 32-47 and 48-63 the same of mate 1.  Nothing is written when any of
+// the call's three outputs exceeds its capacity so far.
+template <bool PERM>
+__global__ void __launch_bounds__(64) k_bam_write(DevSim S, NameTable names, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_only_first, RawLayout raw, const BamPair *side,
+                                                 const uint64_t *offsets, char *dst, uint64_t cap, const uint64_t *fastq_end0, const uint64_t *fastq_end1, uint64_t fastq_cap0,
+                                                 uint64_t fastq_cap1, const uint32_t *perm, uint32_t lds_bytes) {
+    extern __shared__ __attribute__((aligned(16))) char s_bam[];
+    using Image = WaveImage<PERM, kSamPairs>;
+    const uint32_t lane = threadIdx.x, part = lane / kSamPairs, seg = part >> 1, half = part & 1u;
+    if (Image::first() >= n_pairs) return;
+    if (offsets[n_pairs] > cap || *fastq_end0 > fastq_cap0 || *fastq_end1 > fastq_cap1) return;      // a buffer of the call is too small: write nothing (RSQ_ENOSPC)
+    const Image im(offsets, n_pairs, dst, lds_bytes, perm, lane);
+    const uint64_t pair = im.item;
+    ReadMeta m{};
+    Fragment f{};
+    BamPair p{};
+    uint64_t r = 0;
+    if (im.active) {
+        r = (uint64_t)seg * n_pairs + im.row;
+        m = raw.meta[r];
+        p = side[im.row];
+        if (frags) f = frags[pair];
+    }
+    const bool has_f = frags != nullptr;
+    const WordColumn seq = raw.seq_of(r), qual = raw.qual_of(r), ops = raw.ops_of(r);
+    const uint64_t ao_number = adapter_only_first + pair + 1u;
+    const BamMate b = seg ? p.mate[1] : p.mate[0];
+    const SamAlign a = sam_align(has_f, f, seg, p.mate[0].w, p.mate[1].w);
+    const uint32_t rec_at = seg ? p.mate[0].w.bytes : 0u;              // of the record within its pair's bytes
+    if (!im.through_lds) {
+        if (im.active && half == 0u) bam_record(S, names, has_f, f, ao_number, m, seq, qual, ops, b, a, dst + offsets[pair] + rec_at);
+        return;
+    }
+    im.clear(s_bam, lds_bytes);
+    if (im.active) {
+        const uint32_t qual_at = b.w.bytes - bam_tags_size(m) - m.read_len;
+        ImageSink t(im.item_text(s_bam) + rec_at + (half ? qual_at : 0u));
+        if (half == 0u) bam_head(S, names, has_f, f, ao_number, m, seq, ops, b, a, t);
+        else {
+            bam_qual(qual, m.read_len, a.reverse != 0u, S.phred_offset, t);
+            bam_tags(m, ops, t);
+        }
+        t.finish();
+    }
+    im.store_out(s_bam);
+}
+#endif
+
+}  // namespace rsq

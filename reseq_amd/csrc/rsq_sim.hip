@@ -28,6 +28,7 @@
 #include "rsq_reads.h"
 #include "rsq_format.h"
 #include "rsq_sam.h"
+#include "rsq_bam.h"
 #include "rsq_pack.h"
 #include "rsq_prepass.h"
 #include "rsq_spec.h"
@@ -204,6 +205,7 @@ struct rsq_sim : PrepassSim {
         DevBuf bin_keys, bin_small, bin_perm, bin_frags, bin_fvars;      // reads binned by tile: key per item; histogram, bins, counters (one small buffer); the sorted items
         DevBuf fa_counts, fa_first, fa_at, fa_len, fa_id_len, fa_frag_len, fa_seg, fa_codes, fa_summary;      // rsq_sim_error_model_fasta (rsq_fasta.h)
         DevBuf sam_sizes, sam_side, off_sam;      // truth alignments (rsq_sam.h): bytes per pair, both mates' walks per raw row, the pairs' offsets in the SAM text
+        DevBuf bam_side;                          // the same calls with BAM records (rsq_bam.h): their side entries; sizes and offsets live in sam_sizes / off_sam
         DevBuf cell_info;              // the sieve without variants: per candidate the first strand's count and the two strands (k_sieve_finish<0> -> k_sieve_emit<0>)
         hipEvent_t text_done = nullptr;      // the text stage that last read this set's arrays
     } ws[2];
@@ -242,6 +244,7 @@ struct rsq_sim : PrepassSim {
     DevBuf longest_record;                   // where a call's text stages leave it
     DevBuf sam_totals, sam_longest;          // rsq_sim_pairs_sam: [sub-ranges + 1] bytes of SAM text in front of a sub-range; the call's longest pair of records
     uint64_t sam_pair_bytes = 1100;          // that of the last call and a few bytes (sam_stage sizes the writer's LDS image with it)
+    uint64_t bam_pair_bytes = 700;           // the same for a call that writes BAM records
     uint64_t record_text_bytes = 480;        // the same for the seqToIllumina records' text (error_model_text)
     int force_fill_mode = -1;      // RSQ_FILL_MODE=0: every draw in double precision from HBM (tests run both paths)
     // read kernels compiled for this simulator's profile (rsq_spec.h); `specialize`: option specialize when the simulator was created
@@ -651,21 +654,40 @@ static void text_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint
     s.timers["format_write"].stop(st);
     HIP_CHECK(hipGetLastError());
 }
-// What a call that also writes the truth alignments hands down: the caller's SAM buffer.  nullptr: the call launches neither kernel of rsq_sam.h.
+// What a call that also writes the truth alignments hands down: the caller's SAM (or BAM) buffer.  nullptr: the call launches no kernel of rsq_sam.h or rsq_bam.h.
 struct SamOut {
     char *dst;
     size_t cap;
     size_t *len;
+    bool bam = false;      // BAM records (rsq_bam.h: k_bam_sizes, k_bam_write) in place of SAM text; the call then launches neither kernel of rsq_sam.h
 };
 // SAM text of the pairs of reads_stage, behind their text_stage on the same stream (it reads the FASTQ offsets' totals: nothing is written unless all three texts
-// fit so far).  Offsets continue at sam_totals[part]; where the part ends goes to sam_totals[part + 1].
+// fit so far).  Offsets continue at sam_totals[part]; where the part ends goes to sam_totals[part + 1].  BAM records (sam.bam) take the same route with
+// k_bam_sizes / k_bam_write and their own side array; sizes, offsets and totals live in the same buffers (a call writes one kind).
 static void sam_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_first, const ReadsDone &rd, char *r1, size_t r1_cap, char *r2, size_t r2_cap, const SamOut &sam,
                       uint32_t part, hipStream_t st) {
     rsq_sim::Workspace &w = *s.cur;
     w.sam_sizes.reserve(n_pairs * 4 + 16);
-    w.sam_side.reserve(n_pairs * sizeof(SamPair) + 16);
     w.off_sam.reserve((n_pairs + 1) * 8);
     uint64_t *totals = s.sam_totals.as<uint64_t>();
+    const uint64_t cap = sam.dst ? sam.cap : 0, cap1 = r1 ? r1_cap : 0, cap2 = r2 ? r2_cap : 0;
+    if (sam.bam) {
+        w.bam_side.reserve(n_pairs * sizeof(BamPair) + 16);
+        s.timers["bam_sizes"].start(st);
+        hipLaunchKernelGGL(k_bam_sizes, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw, rd.row_order, w.bam_side.as<BamPair>(),
+                           w.sam_sizes.as<uint32_t>());
+        s.timers["bam_sizes"].stop(st);
+        exclusive_scan(s, w.sam_sizes.as<uint32_t>(), n_pairs, w.off_sam.as<uint64_t>(), st, totals + part, totals + part + 1);
+        hipLaunchKernelGGL(k_max_size, dim3(std::min<uint64_t>(1024, cdiv(n_pairs, 256))), dim3(256), 0, st, w.sam_sizes.as<uint32_t>(), n_pairs, s.sam_longest.as<uint32_t>());
+        const uint32_t lds = sam_lds_bytes(s.bam_pair_bytes, rd.row_order != nullptr);
+        s.timers["bam_write"].start(st);
+        launch_text_waves(k_bam_write<true>, k_bam_write<false>, rd.row_order, dim3(cdiv(n_pairs, kSamPairs)), lds, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw,
+                          w.bam_side.as<BamPair>(), w.off_sam.as<uint64_t>(), sam.dst, cap, w.off_r1.as<uint64_t>() + n_pairs, w.off_r2.as<uint64_t>() + n_pairs, cap1, cap2, rd.row_order, lds);
+        s.timers["bam_write"].stop(st);
+        HIP_CHECK(hipGetLastError());
+        return;
+    }
+    w.sam_side.reserve(n_pairs * sizeof(SamPair) + 16);
     s.timers["sam_sizes"].start(st);
     hipLaunchKernelGGL(k_sam_sizes, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw, rd.row_order, w.sam_side.as<SamPair>(),
                        w.sam_sizes.as<uint32_t>());
@@ -673,7 +695,6 @@ static void sam_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint6
     exclusive_scan(s, w.sam_sizes.as<uint32_t>(), n_pairs, w.off_sam.as<uint64_t>(), st, totals + part, totals + part + 1);
     hipLaunchKernelGGL(k_max_size, dim3(std::min<uint64_t>(1024, cdiv(n_pairs, 256))), dim3(256), 0, st, w.sam_sizes.as<uint32_t>(), n_pairs, s.sam_longest.as<uint32_t>());
     const uint32_t lds = sam_lds_bytes(s.sam_pair_bytes, rd.row_order != nullptr);
-    const uint64_t cap = sam.dst ? sam.cap : 0, cap1 = r1 ? r1_cap : 0, cap2 = r2 ? r2_cap : 0;
     s.timers["sam_write"].start(st);
     launch_text_waves(k_sam_write<true>, k_sam_write<false>, rd.row_order, dim3(cdiv(n_pairs, kSamPairs)), lds, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw,
                       w.sam_side.as<SamPair>(), w.off_sam.as<uint64_t>(), sam.dst, cap, w.off_r1.as<uint64_t>() + n_pairs, w.off_r2.as<uint64_t>() + n_pairs, cap1, cap2, rd.row_order, lds);
@@ -694,9 +715,10 @@ static void enqueue_sam_total(rsq_sim &s, uint32_t parts, hipStream_t text_strea
 }
 static int finish_sam(rsq_sim &s, int rc, const SamOut &sam, size_t r1_len, size_t r2_len) {
     *sam.len = s.mailbox[6];
-    if ((uint32_t)s.mailbox[7]) s.sam_pair_bytes = (uint32_t)s.mailbox[7] + 16u;
+    if ((uint32_t)s.mailbox[7]) (sam.bam ? s.bam_pair_bytes : s.sam_pair_bytes) = (uint32_t)s.mailbox[7] + 16u;
     if (rc == RSQ_ENOSPC || (rc == RSQ_OK && (*sam.len > sam.cap || !sam.dst))) {
-        g_last_error = "output buffers too small: need " + std::to_string(r1_len) + " and " + std::to_string(r2_len) + " bytes of FASTQ text and " + std::to_string(*sam.len) + " of SAM text";
+        g_last_error = "output buffers too small: need " + std::to_string(r1_len) + " and " + std::to_string(r2_len) + " bytes of FASTQ text and " + std::to_string(*sam.len) +
+                       (sam.bam ? " of BAM records" : " of SAM text");
         return RSQ_ENOSPC;
     }
     return rc;
@@ -1271,6 +1293,35 @@ int rsq_ref_sam_header(const rsq_ref *r, char *out, size_t cap, size_t *need) {
     return RSQ_OK;
 }
 
+// the same header in front of the BAM records (rsq_sim_pairs_bam; SAM specification 4.2): magic, the text, the sequences' names and lengths
+int rsq_ref_bam_header(const rsq_ref *r, char *out, size_t cap, size_t *need) {
+    REQUIRE(r && need, "null argument");
+    size_t text_len = 0;
+    (void)rsq_ref_sam_header(r, nullptr, 0, &text_len);
+    std::string text(text_len, '\0'), h = "BAM\1";
+    if (const int rc = rsq_ref_sam_header(r, &text[0], text_len, &text_len)) return rc;
+    auto put32 = [&](uint32_t v) {
+        for (int k = 0; k < 4; ++k) h += (char)((v >> (8 * k)) & 0xFFu);
+    };
+    put32((uint32_t)text.size());
+    h += text;
+    put32((uint32_t)r->r.codes.size());
+    for (uint32_t seq = 0; seq < r->r.codes.size(); ++seq) {
+        const std::string name = r->r.first_part(seq);
+        put32((uint32_t)name.size() + 1u);
+        h += name;
+        h += '\0';
+        put32((uint32_t)r->r.codes[seq].size());
+    }
+    *need = h.size();
+    if (!out || cap < h.size()) {
+        g_last_error = "header buffer too small: need " + std::to_string(h.size()) + " bytes";
+        return RSQ_ENOSPC;
+    }
+    memcpy(out, h.data(), h.size());
+    return RSQ_OK;
+}
+
 int rsq_ref_load_fasta(const char *path, rsq_ref **out) {
     REQUIRE(path && out, "null argument");
     try {
@@ -1746,6 +1797,37 @@ int rsq_sim_pairs_sam(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1
     const SamOut sam{sam_dev, sam_cap, sam_len};
     return guard([&] { return sim_pairs(*s, block_lo, block_hi, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, n_pairs, frags_dev, frags_cap, (hipStream_t)stream, &sam); });
 }
+// ... as BAM records (rsq_bam.h).  What BAM cannot hold is refused here, before anything is launched: l_read_name is a byte, so no QNAME may exceed 254 characters
+// (the base identifier, the longest reference name, every number at its widest), and the bins cover 2^29 bases.
+static bool bam_refusal(const rsq_sim &s) {
+    if (s.has_variants) {
+        g_last_error = "truth alignments (BAM) are not available for a reference with variants (rsq_ref_read_variants)";
+        return true;
+    }
+    size_t longest_name = 0;
+    uint32_t longest_seq = 0;
+    for (const std::string &n : s.ref_first_names) longest_name = std::max(longest_name, n.size());
+    for (const uint32_t l : s.seq_len) longest_seq = std::max(longest_seq, l);
+    if (longest_seq > kBamMaxRefLen) {
+        g_last_error = "truth alignments (BAM): a reference sequence of " + std::to_string(longest_seq) + " bases is longer than the 2^29 that BAM's bins cover";
+        return true;
+    }
+    // "{base}{block}_{number}:{pos}:{name}:{pos}:{tile}:1337:1337" with 32-bit block and number and a 16-bit tile; "{base}0_{number}:0:Adapter:0:{tile}:1337:1337" with a 64-bit number
+    const size_t mapped = s.names.base_len + 10 + 1 + 10 + 1 + 2 * (size_t)digits_u32(longest_seq) + 2 + longest_name + 1 + 5 + 10;
+    const size_t adapter_only = s.names.base_len + 2 + 20 + 12 + 1 + 5 + 10;
+    if (std::max(mapped, adapter_only) > kBamMaxQname) {
+        g_last_error = "truth alignments (BAM): a read name could take " + std::to_string(std::max(mapped, adapter_only)) + " characters, BAM holds 254 (shorten the reference names or the base identifier)";
+        return true;
+    }
+    return false;
+}
+int rsq_sim_pairs_bam(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len, char *bam_dev,
+                      size_t bam_cap, size_t *bam_len, uint64_t *n_pairs, rsq_fragment *frags_dev, size_t frags_cap, void *stream) {
+    REQUIRE(s && r1_len && r2_len && bam_len && n_pairs, "null argument");
+    if (bam_refusal(*s)) return RSQ_EINVAL;
+    const SamOut bam{bam_dev, bam_cap, bam_len, true};
+    return guard([&] { return sim_pairs(*s, block_lo, block_hi, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, n_pairs, frags_dev, frags_cap, (hipStream_t)stream, &bam); });
+}
 
 // ---- a rank's share, generated once and kept (include/reseq_amd.h rsq_sim_job_*)
 constexpr size_t kJobChunkBytes = (size_t)2 << 30, kJobSliceBytes = (size_t)32 << 20;
@@ -2199,6 +2281,16 @@ int rsq_sim_adapter_only_pairs_sam(rsq_sim *s, uint64_t first, uint64_t n, char 
     return guard([&] {
         HIP_CHECK(hipSetDevice(s->device));
         return adapter_only_pairs(*s, n, first, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, (hipStream_t)stream, &sam);
+    });
+}
+int rsq_sim_adapter_only_pairs_bam(rsq_sim *s, uint64_t first, uint64_t n, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len, char *bam_dev,
+                                   size_t bam_cap, size_t *bam_len, void *stream) {
+    REQUIRE(s && r1_len && r2_len && bam_len && s->prepared, "simulator not prepared");
+    if (bam_refusal(*s)) return RSQ_EINVAL;
+    const SamOut bam{bam_dev, bam_cap, bam_len, true};
+    return guard([&] {
+        HIP_CHECK(hipSetDevice(s->device));
+        return adapter_only_pairs(*s, n, first, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, (hipStream_t)stream, &bam);
     });
 }
 

@@ -1,0 +1,307 @@
+"""Truth alignments as BAM (reseq_amd/csrc/rsq_bam.h; include/reseq_amd.h rsq_sim_pairs_bam) without a GPU: the header, and the per-lane functions -- record
+size, fixed fields, CIGAR words, packed SEQ, QUAL, tags -- run on the CPU (tests/hostemu/bam_trial.cpp, built here with g++) on crafted rows.  A BAM record is a
+pure re-encoding of its SAM line: `decode_bam` below (pure Python, `struct`) turns the records back into SAM text, checking block_size, l_read_name and
+bin == reg2bin on the way, and that text must equal `sam_pair` of tests/test_truth_sam.py, the statement the SAM writer is pinned to, byte for byte.
+tests/test_truth_bam_gpu.py applies the same decoder to the device's output."""
+import ctypes as C
+import os
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+from reseq_amd import api
+from test_truth_sam import CRAFTED, D, GOLDEN, HERE, I, M, NAMES, TrialMate, TrialPair, fragment, make_mate, random_template, sam_text, template_bases
+
+MARKER = 0xA7
+UNMAPPED_BIN = 4680
+_CIGAR_OPS = b"MIDNSHP=X"
+_SEQ_CODES = b"=ACMGRSVTWYHKDBN"
+
+
+# ------------------------------------------------------------------------------------------------ the decoder
+def reg2bin(beg, end):
+    """SAM specification 5.3"""
+    end -= 1
+    for shift, first in ((14, 4681), (17, 585), (20, 73), (23, 9), (26, 1)):
+        if beg >> shift == end >> shift:
+            return first + (beg >> shift)
+    return 0
+
+
+def decode_bam(data, names):
+    """(the SAM text of the uncompressed records in `data`, their fixed fields as dicts).  Asserts what SAM text cannot show: block_size, l_read_name, bin."""
+    lines, records, at = [], [], 0
+    while at < len(data):
+        assert at + 36 <= len(data)
+        (block_size,) = struct.unpack_from("<i", data, at)
+        at += 4
+        end = at + block_size
+        assert block_size >= 32 and end <= len(data), (block_size, at, len(data))
+        ref_id, pos, l_read_name, mapq, bin_, n_cigar, flag, l_seq, next_ref_id, next_pos, tlen = struct.unpack_from("<iiBBHHHIiii", data, at)
+        p = at + 32
+        name = data[p:p + l_read_name]
+        assert l_read_name >= 2 and len(name) == l_read_name and name[-1:] == b"\0" and b"\0" not in name[:-1], name
+        p += l_read_name
+        elements = [(c >> 4, _CIGAR_OPS[c & 15]) for c in struct.unpack_from("<%dI" % n_cigar, data, p)]
+        p += 4 * n_cigar
+        packed = data[p:p + (l_seq + 1) // 2]
+        p += (l_seq + 1) // 2
+        assert len(packed) == (l_seq + 1) // 2 and (l_seq % 2 == 0 or packed[-1] & 15 == 0), "an odd length leaves the last low nibble 0"
+        seq = bytes(_SEQ_CODES[(packed[i >> 1] >> (0 if i & 1 else 4)) & 15] for i in range(l_seq))
+        qual = data[p:p + l_seq]
+        assert len(qual) == l_seq and all(q < 94 for q in qual)
+        p += l_seq
+        tags = []
+        while p < end:
+            tag, kind = data[p:p + 2], data[p + 2:p + 3]
+            p += 3
+            if kind == b"Z":
+                stop = data.index(b"\0", p)
+                tags.append(tag + b":Z:" + data[p:stop])
+                p = stop + 1
+            else:
+                assert kind == b"S", kind
+                tags.append(tag + b":i:%d" % struct.unpack_from("<H", data, p))
+                p += 2
+        assert p == end, "block_size is the bytes behind it"
+        mapped = not flag & 0x4
+        if mapped:
+            span = sum(n for n, op in elements if op in b"MD")
+            assert 0 <= ref_id < len(names) and next_ref_id == ref_id and pos >= 0 and next_pos >= 0
+            assert bin_ == reg2bin(pos, pos + max(span, 1)), (bin_, pos, span)
+        else:
+            assert (ref_id, pos, next_ref_id, next_pos, mapq, bin_, n_cigar, tlen) == (-1, -1, -1, -1, 0, UNMAPPED_BIN, 0, 0)
+        cigar = b"".join(b"%d%c" % e for e in elements) or b"*"
+        fields = [name[:-1], b"%d" % flag, names[ref_id] if ref_id >= 0 else b"*", b"%d" % (pos + 1), b"%d" % mapq, cigar, b"=" if next_ref_id >= 0 else b"*",
+                  b"%d" % (next_pos + 1), b"%d" % tlen, seq, bytes(q + 33 for q in qual)] + tags
+        lines.append(b"\t".join(fields) + b"\n")
+        records.append(dict(block_size=block_size, ref_id=ref_id, pos=pos, l_read_name=l_read_name, mapq=mapq, bin=bin_, n_cigar=n_cigar, flag=flag, l_seq=l_seq,
+                            next_ref_id=next_ref_id, next_pos=next_pos, tlen=tlen, packed=packed))
+        at = end
+    return b"".join(lines), records
+
+
+def decode_bam_header(data):
+    """(header text, [(name, length)], bytes used)"""
+    assert data[:4] == b"BAM\1"
+    (l_text,) = struct.unpack_from("<I", data, 4)
+    text = data[8:8 + l_text]
+    (n_ref,) = struct.unpack_from("<I", data, 8 + l_text)
+    at, refs = 12 + l_text, []
+    for _ in range(n_ref):
+        (l_name,) = struct.unpack_from("<I", data, at)
+        name = data[at + 4:at + 4 + l_name]
+        assert name[-1:] == b"\0"
+        (l_ref,) = struct.unpack_from("<I", data, at + 4 + l_name)
+        refs.append((name[:-1], l_ref))
+        at += 8 + l_name
+    return text, refs, at
+
+
+def test_the_decoder_on_a_record_spelled_out():
+    """the decoder itself against a record assembled by hand from the specification's example fields"""
+    name = b"r1\0"
+    body = struct.pack("<iiBBHHHIiii", 0, 99, len(name), 60, reg2bin(99, 104), 2, 99, 5, 0, 199, 150) + name + struct.pack("<II", 3 << 4 | 0, 2 << 4 | 4)
+    body += bytes([0x12, 0x48, 0xF0]) + bytes([30, 31, 32, 33, 2]) + b"XCZ3M2S\0" + b"XES" + struct.pack("<H", 7)
+    text, recs = decode_bam(struct.pack("<i", len(body)) + body, [b"chrA"])
+    assert text == b"r1\t99\tchrA\t100\t60\t3M2S\t=\t200\t150\tACGTN\t?@AB#\tXC:Z:3M2S\tXE:i:7\n" and recs[0]["bin"] == 4681
+    assert [reg2bin(0, 1), reg2bin((1 << 14) - 1, (1 << 14) + 1), reg2bin(1 << 26, (1 << 26) + 5), reg2bin((1 << 26) - 1, (1 << 26) + 1), reg2bin(-1, 0)] == [4681, 585, 4681 + (1 << 12), 0, 4680]
+
+
+# ------------------------------------------------------------------------------------------------ the header and the symbols
+def test_header_of_the_golden_reference():
+    ref = api.Reference(os.path.join(GOLDEN, "reference-test.fa"))
+    try:
+        text = ref.sam_header()
+        want = b"BAM\1" + struct.pack("<I", len(text)) + text + struct.pack("<I", 2)
+        for name, length in ((b"NC_000913.3_1-500", 500), (b"NC_000913.3_10000-10500", 501)):
+            want += struct.pack("<I", len(name) + 1) + name + b"\0" + struct.pack("<I", length)
+        assert ref.bam_header() == want
+        assert decode_bam_header(want) == (text, [(b"NC_000913.3_1-500", 500), (b"NC_000913.3_10000-10500", 501)], len(want))
+        need = C.c_size_t(0)
+        small = C.create_string_buffer(b"#" * (len(want) - 1), len(want) - 1)
+        assert api.lib().rsq_ref_bam_header(ref.h, small, len(want) - 1, C.byref(need)) == api.RSQ_ENOSPC
+        assert need.value == len(want) and small.raw == b"#" * (len(want) - 1)
+        need = C.c_size_t(0)
+        assert api.lib().rsq_ref_bam_header(ref.h, None, 0, C.byref(need)) == api.RSQ_ENOSPC and need.value == len(want)
+        exact = C.create_string_buffer(len(want))
+        assert api.lib().rsq_ref_bam_header(ref.h, exact, len(want), C.byref(need)) == api.RSQ_OK and exact.raw == want
+    finally:
+        ref.close()
+
+
+def test_abi_symbols():
+    header = open(os.path.join(os.path.dirname(HERE), "include", "reseq_amd.h")).read()
+    for name in ("rsq_sim_pairs_bam", "rsq_sim_adapter_only_pairs_bam", "rsq_ref_bam_header"):
+        assert ("int %s(" % name) in header
+        assert getattr(api.lib(), name).argtypes is not None
+    for method in ("pairs_bam", "pairs_bam_device", "adapter_only_pairs_bam"):
+        assert callable(getattr(api.Simulator, method))
+    assert callable(api.Reference.bam_header)
+
+
+# ------------------------------------------------------------------------------------------------ the per-lane functions on the host
+@pytest.fixture(scope="module")
+def trial_lib(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("bam_trial") / "libbam_trial.so")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-shared", "-o", out,
+                    os.path.join(HERE, "hostemu", "bam_trial.cpp")], check=True)
+    L = C.CDLL(out)
+    L.bam_trial.argtypes = [C.POINTER(TrialPair), C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    return L
+
+
+def run_pair(L, mates, frag, phred_offset, adapter_only_number=0, tile=1101, base=b"ReseqRead_", names=NAMES, at=0):
+    """(fastq record 1, fastq record 2, the pair's two BAM records) from the trial library, the records written `at` bytes into a marked buffer: bam_record_size
+    is what bam_record wrote, nothing around the records is touched, and (inside the trial) the writer kernel's two sinks a mate give the same bytes"""
+    name_ptr = np.concatenate([[0], np.cumsum([len(n) for n in names])]).astype(np.uint32)
+    t = TrialPair(has_fragment=0 if frag is None else 1, adapter_only_number=adapter_only_number, phred_offset=phred_offset, tile=tile, base_identifier=base,
+                  names=b"".join(names), name_ptr=name_ptr.ctypes.data)
+    if frag is not None:
+        t.seq, t.start, t.len, t.strand, t.block, t.number = (int(frag[k]) for k in ("seq", "start", "len", "strand", "block", "number"))
+    keep = []
+    for seg, m in enumerate(mates):
+        arrays = [np.ascontiguousarray(m[k]) if len(m[k]) else np.zeros(1, np.uint8) for k in ("seq", "qual", "ops")]
+        keep.append(arrays)
+        t.mate[seg] = TrialMate(m["read_len"], m["n_iter_m"], m["n_iter_s"], m["hard_clip"], m["num_errors"], *(a.ctypes.data for a in arrays))
+    cap = 8192
+    f1, f2 = (C.create_string_buffer(cap) for _ in range(2))
+    bam = C.create_string_buffer(bytes([MARKER]) * cap, cap)
+    sizes = np.zeros(6, np.uint32)
+    assert L.bam_trial(C.byref(t), f1, f2, bam, at, cap, sizes.ctypes.data) == 0
+    assert sizes[2] == sizes[4] and sizes[3] == sizes[5], sizes          # bam_record_size is the record's length
+    end = at + int(sizes[2]) + int(sizes[3])
+    assert bam.raw[:at] == bytes([MARKER]) * at and bam.raw[end:] == bytes([MARKER]) * (cap - end)
+    return f1.raw[:sizes[0]], f2.raw[:sizes[1]], bam.raw[at:end]
+
+
+def check_pair(L, mates, frag, phred_offset, names=NAMES, **kw):
+    f1, f2, bam = run_pair(L, mates, frag, phred_offset, names=names, **kw)
+    want = sam_text(None if frag is None else [frag], f1, f2, names, phred_offset)
+    got, records = decode_bam(bam, names)
+    assert got == want, (got, want, f1, f2)
+    assert len(records) == 2
+    return got, records
+
+
+LENGTHS = [1, 2, 3, 4, 5, 7, 8, 9, 30, 31, 150, 151]      # every residue modulo 8, odd lengths, the single-word row
+
+
+@pytest.mark.parametrize("phred_offset", [33, 64])
+def test_read_lengths_in_both_orientations(trial_lib, phred_offset):
+    """each length as the forward and as the reverse mate, without N, with N at both ends (both nibbles of the first and the last byte) and with N anywhere"""
+    rng = np.random.default_rng(2000 + phred_offset)
+    at = 0
+    for read_len in LENGTHS:
+        for strand in (0, 1):
+            for n_mode in ("none", "ends", "scattered"):
+                mates = []
+                for seg in (0, 1):
+                    n_adapter = int(rng.integers(0, read_len)) if rng.random() < 0.4 else 0
+                    m = make_mate(rng, random_template(rng, read_len - n_adapter, 0.1 if n_mode == "scattered" else 0.0), [M] * n_adapter, 0, phred_offset, with_n=n_mode == "scattered")
+                    assert m["read_len"] == read_len
+                    if n_mode == "ends":
+                        m["seq"][[0, min(1, read_len - 1), max(0, read_len - 2), read_len - 1]] = 4
+                    mates.append(m)
+                length = max(template_bases(m["ops"][:m["n_iter_m"]]) for m in mates) + int(rng.integers(0, 30))
+                got, records = check_pair(trial_lib, mates, fragment(int(rng.integers(0, 3)), int(rng.integers(0, 100000)), length, strand), phred_offset, at=at % 4)
+                at += 1
+                assert [r["flag"] for r in records] == ([99, 147] if strand == 0 else [83, 163])
+                assert all(r["l_seq"] == read_len and r["mapq"] == 60 for r in records)
+                if n_mode == "ends":
+                    for r in records:                              # N is 15 in either orientation, in the high and in the low nibble
+                        assert r["packed"][0] >> 4 == 15 and (read_len < 2 or (r["packed"][0] & 15 == 15 and r["packed"][(read_len - 1) >> 1] >> (0 if (read_len - 1) & 1 else 4) & 15 == 15))
+
+
+def test_packed_bases_spelled_out(trial_lib):
+    """literal nibbles, independent of the decoder's table: ACGTN forward is 12 48 F0; its reverse complement NACGT is F1 24 80"""
+    rng = np.random.default_rng(3)
+    m = make_mate(rng, [M] * 5, [], 0, 33)
+    m["seq"][:] = [0, 1, 2, 3, 4]
+    m["qual"][:] = [33 + 2, 33 + 10, 33 + 20, 33 + 30, 33 + 40]
+    other = make_mate(rng, [M] * 8, [], 0, 33)
+    for seg, want_seq, want_qual in ((0, bytes([0x12, 0x48, 0xF0]), bytes([2, 10, 20, 30, 40])), (1, bytes([0xF1, 0x24, 0x80]), bytes([40, 30, 20, 10, 2]))):
+        _, _, bam = run_pair(trial_lib, [m, other] if seg == 0 else [other, m], fragment(0, 100, 20, 0), 33)
+        _, records = decode_bam(bam, NAMES)
+        rec_at = 0 if seg == 0 else 4 + records[0]["block_size"]
+        r = records[seg]
+        seq_at = rec_at + 36 + r["l_read_name"] + 4 * r["n_cigar"]
+        assert bam[seq_at:seq_at + 3] == want_seq and bam[seq_at + 3:seq_at + 8] == want_qual
+        assert bam[seq_at + 8:seq_at + 11] == b"XCZ" and bam[rec_at + 4 + r["block_size"] - 5:rec_at + 4 + r["block_size"] - 2] == b"XES"
+
+
+@pytest.mark.parametrize("phred_offset", [33, 64])
+@pytest.mark.parametrize("name", ["leading D (ReSeq prints 0M first)", "trailing D", "D at both ends", "leading I", "a template part of D alone", "I and D inside the adapter part",
+                                  "a tail alone behind the template", "long plain stretches around an indel"])
+def test_crafted_ops(trial_lib, name, phred_offset):
+    rng = np.random.default_rng(sorted(CRAFTED).index(name) * 2 + phred_offset)
+    template_ops, adapter_ops, tail = CRAFTED[name]
+    plain = make_mate(rng, [M] * 21, [M] * 3, 1, phred_offset)
+    for strand in (0, 1):
+        for seg in (0, 1):                                    # the crafted mate as either segment: forward and reverse
+            crafted = make_mate(rng, template_ops, adapter_ops, tail, phred_offset, with_n=True)
+            mates = [plain, crafted] if seg else [crafted, plain]
+            length = max(21, template_bases(template_ops)) + 5
+            got, records = check_pair(trial_lib, mates, fragment(1, 4321, length, strand), phred_offset, at=seg + 1)
+            cigar = got.splitlines()[seg].split(b"\t")[5]
+            assert records[seg]["n_cigar"] == sum(chr(c).isalpha() for c in cigar)
+            if name == "a template part of D alone":          # the CIGAR is the clip alone: no reference bases, the bin is that of one base
+                assert cigar == b"4S" and records[seg]["bin"] == reg2bin(records[seg]["pos"], records[seg]["pos"] + 1)
+
+
+def test_a_plain_pair(trial_lib):
+    rng = np.random.default_rng(21)
+    mates = [make_mate(rng, [M] * 30, [], 0, 33), make_mate(rng, [M] * 30, [], 0, 33)]
+    got, records = check_pair(trial_lib, mates, fragment(0, 999, 100, 0), 33)
+    assert [r["n_cigar"] for r in records] == [1, 1] and [r["pos"] for r in records] == [999, 1069] and [r["tlen"] for r in records] == [100, -100]
+
+
+def test_unmapped_pairs(trial_lib):
+    rng = np.random.default_rng(9)
+    for phred_offset in (33, 64):
+        mates = [make_mate(rng, [], [M] * 9 + [I, M, D, M], 5, phred_offset), make_mate(rng, [], [M] * 12, 3, phred_offset, with_n=True)]
+        got, records = check_pair(trial_lib, mates, None, phred_offset, adapter_only_number=4_300_000_123, at=3)
+        assert [r["flag"] for r in records] == [77, 141] and got.startswith(b"ReseqRead_0_4300000123:0:Adapter:0:1101:1337:1337\t77\t*\t0\t0\t*\t*\t0\t0\t")
+        # SEQ and QUAL in FASTQ orientation (the decoder has asserted refID, pos, mapq, bin, n_cigar_op and tlen)
+        f1, f2, _ = run_pair(trial_lib, mates, None, phred_offset, adapter_only_number=4_300_000_123)
+        for line, fq in zip(got.splitlines(), (f1, f2)):
+            assert line.split(b"\t")[9] == fq.split(b"\n")[1]
+    # a fragment of length 0 inside rsq_sim_pairs is unmapped as well
+    got, records = check_pair(trial_lib, mates, fragment(2, 77, 0, 1), 64)
+    assert [r["flag"] for r in records] == [77, 141]
+
+
+def test_bins_inside_and_across_their_boundaries(trial_lib):
+    """[pos, end) of the 30M mate (forward, then reverse) below, across, ending at and beginning at every level's boundary; the other mate lies 170 bases away"""
+    rng = np.random.default_rng(31)
+    names = [b"long"]
+    seen = set()
+    for shift in (14, 17, 20, 23, 26):
+        edge = 1 << shift
+        for start in (edge - 31, edge - 30, edge - 15, edge - 1, edge):
+            for strand in (0, 1):
+                mates = [make_mate(rng, [M] * 30, [], 0, 33), make_mate(rng, [M] * 12 + [D] + [M] * 18, [], 0, 33)]
+                frag = fragment(0, start - (170 if strand else 0), 200, strand)
+                got, records = check_pair(trial_lib, mates, frag, 33, names=names)
+                r = records[0]                                 # the 30M mate begins at `start` on either strand
+                assert r["pos"] == start
+                across = start < edge < start + 30
+                if across:                                     # the smallest bin that holds both sides of a level-`shift` boundary lies above that level
+                    assert r["bin"] < {14: 4681, 17: 585, 20: 73, 23: 9, 26: 1}[shift]
+                else:
+                    assert r["bin"] >= 4681
+                seen.add(r["bin"])
+    assert 0 in seen and len(seen) > 10
+
+
+def test_a_qname_of_254_bytes(trial_lib):
+    rng = np.random.default_rng(41)
+    mates = [make_mate(rng, [M] * 9, [], 0, 33), make_mate(rng, [M] * 9, [], 0, 33)]
+    frag = fragment(1, 12345, 50, 0)
+    short, _ = check_pair(trial_lib, mates, frag, 33, names=[b"a", b"b", b"c"])
+    filler = 254 - len(short.split(b"\t")[0]) + 1
+    names = [b"a", b"n" * filler, b"c"]
+    got, records = check_pair(trial_lib, mates, frag, 33, names=names, at=1)
+    assert [len(line.split(b"\t")[0]) for line in got.splitlines()] == [254, 254] and [r["l_read_name"] for r in records] == [255, 255]
