@@ -278,7 +278,9 @@ int rsq_sim_job_compress(rsq_sim *s, uint64_t *r1_bytes, uint64_t *r2_bytes);
  * names of main.cpp:404,412): text_dev[0, text_len) -- device memory -- as gzip members (RFC 1952) one behind the other in out_dev, every member the deflate
  * (RFC 1951, one block with a dynamic Huffman code taken from a sample of the call's text) of at most 65280 bytes of text, framed like a BGZF block (extra field
  * "BC"); concatenated members are a gzip file for zlib's gzread, gzip -d, SeqAn and bgzip alike.  *out_len = their bytes; RSQ_ENOSPC (and the size needed) if
- * out_cap is smaller -- rsq_gzip_bound(text_len) always suffices.  Kernel time: "gzip".  rsq_sim_job_compress uses it unless option host_gzip is 1. */
+ * out_cap is smaller -- rsq_gzip_bound(text_len) always suffices.  Kernel time: "gzip".  rsq_sim_job_compress uses it unless option host_gzip is 1.  The members
+ * are a function of the text, of the code (a kept one: below) and of option gzip_route (0 / 1: the text searched by FASTQ lines / densely, whatever the sample
+ * says; -1, the default: the sample decides) alone -- not of the addresses, nor of option gzip_stretch (pieces per pass through the slots, default 8192). */
 size_t rsq_gzip_bound(size_t text_len);
 /* the 28 bytes that end a BGZF file (an empty member; bgzip / htslib warn when it is missing, gzip / zlib / SeqAn read it as no text): returns 28 and, with room,
  * writes them to out.  The members of rsq_sim_gzip_device are framed as BGZF blocks; whoever finishes a file of them appends this one (the command line, the

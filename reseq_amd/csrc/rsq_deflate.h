@@ -99,7 +99,7 @@ RSQ_HD uint32_t low_zero_bytes(uint32_t x) {           // number of low bytes of
     return (uint32_t)__builtin_ctz(x) >> 3;
 #endif
 }
-// Where the walk reads the piece: plain memory (the host), or the ring of its last kRing bytes in LDS (the device; byte p at p mod kRing, the ring's first four
+// Where the walk reads the piece: plain memory (the host), or the ring of its last kRing bytes in LDS (the device; byte p at p mod kRing, the ring's first
 // bytes repeated behind its end so that a word may begin on its last three bytes)
 struct PlainText {
     const uint8_t *t;
@@ -112,17 +112,34 @@ struct PlainText {
         return v;
     }
 };
+// What a round does to the ring, for the kernel (ring_load) and for the ring of tests/hostemu alike: bytes [from, to) of the piece are new -- the round and kAhead
+// bytes behind it; the first round brings its own bytes as well -- and everything older stays.  The walk also reads a little BEHIND the piece's end: the second word
+// of a six-byte key (phase A1), and the last segment whole.  Those slots hold text kRing bytes back, or, in a piece shorter than the ring, whatever the LDS held
+// before; so every round zeroes [zero_from, zero_to) = the kRingTail bytes behind what it loaded (the next round's text overwrites them; behind the piece's end they
+// stay), which is what PlainText reads there.  A member is then a function of its text alone.  No match loses history by it: the slots' old text lies further back
+// than any match of the round reaches.
+constexpr uint32_t kRingRepeat = 16u;                // the ring's first bytes stand again behind its end: a word, or a thread's 16 bytes, may begin on its last bytes
+constexpr uint32_t kRingTail = 48u;                  // a segment and a word, rounded up to 16
+static_assert(kRingTail >= kSeg + 4u && kRingTail <= kThreads && kMaxDist + kRound + kAhead + kRingTail <= kRing, "the zeroed bytes behind a round's text displace no text that a match may reach");
+struct RingRound {
+    uint32_t from, to, zero_from, zero_to;
+};
+RSQ_HD uint32_t ring_index(uint32_t p) { return p & (kRing - 1u); }
+RSQ_HD RingRound ring_round(uint32_t round_lo, uint32_t len) {
+    const uint32_t to = round_lo + kRound + kAhead < len ? round_lo + kRound + kAhead : len;
+    return RingRound{round_lo ? round_lo + kAhead : 0u, to, to, to + kRingTail};
+}
 struct RingText {
     const RSQ_LDS uint8_t *ring;
-    RSQ_HD uint32_t byte(uint32_t p) const { return ring[p & (kRing - 1u)]; }
+    RSQ_HD uint32_t byte(uint32_t p) const { return ring[ring_index(p)]; }
     RSQ_HD uint32_t word(uint32_t p) const {
 #if defined(__HIP_DEVICE_COMPILE__)
         // two aligned words and a byte shift: an unaligned word would be read byte by byte
-        const RSQ_LDS uint32_t *w = reinterpret_cast<const RSQ_LDS uint32_t *>(ring) + ((p & (kRing - 1u)) >> 2);
+        const RSQ_LDS uint32_t *w = reinterpret_cast<const RSQ_LDS uint32_t *>(ring) + (ring_index(p) >> 2);
         return __builtin_amdgcn_alignbyte(w[1], w[0], p & 3u);
 #else
         uint32_t v;
-        memcpy(&v, ring + (p & (kRing - 1u)), 4);
+        memcpy(&v, ring + ring_index(p), 4);
         return v;
 #endif
     }
@@ -448,10 +465,10 @@ __device__ inline void ring_load(RSQ_LDS uint8_t *ring, const uint8_t *t, uint32
     const uint32_t tid = threadIdx.x;
     if ((((uintptr_t)t | lo) & 15u) == 0) {
         const uint32_t whole = (hi - lo) / 16u;
-        for (uint32_t i = tid; i < whole; i += kThreads) *reinterpret_cast<RSQ_LDS uint4 *>(ring + ((lo + 16u * i) & (kRing - 1u))) = *reinterpret_cast<const uint4 *>(t + lo + 16u * i);
-        for (uint32_t p = lo + 16u * whole + tid; p < hi; p += kThreads) ring[p & (kRing - 1u)] = t[p];
+        for (uint32_t i = tid; i < whole; i += kThreads) *reinterpret_cast<RSQ_LDS uint4 *>(ring + ring_index(lo + 16u * i)) = *reinterpret_cast<const uint4 *>(t + lo + 16u * i);
+        for (uint32_t p = lo + 16u * whole + tid; p < hi; p += kThreads) ring[ring_index(p)] = t[p];
     } else
-        for (uint32_t p = lo + tid; p < hi; p += kThreads) ring[p & (kRing - 1u)] = t[p];
+        for (uint32_t p = lo + tid; p < hi; p += kThreads) ring[ring_index(p)] = t[p];
 }
 // The bits of `total` more bits stand in the round's buffer from bit `frac` (< 32) on: its complete words go to the member's data (coalesced), the buffer is zeroed
 // and the last, incomplete word moves to its front.  Returns the number of words written.  All threads; barriers inside.
@@ -519,13 +536,14 @@ __global__ void __launch_bounds__(kThreads) k_gzip_pieces(const uint8_t *text, u
     }
     for (uint32_t round_lo = 0; round_lo < len; round_lo += kRound) {
         const uint32_t round_hi = round_lo + kRound < len ? round_lo + kRound : len;
-        // the ring: this round and kAhead bytes behind it are new (the first round brings its own bytes as well), everything older stays
+        // the ring (ring_round): this round and kAhead bytes behind it are new, everything older stays; zeros behind them, which stay behind the piece's end
         {
-            const uint32_t from = round_lo ? round_lo + kAhead : 0u, to = round_lo + kRound + kAhead < len ? round_lo + kRound + kAhead : len;
+            const RingRound r = ring_round(round_lo, len);
             __syncthreads();
-            if (from < to) ring_load(ring, t, from, to);
+            if (r.from < r.to) ring_load(ring, t, r.from, r.to);
+            if (tid < r.zero_to - r.zero_from) ring[ring_index(r.zero_from + tid)] = 0u;
             __syncthreads();
-            if (tid < 16u) ring[kRing + tid] = ring[tid];
+            if (tid < kRingRepeat) ring[kRing + tid] = ring[tid];
         }
         __syncthreads();
         RSQ_GZ_MARK(0);
@@ -589,7 +607,7 @@ __global__ void __launch_bounds__(kThreads) k_gzip_pieces(const uint8_t *text, u
         // entered is its candidate, kept as a distance (for the probed positions: the others inherit)
         for (uint32_t group = round_lo; group < round_hi; group += kThreads) {
             const uint32_t p = group + tid, rel = p - round_lo;
-            const bool hashed = p + 4u <= len && (STEP == 1u || ((s_kind[rel / kSeg] >> (rel % kSeg)) & 1u));      // (bytes behind the piece's end may be anything: they are never counted)
+            const bool hashed = p + 4u <= len && (STEP == 1u || ((s_kind[rel / kSeg] >> (rel % kSeg)) & 1u));      // (a key's last bytes may lie behind the piece's end: zeros, ring_round)
             const uint32_t h = hashed ? (STEP == 1u ? hash4(rt.word(p)) : hash6(rt.word(p), rt.word(p + 4u))) : 0u, cand = hashed ? head[h] : 0u;
             __syncthreads();
             if (hashed) atomicMax(&head[h], p + 1u);
@@ -870,10 +888,40 @@ inline Codes build_codes(const uint32_t *sample) {
 }
 
 // ---------------------------------------------------------------------------------------- host: a piece, thread by thread (tests/hostemu)
+// Where the host's walk reads the piece.  PlainPiece: the text where it lies, zeros behind its end.  RingPiece: a ring like the kernel's, filled round by round by the
+// kernel's own rule (ring_round, ring_index) and full of `fill` before -- the LDS of a workgroup holds whatever the workgroup before it left -- so that the ring's
+// index arithmetic runs on the CPU and every byte the kernel can see that is not the piece's text is seen by this walk too.
+struct PlainPiece : PlainText {
+    PlainPiece(const uint8_t *text, uint32_t len) : PlainText{text, len} {}
+    void round(uint32_t) {}
+    void segment(uint32_t lo, uint32_t *words) const {                // the 32 bytes of a thread's segment
+        for (uint32_t k = 0; k < kSeg / 4u; ++k) words[k] = word(lo + 4u * k);
+    }
+};
+struct RingPiece {
+    std::vector<uint8_t> bytes;
+    const uint8_t *text;
+    uint32_t len;
+    RingPiece(const uint8_t *text_, uint32_t len_, uint8_t fill) : bytes(kRing + kRingRepeat, fill), text(text_), len(len_) {}
+    uint32_t byte(uint32_t p) const { return bytes[ring_index(p)]; }
+    uint32_t word(uint32_t p) const { return load4(bytes.data() + ring_index(p)); }
+    void round(uint32_t round_lo) {
+        const RingRound r = ring_round(round_lo, len);
+        for (uint32_t p = r.from; p < r.to; ++p) bytes[ring_index(p)] = text[p];
+        for (uint32_t p = r.zero_from; p < r.zero_to; ++p) bytes[ring_index(p)] = 0u;
+        for (uint32_t i = 0; i < kRingRepeat; ++i) bytes[kRing + i] = bytes[i];
+    }
+    void segment(uint32_t lo, uint32_t *words) const { memcpy(words, bytes.data() + ring_index(lo), kSeg); }
+};
+// why a piece was not coded (piece_on_the_host_t gave it up: it is stored)
+struct PieceNote {
+    uint32_t stored_why = 0;             // 0: coded; 1: a round's bits overflowed the round's buffer; 2: no smaller than stored
+    uint32_t overflow_round = 0;         // the first round that overflowed
+};
 // The device's walk with the workgroup's threads taken one after the other: `hist` != nullptr counts the piece's symbols (the sample), else the member is written
 // to out (kSlot bytes, zeroed here); returns the member's size, 0 where the device gives the piece up (a round's bits beyond its buffer, or no smaller than stored).
-template <uint32_t STEP>
-inline uint32_t piece_on_the_host_t(const uint8_t *text, uint32_t n, const Codes *codes, uint8_t *out, uint32_t *hist) {
+template <uint32_t STEP, class Piece>
+inline uint32_t piece_on_the_host_t(Piece &tx, const uint8_t *text, uint32_t n, const Codes *codes, uint8_t *out, uint32_t *hist, PieceNote *note) {
     std::vector<uint32_t> head((size_t)1 << kHashBits, 0);
     std::vector<uint16_t> found(kRound / STEP);
     std::vector<uint32_t> data((size_t)kSlotWords + kOutWords + 4, 0);      // the deflate data, all of it in one buffer of bits
@@ -887,19 +935,19 @@ inline uint32_t piece_on_the_host_t(const uint8_t *text, uint32_t n, const Codes
         for (uint32_t w = 0; w * 32u < codes->header_bits; ++w) data[w] = codes->header[w];
         bit = codes->header_bits;
     }
-    const PlainText pt{text, n};
     uint32_t line_state = kLineStateAtStart;
     for (uint32_t round_lo = 0; round_lo < n; round_lo += kRound) {
         const uint32_t round_hi = std::min(n, round_lo + kRound);
+        tx.round(round_lo);
         std::fill(found.begin(), found.end(), 0);
         // the lines of the round: per segment which of its positions are searched, and the bytes that repeat the byte before them
         std::vector<uint32_t> kinds(kThreads, 0), eqs(kThreads, 0);
         for (uint32_t t = 0; t < kThreads; ++t) {
             const uint32_t lo = round_lo + t * kSeg;
-            uint32_t words[kSeg / 4u] = {0};
-            for (uint32_t i = 0; i < kSeg && lo + i < n; ++i) words[i >> 2] |= (uint32_t)text[lo + i] << ((i & 3u) * 8u);
+            uint32_t words[kSeg / 4u];
+            tx.segment(lo, words);
             const uint32_t valid = lo >= round_hi ? 0u : (round_hi - lo >= kSeg ? 0xFFFFFFFFu : (1u << (round_hi - lo)) - 1u);
-            const uint32_t starts = ((bytes_equal_to(words, '\n') << 1) | (lo && lo < round_hi && text[lo - 1u] == '\n' ? 1u : 0u)) & valid, at = bytes_equal_to(words, '@');
+            const uint32_t starts = ((bytes_equal_to(words, '\n') << 1) | (lo && lo < round_hi && tx.byte(lo - 1u) == '\n' ? 1u : 0u)) & valid, at = bytes_equal_to(words, '@');
             kinds[t] = (STEP == 1u ? 0xFFFFFFFFu : line_kinds(line_state, starts, at)) & valid;
             eqs[t] = bytes_equal_to_previous(words);
             line_state = line_apply(line_transfer(starts, at), line_state);
@@ -909,7 +957,7 @@ inline uint32_t piece_on_the_host_t(const uint8_t *text, uint32_t n, const Codes
         for (uint32_t group = round_lo; group < round_hi; group += kThreads) {
             uint32_t cand[kThreads];
             auto searched = [&](uint32_t p) { return p < round_hi && ((kinds[(p - round_lo) / kSeg] >> ((p - round_lo) % kSeg)) & 1u) && p + 4u <= n; };
-            auto hash_at = [&](uint32_t p) { return STEP == 1u ? hash4(load4(text + p)) : hash6(load4(text + p), pt.word(p + 4u)); };
+            auto hash_at = [&](uint32_t p) { return STEP == 1u ? hash4(tx.word(p)) : hash6(tx.word(p), tx.word(p + 4u)); };
             for (uint32_t t = 0; t < kThreads; ++t) cand[t] = searched(group + t) ? head[hash_at(group + t)] : 0u;
             for (uint32_t t = 0; t < kThreads; ++t)
                 if (searched(group + t)) {
@@ -924,7 +972,7 @@ inline uint32_t piece_on_the_host_t(const uint8_t *text, uint32_t n, const Codes
         // phase A2: every kProbeStep-th searched position is probed, the positions behind it inherit
         for (uint32_t p = round_lo; p < round_hi; p += STEP) {
             if (!((kinds[(p - round_lo) / kSeg] >> ((p - round_lo) % kSeg)) & 1u)) continue;
-            found[(p - round_lo) / STEP] = (uint16_t)probe(pt, n, round_lo, p, found[(p - round_lo) / STEP]);
+            found[(p - round_lo) / STEP] = (uint16_t)probe(tx, n, round_lo, p, found[(p - round_lo) / STEP]);
         }
         uint32_t round_bits = 0;
         std::vector<SegmentT<STEP>> segs(kThreads);
@@ -936,8 +984,7 @@ inline uint32_t piece_on_the_host_t(const uint8_t *text, uint32_t n, const Codes
             memset(&g, 0, sizeof g);
             g.kind = kinds[t];
             g.eq = eqs[t];
-            for (uint32_t i = 0; i < kSeg; ++i)
-                if (lo + i < n) g.text[i >> 2] |= (uint32_t)text[lo + i] << ((i & 3u) * 8u);
+            tx.segment(lo, g.text);
             for (uint32_t j = 0; j < kSeg / STEP; ++j) g.found[j >> 1] |= (uint32_t)found[(lo - round_lo) / STEP + j] << ((j & 1u) * 16u);
             if (hist) {
                 auto add = [hist](uint32_t s) { ++hist[s]; };
@@ -951,7 +998,10 @@ inline uint32_t piece_on_the_host_t(const uint8_t *text, uint32_t n, const Codes
             }
         }
         if (hist) continue;
-        if ((bit & 31u) + round_bits > kOutWords * 32u) overflow = true;                     // the device's buffer for a round's bits
+        if ((bit & 31u) + round_bits > kOutWords * 32u && !overflow) {                       // the device's buffer for a round's bits
+            overflow = true;
+            if (note) note->stored_why = 1u, note->overflow_round = round_lo / kRound;
+        }
         if (overflow) continue;
         for (uint32_t t = 0; t < kThreads; ++t) {
             BitSink<const uint32_t *, Or> sink{codes->litlen, codes->dist, Or{data.data() + (bit >> 5)}, (uint32_t)(bit & 31u)};
@@ -969,6 +1019,7 @@ inline uint32_t piece_on_the_host_t(const uint8_t *text, uint32_t n, const Codes
     }
     bit += codes->litlen[256] & 15u;
     const uint32_t data_bytes = (uint32_t)((bit + 7u) / 8u), member = kHeaderBytes + data_bytes + kTrailerBytes;
+    if (!overflow && data_bytes > 5u + n && note) note->stored_why = 2u;
     if (overflow || data_bytes > 5u + n) return 0;                   // as the device decides: no smaller than stored
     memset(out, 0, kSlot);
     memcpy(out + kSlotPad + kHeaderBytes, data.data(), data_bytes);
@@ -1009,8 +1060,15 @@ inline uint32_t stored_piece_on_the_host(const uint8_t *text, uint32_t n, uint8_
     }
     return member;
 }
-inline uint32_t piece_on_the_host(const uint8_t *text, uint32_t n, const Codes *codes, uint8_t *out, uint32_t *hist, bool dense = false) {
-    return dense ? piece_on_the_host_t<kDenseStep>(text, n, codes, out, hist) : piece_on_the_host_t<kProbeStep>(text, n, codes, out, hist);
+// ring_fill < 0: the walk reads the text where it lies (PlainPiece); 0..255: through a ring that was full of this byte (RingPiece)
+inline uint32_t piece_on_the_host(const uint8_t *text, uint32_t n, const Codes *codes, uint8_t *out, uint32_t *hist, bool dense = false, int ring_fill = -1, PieceNote *note = nullptr) {
+    if (note) *note = PieceNote{};
+    if (ring_fill < 0) {
+        PlainPiece tx(text, n);
+        return dense ? piece_on_the_host_t<kDenseStep>(tx, text, n, codes, out, hist, note) : piece_on_the_host_t<kProbeStep>(tx, text, n, codes, out, hist, note);
+    }
+    RingPiece tx(text, n, (uint8_t)ring_fill);
+    return dense ? piece_on_the_host_t<kDenseStep>(tx, text, n, codes, out, hist, note) : piece_on_the_host_t<kProbeStep>(tx, text, n, codes, out, hist, note);
 }
 // which pieces of a call are the sample: at most 64, spread evenly
 inline uint32_t sample_stride(uint64_t n_pieces) { return (uint32_t)std::max<uint64_t>(1, (n_pieces + 63) / 64); }
@@ -1033,12 +1091,14 @@ inline bool dense_pays(const uint32_t *sample_lines, const uint32_t *sample_dens
     return (double)dense < (1.0 - kDenseMustSave) * (double)lines;
 }
 // the whole call on the host (tests/hostemu): text -> members, appended to out
-inline void gzip_on_the_host(const uint8_t *text, uint64_t n, std::vector<uint8_t> &out, int force_route = -1 /* 0 / 1: FASTQ lines / dense, whatever the sample says */) {
+// ring_fill: piece_on_the_host's; notes: a PieceNote per piece; took_dense: the route of the call
+inline void gzip_on_the_host(const uint8_t *text, uint64_t n, std::vector<uint8_t> &out, int force_route = -1 /* 0 / 1: FASTQ lines / dense, whatever the sample says */,
+                             int ring_fill = -1, std::vector<PieceNote> *notes = nullptr, bool *took_dense = nullptr) {
     const uint64_t n_pieces = (n + kPiece - 1) / kPiece;
     const uint32_t stride = sample_stride(n_pieces);
     auto sample = [&](bool dense) {
         std::vector<uint32_t> hist(kLitLen + kDist, 0);
-        for (uint64_t i = 0; i < n_pieces; i += stride) piece_on_the_host(text + i * kPiece, (uint32_t)std::min<uint64_t>(kPiece, n - i * kPiece), nullptr, nullptr, hist.data(), dense);
+        for (uint64_t i = 0; i < n_pieces; i += stride) piece_on_the_host(text + i * kPiece, (uint32_t)std::min<uint64_t>(kPiece, n - i * kPiece), nullptr, nullptr, hist.data(), dense, ring_fill);
         return hist;
     };
     std::vector<uint32_t> hist = sample(force_route == 1);
@@ -1050,10 +1110,12 @@ inline void gzip_on_the_host(const uint8_t *text, uint64_t n, std::vector<uint8_
     }
     Codes codes = build_codes(hist.data());
     codes.dense = dense ? 1u : 0u;
+    if (took_dense) *took_dense = dense;
+    if (notes) notes->assign(n_pieces, PieceNote{});
     std::vector<uint8_t> slot(kSlot);
     for (uint64_t i = 0; i < n_pieces; ++i) {
         const uint32_t len = (uint32_t)std::min<uint64_t>(kPiece, n - i * kPiece);
-        uint32_t member = piece_on_the_host(text + i * kPiece, len, &codes, slot.data(), nullptr, dense);
+        uint32_t member = piece_on_the_host(text + i * kPiece, len, &codes, slot.data(), nullptr, dense, ring_fill, notes ? &(*notes)[i] : nullptr);
         if (!member) member = stored_piece_on_the_host(text + i * kPiece, len, slot.data());
         out.insert(out.end(), slot.begin() + kSlotPad, slot.begin() + kSlotPad + member);
     }

@@ -2055,19 +2055,22 @@ static void gzip_code_of(rsq_sim &s, const uint8_t *text, size_t n, hipStream_t 
     uint32_t *lines = s.gz_hist.as<uint32_t>(), *dense = lines + gz::kLitLen + gz::kDist;
     HIP_CHECK(hipMemsetAsync(lines, 0, 2 * (gz::kLitLen + gz::kDist) * 4, st));
     const dim3 grid((uint32_t)cdiv(n_pieces, stride)), block(gz::kThreads);
-    hipLaunchKernelGGL((gz::k_gzip_pieces<true, gz::kProbeStep>), grid, block, 0, st, text, (uint64_t)n, stride, (const gz::Codes *)nullptr, (uint8_t *)nullptr, (uint32_t *)nullptr, lines);
-    hipLaunchKernelGGL((gz::k_gzip_pieces<true, gz::kDenseStep>), grid, block, 0, st, text, (uint64_t)n, stride, (const gz::Codes *)nullptr, (uint8_t *)nullptr, (uint32_t *)nullptr, dense);
+    const int64_t route = s.opt.gzip_route;                          // < 0: the sample decides; 0 / > 0: by lines / dense whatever it says (only that route's sample is taken)
+    if (route <= 0)
+        hipLaunchKernelGGL((gz::k_gzip_pieces<true, gz::kProbeStep>), grid, block, 0, st, text, (uint64_t)n, stride, (const gz::Codes *)nullptr, (uint8_t *)nullptr, (uint32_t *)nullptr, lines);
+    if (route != 0)
+        hipLaunchKernelGGL((gz::k_gzip_pieces<true, gz::kDenseStep>), grid, block, 0, st, text, (uint64_t)n, stride, (const gz::Codes *)nullptr, (uint8_t *)nullptr, (uint32_t *)nullptr, dense);
     HIP_CHECK(hipGetLastError());
     uint32_t hist[2][gz::kLitLen + gz::kDist];
     HIP_CHECK(hipMemcpyAsync(hist, lines, sizeof hist, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
-    s.gz_dense = gz::dense_pays(hist[0], hist[1]);
+    s.gz_dense = route < 0 ? gz::dense_pays(hist[0], hist[1]) : route > 0;
     gz::Codes codes = gz::build_codes(hist[s.gz_dense ? 1 : 0]);
     codes.dense = s.gz_dense ? 1u : 0u;
     HIP_CHECK(hipMemcpyAsync(s.gz_codes.as<char>(), &codes, sizeof codes, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipStreamSynchronize(st));                             // `codes` leaves scope
 }
-// text[0, n) of device memory as gzip members behind each other in out (device memory, room for out_cap bytes): stretches of at most kGzipStretch pieces go through
+// text[0, n) of device memory as gzip members behind each other in out (device memory, room for out_cap bytes): stretches of at most kGzipStretch pieces (option gzip_stretch: of so many) go through
 // the slots (compress, store what did not fit, scan the sizes, move the members into place).  *out_len = the bytes of all members; more than out_cap: nothing
 // useful is in out, RSQ_ENOSPC.  with_code: the call's code is taken from this text first (else the caller has set it: several arrays of one job share a code).
 constexpr uint64_t kGzipStretch = 8192;                              // pieces per pass: 535 MB of text, as much again in slots
@@ -2079,7 +2082,7 @@ static int gzip_device(rsq_sim &s, const uint8_t *text, size_t n, uint8_t *out, 
         s.gz_have_code = true;
     }
     const uint64_t n_pieces = cdiv(n, gz::kPiece);
-    const uint64_t stretch = std::min<uint64_t>(n_pieces, kGzipStretch);
+    const uint64_t stretch = std::min<uint64_t>(n_pieces, s.opt.gzip_stretch > 0 ? (uint64_t)s.opt.gzip_stretch : kGzipStretch);
     s.gz_slots.reserve(stretch * gz::kSlot);
     s.gz_sizes.reserve(stretch * 4);
     s.gz_at.reserve((stretch + 1) * 8);

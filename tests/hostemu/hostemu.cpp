@@ -699,9 +699,24 @@ int emu_gzip(const uint8_t *text, uint64_t n, int force_stored, uint8_t *out, ui
                 const uint32_t m = rsq::gz::stored_piece_on_the_host(text + at, (uint32_t)std::min<uint64_t>(rsq::gz::kPiece, n - at), slot.data());
                 members.insert(members.end(), slot.begin() + rsq::gz::kSlotPad, slot.begin() + rsq::gz::kSlotPad + m);
             }
-        } else rsq::gz::gzip_on_the_host(text, n, members);
+        } else rsq::gz::gzip_on_the_host(text, n, members, (int)std::max<int64_t>(-1, std::min<int64_t>(1, options().gzip_route)));      // option gzip_route, as the library takes it
         *len = members.size();
         if (members.size() <= cap && !members.empty()) memcpy(out, members.data(), members.size());
+    });
+}
+// emu_gzip with the route given (-1: the sample decides, 0: FASTQ by its lines, 1: dense) and the walk reading the text through a ring like the kernel's that was full
+// of the byte ring_fill before (0..255; -1: the text where it lies, zeros behind its end, as emu_gzip reads it).  pieces (room for pieces_cap pieces, may be null): three
+// words per piece -- the route taken (0 / 1), why the piece was stored (0: it was not; 1: a round's bits overflowed the round's buffer; 2: no smaller than stored), and
+// the first round that overflowed.
+int emu_gzip_walk(const uint8_t *text, uint64_t n, int route, int ring_fill, uint8_t *out, uint64_t cap, uint64_t *len, uint32_t *pieces, uint64_t pieces_cap) {
+    return guard([&] {
+        std::vector<uint8_t> members;
+        std::vector<rsq::gz::PieceNote> notes;
+        bool dense = false;
+        rsq::gz::gzip_on_the_host(text, n, members, route, ring_fill, &notes, &dense);
+        *len = members.size();
+        if (members.size() <= cap && !members.empty()) memcpy(out, members.data(), members.size());
+        for (size_t i = 0; pieces && i < notes.size() && i < pieces_cap; ++i) pieces[3 * i] = dense ? 1u : 0u, pieces[3 * i + 1] = notes[i].stored_why, pieces[3 * i + 2] = notes[i].overflow_round;
     });
 }
 // the code a sample's counts lead to: lengths of the 286 + 30 symbols and the header's size, for the tests of the code builder

@@ -11,9 +11,8 @@ import numpy as np
 import pytest
 
 from backends import emu_lib
+from gzip_texts import PIECE, corpus, fastq_text, random_bytes, tail_text_t1, tail_text_t2
 from reseq_amd import synth
-
-PIECE = 65280
 
 
 def emu_gzip(text, force_stored=False):
@@ -24,6 +23,22 @@ def emu_gzip(text, force_stored=False):
     out = C.create_string_buffer(max(1, need.value))
     assert L.emu_gzip(text, len(text), int(force_stored), out, need.value, C.byref(need)) == 0
     return out.raw[:need.value]
+
+
+def emu_gzip_walk(text, route=-1, ring_fill=-1):
+    """the emulation with the route given (-1: the sample decides, 0: by lines, 1: dense), its walk reading the text where it lies (ring_fill -1) or through a ring like the
+    kernel's that was full of the byte ring_fill before; returns (members, per piece (route taken, why stored: 0 not / 1 a round overflowed / 2 no smaller than stored,
+    the round that overflowed))"""
+    L = emu_lib()
+    L.emu_gzip_walk.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64]
+    n_pieces = -(-len(text) // PIECE)
+    cap = len(text) + 31 * n_pieces
+    out = C.create_string_buffer(max(1, cap))
+    notes = np.zeros((max(1, n_pieces), 3), np.uint32)
+    need = C.c_uint64(0)
+    assert L.emu_gzip_walk(text, len(text), route, ring_fill, out, cap, C.byref(need), notes.ctypes.data, n_pieces) == 0
+    assert need.value <= cap, "text + 31 bytes bound every member"
+    return out.raw[:need.value], [tuple(int(x) for x in row) for row in notes[:n_pieces]]
 
 
 def members_of(blob):
@@ -44,20 +59,6 @@ def members_of(blob):
         at += bsize + 1
     assert at == len(blob)
     return out
-
-
-def fastq_text(n_records, seed=1, read_len=150, quality_values=40):
-    rng = np.random.default_rng(seed)
-    recs = []
-    pos = 1000
-    for i in range(n_records):
-        pos += int(rng.integers(0, 5))
-        seq = bytes(b"ACGT"[c] for c in rng.integers(0, 4, read_len))
-        q = rng.integers(0, quality_values, read_len)
-        q[rng.random(read_len) < 0.6] = quality_values - 1                     # long runs of the best quality, as real reads have
-        qual = bytes(int(x) + 35 for x in q)
-        recs.append(b"@ReseqRead%d_%d:%d:synthEcoli0:%d:0:1337:1337 %dM E%d\n%s\n+\n%s\n" % (1 + i // 1000, i % 1000, pos, pos + 350 + int(rng.integers(0, 40)), read_len, int(rng.integers(0, 3)), seq, qual))
-    return b"".join(recs)
 
 
 def test_members_inflate_to_the_text_and_carry_the_bgzf_frame():
@@ -142,6 +143,73 @@ def test_the_code_of_a_call():
         assert 17 + 4 * 3 <= bits.value <= 128 * 32
 
 
+# ------------------------------------------------------------------------------------------------------------------------- the corpus (gzip_texts.py)
+CORPUS = dict(corpus())
+ROUTES = (-1, 0, 1)                        # the sample decides, FASTQ by its lines, dense
+_walks = {}
+
+
+def walk_of(name, route):
+    """the emulation's members and notes for a text of the corpus by a route, computed once for all tests"""
+    if (name, route) not in _walks:
+        _walks[name, route] = emu_gzip_walk(CORPUS[name], route)
+    return _walks[name, route]
+
+
+def check_members(blob, text):
+    """the members carry the BGZF frame and inflate (members_of), their texts join to the input, every member is at most its text + 31 bytes (the kernel stores a
+    piece whose deflate data would be more than 5 + len bytes: 18 of header, 5 + len, 8 of trailer) and the whole is within rsq_gzip_bound"""
+    from reseq_amd import api
+    members = members_of(blob)
+    assert b"".join(t for _, t in members) == text
+    assert [len(t) for _, t in members] == [min(PIECE, len(text) - at) for at in range(0, len(text), PIECE)]
+    assert all(len(m) <= len(t) + 31 for m, t in members)
+    assert len(blob) <= api.lib().rsq_gzip_bound(len(text))
+
+
+@pytest.mark.parametrize("name", list(CORPUS))
+def test_corpus_on_the_host(name):
+    """every text by every route: members that inflate to the text within their bounds; and the walk that reads the text through a ring like the kernel's -- filled round by
+    round by the kernel's own rule, full of zeros, of 0xFF or of 'I' before -- writes the bytes of the walk over the text where it lies: a member is a function of its
+    text, whatever the LDS held.  (Without the zeros that a round puts behind the text it loads (gz::ring_round) this fails for T1, the T2 texts and the line of random bases.)"""
+    text = CORPUS[name]
+    for route in ROUTES:
+        blob, notes = walk_of(name, route)
+        check_members(blob, text)
+        assert route < 0 or all(r == route for r, _, _ in notes)
+        for fill in (0x00, 0xFF, ord("I")):
+            ring, ring_notes = emu_gzip_walk(text, route, fill)
+            assert ring == blob and ring_notes == notes, (name, route, fill)
+    assert emu_gzip(text) == walk_of(name, -1)[0]
+
+
+def test_the_corpus_reaches_the_paths_it_was_built_for():
+    notes = {name: walk_of(name, -1)[1] for name in CORPUS}
+    dense = [name for name, pieces in notes.items() if pieces and pieces[0][0] == 1]
+    lines = [name for name, pieces in notes.items() if pieces and pieces[0][0] == 0]
+    overflow_late = [(name, i) for name, pieces in notes.items() for i, (_, why, at_round) in enumerate(pieces) if why == 1 and at_round > 0]
+    no_smaller = [(name, i) for name, pieces in notes.items() for i, (_, why, _) in enumerate(pieces) if why == 2]
+    assert len(dense) >= 3 and len(lines) >= 8 and len(overflow_late) >= 1 and len(no_smaller) >= 2, (dense, lines, overflow_late, no_smaller)
+    # a stored piece is a stored member, and no other is
+    for name, pieces in notes.items():
+        members = members_of(walk_of(name, -1)[0])
+        assert [len(m) == len(t) + 31 and m[18] == 1 for m, t in members] == [why != 0 for _, why, _ in pieces], name
+
+
+def test_the_walks_under_the_sanitizers(tmp_path):
+    """tests/hostemu/gzip_trial.cpp, a program of its own built with -fsanitize=address,undefined: the corpus by both routes through the walk over the text and the walk
+    through the ring -- no read behind a text or the ring, no shift or index out of range"""
+    import os
+    import subprocess
+    exe, texts = str(tmp_path / "gzip_trial"), tmp_path / "texts.bin"
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-o", exe,
+                    os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostemu", "gzip_trial.cpp")], check=True)
+    texts.write_bytes(b"".join(struct.pack("<Q", len(t)) + t for t in CORPUS.values()))
+    r = subprocess.run([exe, str(texts)], capture_output=True, text=True)
+    assert r.returncode == 0 and f"{len(CORPUS)} texts" in r.stdout, (r.returncode, r.stdout, r.stderr[-4000:])
+
+
+
 # ------------------------------------------------------------------------------------------------------------------------- on the device
 @pytest.fixture(scope="module")
 def sim(tiny_profile_path):
@@ -179,6 +247,131 @@ def test_too_small_an_output_is_refused_with_the_size_needed(sim):
     assert api.lib().rsq_gzip_bound(len(text)) >= n
     src.free()
     out.free()
+
+
+@pytest.fixture(autouse=True)
+def gzip_route_back_to_its_default():
+    """rsq_options puts an option back to 0 when a test ends, which for gzip_route is not the default but "by lines": this fixture, set up before every other and so
+    torn down after them, puts the sample back in charge, in the library and in the emulation"""
+    yield
+    from backends import set_option_everywhere
+    set_option_everywhere("gzip_route", -1)
+
+
+def device_gzip(sim, rsq_options, text, route=-1, stretch=0, call=None):
+    """sim.gzip(text) -- or call() -- with the options gzip_route and gzip_stretch set in the library and the emulation; the simulator is back at the defaults afterwards"""
+    rsq_options("gzip_route", route)
+    rsq_options("gzip_stretch", stretch)
+    sim.take_options()
+    try:
+        return call() if call else sim.gzip(text)
+    finally:
+        rsq_options("gzip_route", -1)
+        rsq_options("gzip_stretch", 0)
+        sim.take_options()
+
+
+def test_the_emulation_takes_the_route_from_the_option(rsq_options):
+    """option gzip_route (rsq_host.h Options) in the emulation's emu_gzip, as the library takes it in rsq_sim_gzip_device"""
+    text = CORPUS["tiny fastq"][:PIECE + 3000]
+    by_route = [emu_gzip_walk(text, route)[0] for route in (0, 1)]
+    assert by_route[0] != by_route[1]
+    for route in (0, 1):
+        rsq_options("gzip_route", route)
+        assert emu_gzip(text) == by_route[route]
+
+
+def test_the_route_is_the_samples_again_behind_a_test_that_set_it():
+    from reseq_amd import api
+    assert emu_lib().emu_get_option(b"gzip_route") == -1 and api.get_option("gzip_route") == -1 and api.get_option("gzip_stretch") == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(CORPUS))
+def test_corpus_on_the_device(sim, rsq_options, name):
+    """every text of the corpus by both routes: the kernels' members inflate to the text within their bounds and are, byte for byte, the emulation's by the same route"""
+    text = CORPUS[name]
+    for route in (0, 1):
+        got = device_gzip(sim, rsq_options, text, route, call=lambda: (sim.gzip(text), emu_gzip(text)))
+        check_members(got[0], text)
+        assert got[0] == got[1] == walk_of(name, route)[0], (name, route)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tail_text", [tail_text_t2, tail_text_t1])
+def test_a_member_does_not_depend_on_what_the_lds_held(sim, rsq_options, tail_text):
+    """the walk reads behind a piece's end (gzip_texts.tail_text_t1, tail_text_t2): the same text before and after a text that leaves 'I' in the LDS of every compute unit
+    it ran on gives the same members, the emulation's.  By lines: the dense route takes no runs from the segment's own bytes and keys a position with four bytes."""
+    text = tail_text()
+    first, _, again = device_gzip(sim, rsq_options, text, route=0, call=lambda: (sim.gzip(text), sim.gzip(b"I" * 70000), sim.gzip(text)))
+    assert first == again == emu_gzip_walk(text, 0)[0]
+    check_members(first, text)
+
+
+@pytest.mark.gpu
+def test_text_and_members_at_odd_addresses(sim):
+    """the text at addresses 1, 3, 8 and 15 bytes behind a 16-byte boundary (ring_load and crc32_slice read 16 bytes at a time only where memory allows; the stored piece is
+    copied from there too), the members 0 to 3 bytes behind a word boundary (k_gzip_compact's leading bytes): the bytes of the aligned call"""
+    from reseq_amd import api
+    text = CORPUS["overflow in a late round"][:3 * PIECE + 1000]           # piece 1 is stored
+    lib, cap = api.lib(), api.lib().rsq_gzip_bound(len(text))
+    want, notes = emu_gzip_walk(text)
+    assert [why for _, why, _ in notes] == [0, 1, 0, 0]
+    assert sim.gzip(text) == want
+    src, out = api.DeviceArray(0, len(text) + 16), api.DeviceArray(0, cap + 4)
+    data = np.frombuffer(text, np.uint8)
+    try:
+        assert src.ptr.value % 16 == 0 and out.ptr.value % 4 == 0
+        for k in (1, 3, 8, 15):
+            assert lib.rsq_dev_upload(0, C.c_void_p(src.ptr.value + k), data.ctypes.data, len(text)) == api.RSQ_OK
+            for j in (0, 1, 2, 3):
+                n, rc = sim.gzip_device(src.ptr.value + k, len(text), out.ptr.value + j, cap)
+                assert rc == api.RSQ_OK and n == len(want)
+                got = np.zeros(n, np.uint8)
+                assert lib.rsq_dev_download(0, got.ctypes.data, C.c_void_p(out.ptr.value + j), n) == api.RSQ_OK
+                assert got.tobytes() == want, (k, j)
+    finally:
+        src.free()
+        out.free()
+
+
+@pytest.mark.gpu
+def test_stretches_of_three_pieces(sim, rsq_options):
+    """option gzip_stretch: eight pieces in passes of 3, 3 and 2 through three slots -- the bytes of the one pass, every pass's members behind the ones before at whatever
+    address they end; and an output one byte short is still refused with the exact size"""
+    from reseq_amd import api
+    text = CORPUS["fastq"][:8 * PIECE]
+    whole = sim.gzip(text)
+    assert whole == emu_gzip(text) and len(members_of(whole)) == 8
+
+    def in_stretches():
+        src = api.DeviceArray.from_numpy(0, np.frombuffer(text, np.uint8))
+        out = api.DeviceArray(0, len(whole))
+        try:
+            return sim.gzip(text), sim.gzip_device(src, len(text), out, len(whole) - 1), sim.gzip_device(src, len(text), out, len(whole)), out.to_numpy(np.uint8, len(whole)).tobytes()
+        finally:
+            src.free()
+            out.free()
+    by_three, short, exact, exact_bytes = device_gzip(sim, rsq_options, text, stretch=3, call=in_stretches)
+    assert by_three == whole
+    assert short == (len(whole), api.RSQ_ENOSPC)
+    assert exact == (len(whole), api.RSQ_OK) and exact_bytes == whole
+
+
+@pytest.mark.gpu
+def test_a_kept_code_serves_the_texts_behind_it(sim):
+    """rsq_sim_gzip_keep_code: the first call's code -- FASTQ's -- then serves random bytes, which it does not suit (members that inflate, each within its bound: stored
+    where the code would need more), and the same FASTQ text again, to the same bytes; without it a call has its own code again"""
+    a, b = CORPUS["fastq"][:2 * PIECE + 5000], random_bytes(2 * PIECE + 17, 31)
+    sim.gzip_keep_code(True)
+    try:
+        first, of_b, again = sim.gzip(a), sim.gzip(b), sim.gzip(a)
+    finally:
+        sim.gzip_keep_code(False)
+    check_members(of_b, b)
+    assert first == again == emu_gzip(a)
+    check_members(first, a)
+    assert sim.gzip(b) == emu_gzip(b)
 
 
 @pytest.mark.gpu
