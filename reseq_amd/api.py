@@ -308,25 +308,22 @@ class Reference:
         _check(lib().rsq_ref_sequence_name(self.h, i, buf, len(buf)))
         return buf.value.decode()
 
-    def sam_header(self):
-        """the header of the truth alignments (rsq_ref_sam_header): @HD, one @SQ per sequence, @PG"""
+    def _header(self, fn):
         need = C.c_size_t(0)
-        rc = lib().rsq_ref_sam_header(self.h, None, 0, C.byref(need))
+        rc = fn(self.h, None, 0, C.byref(need))
         if rc != RSQ_ENOSPC:
             _check(rc)
         buf = C.create_string_buffer(need.value + 1)
-        _check(lib().rsq_ref_sam_header(self.h, buf, need.value + 1, C.byref(need)))
+        _check(fn(self.h, buf, need.value + 1, C.byref(need)))
         return buf.raw[:need.value]
+
+    def sam_header(self):
+        """the header of the truth alignments (rsq_ref_sam_header): @HD, one @SQ per sequence, @PG"""
+        return self._header(lib().rsq_ref_sam_header)
 
     def bam_header(self):
         """the same header as the first bytes of a BAM file (rsq_ref_bam_header): magic, the text of sam_header(), the sequences' names and lengths; uncompressed"""
-        need = C.c_size_t(0)
-        rc = lib().rsq_ref_bam_header(self.h, None, 0, C.byref(need))
-        if rc != RSQ_ENOSPC:
-            _check(rc)
-        buf = C.create_string_buffer(need.value)
-        _check(lib().rsq_ref_bam_header(self.h, buf, need.value, C.byref(need)))
-        return buf.raw[:need.value]
+        return self._header(lib().rsq_ref_bam_header)
 
     def read_variants(self, path):
         """Reference::PrepareVariantFile + ReadFirstVariants: returns the number of alleles"""
@@ -558,89 +555,68 @@ class Simulator:
             for d in (r1, r2, fr):
                 d.free()
 
+    def _pairs_truth_device(self, fn, block_lo, block_hi, r1, r2, out, frags, stream):
+        l1, l2, ls, n = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_uint64()
+        rc = fn(self.h, block_lo, block_hi, r1.ptr if r1 else None, r1.nbytes if r1 else 0, C.byref(l1), r2.ptr if r2 else None, r2.nbytes if r2 else 0, C.byref(l2),
+                out.ptr if out else None, out.nbytes if out else 0, C.byref(ls), C.byref(n), frags.ptr if frags else None,
+                frags.nbytes // FRAGMENT_DTYPE.itemsize if frags else 0, stream)
+        return n.value, l1.value, l2.value, ls.value, rc
+
+    def _pairs_truth(self, fn, block_lo, block_hi, stream):
+        n, l1, l2, ls, rc = self._pairs_truth_device(fn, block_lo, block_hi, None, None, None, None, stream)
+        if rc == RSQ_OK and n == 0:
+            return np.zeros(0, FRAGMENT_DTYPE), b"", b"", b""
+        if rc != RSQ_ENOSPC:
+            _check(rc)
+        r1, r2, out = DeviceArray(self.device, l1), DeviceArray(self.device, l2), DeviceArray(self.device, ls)
+        fr = DeviceArray(self.device, (n + 1) * FRAGMENT_DTYPE.itemsize)
+        try:
+            n2, l1b, l2b, lsb, rc = self._pairs_truth_device(fn, block_lo, block_hi, r1, r2, out, fr, stream)
+            _check(rc)
+            assert (n2, l1b, l2b, lsb) == (n, l1, l2, ls)
+            return fr.to_numpy(FRAGMENT_DTYPE, n), r1.to_numpy(np.uint8, l1).tobytes(), r2.to_numpy(np.uint8, l2).tobytes(), out.to_numpy(np.uint8, ls).tobytes()
+        finally:
+            for d in (r1, r2, out, fr):
+                d.free()
+
+    def _adapter_only_pairs_truth(self, fn, first, n, stream):
+        l1, l2, ls = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        rc = fn(self.h, first, n, None, 0, C.byref(l1), None, 0, C.byref(l2), None, 0, C.byref(ls), stream)
+        if rc == RSQ_OK:
+            return b"", b"", b""
+        if rc != RSQ_ENOSPC:
+            _check(rc)
+        r1, r2, out = DeviceArray(self.device, l1.value), DeviceArray(self.device, l2.value), DeviceArray(self.device, ls.value)
+        try:
+            _check(fn(self.h, first, n, r1.ptr, r1.nbytes, C.byref(l1), r2.ptr, r2.nbytes, C.byref(l2), out.ptr, out.nbytes, C.byref(ls), stream))
+            return r1.to_numpy(np.uint8, l1.value).tobytes(), r2.to_numpy(np.uint8, l2.value).tobytes(), out.to_numpy(np.uint8, ls.value).tobytes()
+        finally:
+            for d in (r1, r2, out):
+                d.free()
+
     def pairs_sam_device(self, block_lo, block_hi, r1, r2, sam, frags=None, stream=None):
         """rsq_sim_pairs_sam into caller-owned DeviceArrays (None: only the sizes).  Returns (n_pairs, len1, len2, sam_len, rc)."""
-        l1, l2, ls, n = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_uint64()
-        rc = lib().rsq_sim_pairs_sam(self.h, block_lo, block_hi, r1.ptr if r1 else None, r1.nbytes if r1 else 0, C.byref(l1), r2.ptr if r2 else None, r2.nbytes if r2 else 0,
-                                     C.byref(l2), sam.ptr if sam else None, sam.nbytes if sam else 0, C.byref(ls), C.byref(n), frags.ptr if frags else None,
-                                     frags.nbytes // FRAGMENT_DTYPE.itemsize if frags else 0, stream)
-        return n.value, l1.value, l2.value, ls.value, rc
+        return self._pairs_truth_device(lib().rsq_sim_pairs_sam, block_lo, block_hi, r1, r2, sam, frags, stream)
 
     def pairs_sam(self, block_lo, block_hi, stream=None):
         """pairs() and the truth alignments of the same pairs: (fragments, fastq1 bytes, fastq2 bytes, SAM bytes without header); sized by a first call"""
-        n, l1, l2, ls, rc = self.pairs_sam_device(block_lo, block_hi, None, None, None, None, stream)
-        if rc == RSQ_OK and n == 0:
-            return np.zeros(0, FRAGMENT_DTYPE), b"", b"", b""
-        if rc != RSQ_ENOSPC:
-            _check(rc)
-        r1, r2, sam = DeviceArray(self.device, l1), DeviceArray(self.device, l2), DeviceArray(self.device, ls)
-        fr = DeviceArray(self.device, (n + 1) * FRAGMENT_DTYPE.itemsize)
-        try:
-            n2, l1b, l2b, lsb, rc = self.pairs_sam_device(block_lo, block_hi, r1, r2, sam, fr, stream)
-            _check(rc)
-            assert (n2, l1b, l2b, lsb) == (n, l1, l2, ls)
-            return fr.to_numpy(FRAGMENT_DTYPE, n), r1.to_numpy(np.uint8, l1).tobytes(), r2.to_numpy(np.uint8, l2).tobytes(), sam.to_numpy(np.uint8, ls).tobytes()
-        finally:
-            for d in (r1, r2, sam, fr):
-                d.free()
+        return self._pairs_truth(lib().rsq_sim_pairs_sam, block_lo, block_hi, stream)
 
     def adapter_only_pairs_sam(self, first, n, stream=None):
         """adapter_only_pairs() and the (unmapped) SAM records of the same pairs: (fastq1 bytes, fastq2 bytes, SAM bytes)"""
-        l1, l2, ls = C.c_size_t(), C.c_size_t(), C.c_size_t()
-        rc = lib().rsq_sim_adapter_only_pairs_sam(self.h, first, n, None, 0, C.byref(l1), None, 0, C.byref(l2), None, 0, C.byref(ls), stream)
-        if rc == RSQ_OK:
-            return b"", b"", b""
-        if rc != RSQ_ENOSPC:
-            _check(rc)
-        r1, r2, sam = DeviceArray(self.device, l1.value), DeviceArray(self.device, l2.value), DeviceArray(self.device, ls.value)
-        try:
-            _check(lib().rsq_sim_adapter_only_pairs_sam(self.h, first, n, r1.ptr, r1.nbytes, C.byref(l1), r2.ptr, r2.nbytes, C.byref(l2), sam.ptr, sam.nbytes, C.byref(ls), stream))
-            return r1.to_numpy(np.uint8, l1.value).tobytes(), r2.to_numpy(np.uint8, l2.value).tobytes(), sam.to_numpy(np.uint8, ls.value).tobytes()
-        finally:
-            for d in (r1, r2, sam):
-                d.free()
+        return self._adapter_only_pairs_truth(lib().rsq_sim_adapter_only_pairs_sam, first, n, stream)
 
     def pairs_bam_device(self, block_lo, block_hi, r1, r2, bam, frags=None, stream=None):
         """rsq_sim_pairs_bam into caller-owned DeviceArrays (None: only the sizes).  Returns (n_pairs, len1, len2, bam_len, rc)."""
-        l1, l2, ls, n = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_uint64()
-        rc = lib().rsq_sim_pairs_bam(self.h, block_lo, block_hi, r1.ptr if r1 else None, r1.nbytes if r1 else 0, C.byref(l1), r2.ptr if r2 else None, r2.nbytes if r2 else 0,
-                                     C.byref(l2), bam.ptr if bam else None, bam.nbytes if bam else 0, C.byref(ls), C.byref(n), frags.ptr if frags else None,
-                                     frags.nbytes // FRAGMENT_DTYPE.itemsize if frags else 0, stream)
-        return n.value, l1.value, l2.value, ls.value, rc
+        return self._pairs_truth_device(lib().rsq_sim_pairs_bam, block_lo, block_hi, r1, r2, bam, frags, stream)
 
     def pairs_bam(self, block_lo, block_hi, stream=None):
         """pairs() and the truth alignments of the same pairs as BAM records: (fragments, fastq1 bytes, fastq2 bytes, uncompressed BAM records without header); sized by a first call"""
-        n, l1, l2, ls, rc = self.pairs_bam_device(block_lo, block_hi, None, None, None, None, stream)
-        if rc == RSQ_OK and n == 0:
-            return np.zeros(0, FRAGMENT_DTYPE), b"", b"", b""
-        if rc != RSQ_ENOSPC:
-            _check(rc)
-        r1, r2, bam = DeviceArray(self.device, l1), DeviceArray(self.device, l2), DeviceArray(self.device, ls)
-        fr = DeviceArray(self.device, (n + 1) * FRAGMENT_DTYPE.itemsize)
-        try:
-            n2, l1b, l2b, lsb, rc = self.pairs_bam_device(block_lo, block_hi, r1, r2, bam, fr, stream)
-            _check(rc)
-            assert (n2, l1b, l2b, lsb) == (n, l1, l2, ls)
-            return fr.to_numpy(FRAGMENT_DTYPE, n), r1.to_numpy(np.uint8, l1).tobytes(), r2.to_numpy(np.uint8, l2).tobytes(), bam.to_numpy(np.uint8, ls).tobytes()
-        finally:
-            for d in (r1, r2, bam, fr):
-                d.free()
+        return self._pairs_truth(lib().rsq_sim_pairs_bam, block_lo, block_hi, stream)
 
     def adapter_only_pairs_bam(self, first, n, stream=None):
         """adapter_only_pairs() and the (unmapped) BAM records of the same pairs: (fastq1 bytes, fastq2 bytes, BAM bytes)"""
-        l1, l2, ls = C.c_size_t(), C.c_size_t(), C.c_size_t()
-        rc = lib().rsq_sim_adapter_only_pairs_bam(self.h, first, n, None, 0, C.byref(l1), None, 0, C.byref(l2), None, 0, C.byref(ls), stream)
-        if rc == RSQ_OK:
-            return b"", b"", b""
-        if rc != RSQ_ENOSPC:
-            _check(rc)
-        r1, r2, bam = DeviceArray(self.device, l1.value), DeviceArray(self.device, l2.value), DeviceArray(self.device, ls.value)
-        try:
-            _check(lib().rsq_sim_adapter_only_pairs_bam(self.h, first, n, r1.ptr, r1.nbytes, C.byref(l1), r2.ptr, r2.nbytes, C.byref(l2), bam.ptr, bam.nbytes, C.byref(ls), stream))
-            return r1.to_numpy(np.uint8, l1.value).tobytes(), r2.to_numpy(np.uint8, l2.value).tobytes(), bam.to_numpy(np.uint8, ls.value).tobytes()
-        finally:
-            for d in (r1, r2, bam):
-                d.free()
+        return self._adapter_only_pairs_truth(lib().rsq_sim_adapter_only_pairs_bam, first, n, stream)
 
     def job_generate(self, block_lo, block_hi, batch_blocks=0, stream=None):
         """the rank's share of a job: simulated once, its FASTQ text kept in device memory; returns (pairs, bytes of file 1, bytes of file 2)"""

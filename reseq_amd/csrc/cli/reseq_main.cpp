@@ -22,6 +22,7 @@
 #include <fstream>
 #include <iostream>
 #include <condition_variable>
+#include <deque>
 #include <map>
 #include <mutex>
 #include <thread>
@@ -323,6 +324,24 @@ bool flush_pair(DevBuffer &d1, size_t l1, DevBuffer &d2, size_t l2, AsyncOut &f1
     return f1.good() && f2.good();
 }
 
+// One truth output of illuminaPE (--truthSam: SAM text, plain or .gz; --truthBam: BAM, always BGZF blocks): where every read really came from, written on the
+// device beside the FASTQ text by a call of its own kind
+struct TruthOut {
+    const bool bam;
+    const char *const option;
+    const std::string path;
+    bool gz = false;                                    // the file is gzip members made on the device
+    AsyncOut file;
+    DevBuffer text, packed;                             // a call's records, and their members
+    size_t len = 0;
+    decltype(&rsq_ref_sam_header) header;
+    decltype(&rsq_sim_pairs_sam) pairs;
+    decltype(&rsq_sim_adapter_only_pairs_sam) adapter_only;
+    TruthOut(bool bam_, const std::string &path_)
+        : bam(bam_), option(bam_ ? "--truthBam" : "--truthSam"), path(path_), header(bam_ ? rsq_ref_bam_header : rsq_ref_sam_header), pairs(bam_ ? rsq_sim_pairs_bam : rsq_sim_pairs_sam),
+          adapter_only(bam_ ? rsq_sim_adapter_only_pairs_bam : rsq_sim_adapter_only_pairs_sam) {}
+};
+
 // illuminaPE on several devices inside one process (Simulator::Simulate starts its own worker threads, Simulator.cpp:2830-2836, and hands them blocks, :2384-2401).
 // N host threads, one simulator each on device (worker % devices): every worker prepares, simulates its contiguous share of the blocks with the text kept in device
 // memory (rsq_sim_job_generate), the exclusive scan of the workers' text sizes gives every worker its place in the two files, and all workers write at once
@@ -585,40 +604,35 @@ int illumina_pe(const Args &a) {
         return 1;
     }
     const std::string out1 = a.get("firstReadsOut", "reseq-R1.fq"), out2 = a.get("secondReadsOut", "reseq-R2.fq");      // main.cpp:404,412
-    // --truthSam: where every read really came from, as SAM records written on the device beside the FASTQ text (rsq_sim_pairs_sam); plain or .gz
-    const std::string truth = a.get("truthSam", "");
-    if (a.has("truthSam") && truth.empty()) {
-        ERR("--truthSam needs a file name");
-        return 1;
+    std::deque<TruthOut> truths;                                 // none, one or both; SAM first
+    for (const bool bam : {false, true}) {
+        const char *name = bam ? "truthBam" : "truthSam";
+        if (!a.has(name)) continue;
+        truths.emplace_back(bam, a.get(name, ""));
+        const TruthOut &t = truths.back();
+        if (t.path.empty()) {
+            ERR(t.option << " needs a file name");
+            return 1;
+        }
+        if (!bam && rsq::textio::has_suffix(t.path, ".bz2")) {
+            ERR("--truthSam: bzip2 output is not supported (write .gz or plain SAM)");
+            return 1;
+        }
+        if (!vcf_path.empty()) {
+            ERR(t.option << ": truth alignments are not available for a reference with variants (-V)");
+            return 1;
+        }
+        if (bam && a.has("hostGzip")) {
+            ERR("--truthBam: a BAM file is made of BGZF blocks, which the zlib members of --hostGzip are not (run without --hostGzip)");
+            return 1;
+        }
+        if (bam && truths.size() == 2 && t.path == truths.front().path) {
+            ERR("--truthBam and --truthSam name the same file");
+            return 1;
+        }
     }
-    if (!truth.empty() && rsq::textio::has_suffix(truth, ".bz2")) {
-        ERR("--truthSam: bzip2 output is not supported (write .gz or plain SAM)");
-        return 1;
-    }
-    if (!truth.empty() && !vcf_path.empty()) {
-        ERR("--truthSam: truth alignments are not available for a reference with variants (-V)");
-        return 1;
-    }
-    // --truthBam: the same records as BAM (rsq_sim_pairs_bam): header and records are one byte stream that becomes BGZF blocks on the device, whatever the file's name
-    const std::string truth_bam = a.get("truthBam", "");
-    if (a.has("truthBam") && truth_bam.empty()) {
-        ERR("--truthBam needs a file name");
-        return 1;
-    }
-    if (!truth_bam.empty() && !vcf_path.empty()) {
-        ERR("--truthBam: truth alignments are not available for a reference with variants (-V)");
-        return 1;
-    }
-    if (!truth_bam.empty() && a.has("hostGzip")) {
-        ERR("--truthBam: a BAM file is made of BGZF blocks, which the zlib members of --hostGzip are not (run without --hostGzip)");
-        return 1;
-    }
-    if (!truth_bam.empty() && truth_bam == truth) {
-        ERR("--truthBam and --truthSam name the same file");
-        return 1;
-    }
-    const bool any_truth = !truth.empty() || !truth_bam.empty();
-    const char *truth_option = !truth.empty() ? "--truthSam" : "--truthBam";
+    const bool any_truth = !truths.empty();
+    const char *truth_option = any_truth ? truths.front().option : "";
     rsq_profile *prof = nullptr;
     rsq_ref *ref = nullptr;
     rsq_sim *sim = nullptr;
@@ -721,44 +735,40 @@ int illumina_pe(const Args &a) {
     }
     if (ok && !sys_read.empty()) ok = check(rsq_sim_read_sys_errors(sim, sys_read.c_str()), "Could not read systematic error profile");
     trace.at("prepared");
-    AsyncOut f1, f2, f3, f4;                                     // f3, f4: the truth alignments as SAM and as BAM
+    AsyncOut f1, f2;
     // .gz outputs: the text of every call becomes gzip members on the device (rsq_sim_gzip_device) -- a third of the bytes cross the link and the writer threads
     // only write (--rsqOption host_gzip:1: zlib on host threads behind the writers, as before)
     int64_t host_gzip = 0;
     rsq_get_option("host_gzip", &host_gzip);
     const bool gz1 = !host_gzip && rsq::textio::has_suffix(out1, ".gz"), gz2 = !host_gzip && rsq::textio::has_suffix(out2, ".gz");
-    const bool gz3 = !host_gzip && rsq::textio::has_suffix(truth, ".gz");
-    const bool bam = !truth_bam.empty();
-    if (ok && bam && host_gzip) {                                // (the option set some other way than by --hostGzip)
-        ERR("--truthBam: a BAM file is made of BGZF blocks, which host zlib members are not (run without host_gzip)");
-        ok = false;
+    bool truth_gz = false;
+    for (TruthOut &t : truths) {
+        t.gz = t.bam || (!host_gzip && rsq::textio::has_suffix(t.path, ".gz"));
+        t.text.device = t.packed.device = (int)device;
+        truth_gz = truth_gz || t.gz;
+        if (ok && t.bam && host_gzip) {                          // (the option set some other way than by --hostGzip)
+            ERR("--truthBam: a BAM file is made of BGZF blocks, which host zlib members are not (run without host_gzip)");
+            ok = false;
+        }
     }
     // one Huffman code for the run: the first batch's sample (FASTQ text alone: SAM text is another kind, its calls take their own code)
-    if (ok && (gz1 || gz2) && !gz3 && !bam) rsq_sim_gzip_keep_code(sim, 1);
-    {                                                            // files of device-made members (BGZF blocks) end with BGZF's end-of-file member
-        char eof[32];
-        const size_t n = rsq_gzip_eof_member(eof, sizeof eof);
-        if (gz1) f1.tail.assign(eof, n);
-        if (gz2) f2.tail.assign(eof, n);
-        if (gz3) f3.tail.assign(eof, n);
-    }
+    if (ok && (gz1 || gz2) && !truth_gz) rsq_sim_gzip_keep_code(sim, 1);
+    char eof[32];                                                // files of device-made members (BGZF blocks) end with BGZF's end-of-file member
+    const size_t eof_len = rsq_gzip_eof_member(eof, sizeof eof);
+    if (gz1) f1.tail.assign(eof, eof_len);
+    if (gz2) f2.tail.assign(eof, eof_len);
     if (ok) {
         const bool o1 = f1.open(out1, gz1), o2 = f2.open(out2, gz2);
         if (!o1 || !o2) {
             ERR("Could not open '" << (o1 ? out2 : out1) << "' for writing.");
             ok = false;
         }
-        if (ok && !truth.empty() && !f3.open(truth, gz3)) {
-            ERR("Could not open '" << truth << "' for writing.");
-            ok = false;
-        }
-        if (ok && bam && !f4.open(truth_bam, true)) {
-            ERR("Could not open '" << truth_bam << "' for writing.");
-            ok = false;
-        }
-        if (ok && bam) {                                         // (behind a successful open: a file that was never opened must not send its tail to stdout)
-            char eof[32];
-            f4.tail.assign(eof, rsq_gzip_eof_member(eof, sizeof eof));
+        for (TruthOut &t : truths) {
+            if (!ok) break;
+            if (!t.file.open(t.path, t.gz)) {
+                ERR("Could not open '" << t.path << "' for writing.");
+                ok = false;
+            } else if (t.gz) t.file.tail.assign(eof, eof_len);  // (behind a successful open: a file that was never opened must not send its tail to stdout)
         }
     }
     if (ok) {
@@ -766,8 +776,8 @@ int illumina_pe(const Args &a) {
         rsq_sim_get_info(sim, &info);
         INFO("Aiming for " << info.total_pairs + info.adapter_only_pairs << " read pairs");
         INFO("Starting read generation");
-        DevBuffer d1, d2, g1, g2, d3, g3, d4, g4;
-        d1.device = d2.device = g1.device = g2.device = d3.device = g3.device = d4.device = g4.device = (int)device;
+        DevBuffer d1, d2, g1, g2;
+        d1.device = d2.device = g1.device = g2.device = (int)device;
         uint64_t written = 0;
         // a call's text of one file as members in `g`: true and the members' size, or false
         auto members = [&](bool gz, DevBuffer &d, size_t &len, DevBuffer &g) {
@@ -779,29 +789,41 @@ int illumina_pe(const Args &a) {
             len = packed;
             return check(rc, "Compressing the output failed");
         };
-        const bool sam = !truth.empty();
-        if (ok && sam) {                                         // the header, through the same route as the records
-            size_t need = 0, l3 = 0;
-            rsq_ref_sam_header(ref, nullptr, 0, &need);
+        auto push_truth = [&](TruthOut &t) { return members(t.gz, t.text, t.len, t.packed) && t.file.push(t.gz ? t.packed : t.text, t.len); };
+        for (TruthOut &t : truths) {                             // the header, through the same route as the records (BAM: the first bytes of the stream they continue)
+            if (!ok) break;
+            size_t need = 0;
+            t.header(ref, nullptr, 0, &need);
             std::string header(need, '\0');
-            ok = check(rsq_ref_sam_header(ref, &header[0], need, &need), "SAM header") && d3.ensure(need + 4096) &&
-                 check(rsq_dev_upload((int)device, d3.p, header.data(), need), "upload");
-            l3 = need;
-            ok = ok && members(gz3, d3, l3, g3) && f3.push(gz3 ? g3 : d3, l3);
+            ok = check(t.header(ref, &header[0], need, &need), t.bam ? "BAM header" : "SAM header") && t.text.ensure(need + 4096) &&
+                 check(rsq_dev_upload((int)device, t.text.p, header.data(), need), "upload");
+            t.len = need;
+            ok = ok && push_truth(t);
         }
-        if (ok && bam) {                                         // the BAM header: the first bytes of the stream the records continue
-            size_t need = 0, l4 = 0;
-            rsq_ref_bam_header(ref, nullptr, 0, &need);
-            std::string header(need, '\0');
-            ok = check(rsq_ref_bam_header(ref, &header[0], need, &need), "BAM header") && d4.ensure(need + 4096) && check(rsq_dev_upload((int)device, d4.p, header.data(), need), "upload");
-            l4 = need;
-            ok = ok && members(true, d4, l4, g4) && f4.push(g4, l4);
-        }
-        // a call per output kind: with both --truthSam and --truthBam a batch is simulated once for each (the calls write the same FASTQ text into the same buffers)
-        auto both = [](int rc_sam, int rc_bam) {
-            if (rc_sam != RSQ_OK && rc_sam != RSQ_ENOSPC) return rc_sam;
-            if (rc_bam != RSQ_OK && rc_bam != RSQ_ENOSPC) return rc_bam;
-            return rc_sam == RSQ_ENOSPC || rc_bam == RSQ_ENOSPC ? (int)RSQ_ENOSPC : (int)RSQ_OK;
+        // One batch.  Without a truth output the plain call; else a call per output, SAM first (with both a batch is simulated once for each: the calls write the
+        // same FASTQ text into the same buffers): a hard error ends the batch, RSQ_ENOSPC from either lets the other state its size too, then all buffers grow
+        // and the calls repeat.  n: the batch's pairs, as the calls state them.
+        size_t l1 = 0, l2 = 0;
+        auto batch = [&](auto &&plain, auto &&with_truth, bool spare, const char *failed, const uint64_t &n) {
+            auto calls = [&] {
+                if (truths.empty()) return (int)plain();
+                int rc = RSQ_OK;
+                for (TruthOut &t : truths) {
+                    const int one = with_truth(t);
+                    if (one != RSQ_OK && one != RSQ_ENOSPC) return one;
+                    if (one == RSQ_ENOSPC) rc = RSQ_ENOSPC;
+                }
+                return rc;
+            };
+            auto grown = [&](size_t len) { return len + (spare ? len / 8 : 0) + 4096; };
+            int rc = calls();
+            if (rc == RSQ_ENOSPC) {
+                ok = d1.ensure(grown(l1)) && d2.ensure(grown(l2));
+                for (TruthOut &t : truths) ok = ok && t.text.ensure(grown(t.len));
+                if (ok) rc = calls();
+            }
+            ok = ok && check(rc, failed) && (n == 0 || (members(gz1, d1, l1, g1) && members(gz2, d2, l2, g2) && flush_pair(gz1 ? g1 : d1, l1, gz2 ? g2 : d2, l2, f1, f2)));
+            for (TruthOut &t : truths) ok = ok && (n == 0 || push_truth(t));
         };
         // about 12 M pairs per call: large launches keep the persistent read kernel's tail short (one call of 14.5 M pairs runs at 179 M pairs/s, calls of 2.4 M at
         // 154 M), and sparse coverage needs long block ranges
@@ -809,55 +831,27 @@ int illumina_pe(const Args &a) {
         const uint32_t step = (uint32_t)std::min(400000.0, std::max(2000.0, 12e6 / std::max(1e-9, pairs_per_block)));
         for (uint32_t lo = 1; ok && lo <= info.total_blocks; lo += step) {
             const uint32_t hi = std::min(info.total_blocks + 1, lo + step);
-            size_t l1 = 0, l2 = 0;
             uint64_t n = 0;
-            size_t l3 = 0, l4 = 0;
-            auto call = [&] {
-                const int rc = sam   ? rsq_sim_pairs_sam(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)d3.p, d3.cap, &l3, &n, nullptr, 0, nullptr)
-                               : bam ? (int)RSQ_OK
-                                     : rsq_sim_pairs(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, &n, nullptr, 0, nullptr);
-                if (!bam || (rc != RSQ_OK && rc != RSQ_ENOSPC)) return rc;
-                return both(rc, rsq_sim_pairs_bam(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)d4.p, d4.cap, &l4, &n, nullptr, 0, nullptr));
-            };
-            int rc = call();
-            if (rc == RSQ_ENOSPC) {
-                ok = d1.ensure(l1 + l1 / 8 + 4096) && d2.ensure(l2 + l2 / 8 + 4096) && (!sam || d3.ensure(l3 + l3 / 8 + 4096)) && (!bam || d4.ensure(l4 + l4 / 8 + 4096));
-                if (ok) rc = call();
-            }
-            ok = ok && check(rc, "Simulation failed") && (n == 0 || (members(gz1, d1, l1, g1) && members(gz2, d2, l2, g2) && flush_pair(gz1 ? g1 : d1, l1, gz2 ? g2 : d2, l2, f1, f2)));
-            ok = ok && (!sam || n == 0 || (members(gz3, d3, l3, g3) && f3.push(gz3 ? g3 : d3, l3)));
-            ok = ok && (!bam || n == 0 || (members(true, d4, l4, g4) && f4.push(g4, l4)));
+            batch([&] { return rsq_sim_pairs(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, &n, nullptr, 0, nullptr); },
+                  [&](TruthOut &t) { return t.pairs(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)t.text.p, t.text.cap, &t.len, &n, nullptr, 0, nullptr); }, true,
+                  "Simulation failed", n);
             written += n;
             if (ok && n) INFO("Generated " << written << " read pairs (" << (info.total_pairs ? (written * 100 + info.total_pairs / 2) / info.total_pairs : 0) << "%).");
         }
         for (uint64_t first = 0; ok && first < info.adapter_only_pairs; first += 100000) {       // Simulator.cpp:2359-2382
             const uint64_t n = std::min<uint64_t>(100000, info.adapter_only_pairs - first);
-            size_t l1 = 0, l2 = 0;
-            size_t l3 = 0, l4 = 0;
-            auto call = [&] {
-                const int rc = sam   ? rsq_sim_adapter_only_pairs_sam(sim, first, n, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)d3.p, d3.cap, &l3, nullptr)
-                               : bam ? (int)RSQ_OK
-                                     : rsq_sim_adapter_only_pairs(sim, first, n, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, nullptr);
-                if (!bam || (rc != RSQ_OK && rc != RSQ_ENOSPC)) return rc;
-                return both(rc, rsq_sim_adapter_only_pairs_bam(sim, first, n, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)d4.p, d4.cap, &l4, nullptr));
-            };
-            int rc = call();
-            if (rc == RSQ_ENOSPC) {
-                ok = d1.ensure(l1 + 4096) && d2.ensure(l2 + 4096) && (!sam || d3.ensure(l3 + 4096)) && (!bam || d4.ensure(l4 + 4096));
-                if (ok) rc = call();
-            }
-            ok = ok && check(rc, "Simulation of adapter-only pairs failed") && members(gz1, d1, l1, g1) && members(gz2, d2, l2, g2) && flush_pair(gz1 ? g1 : d1, l1, gz2 ? g2 : d2, l2, f1, f2);
-            ok = ok && (!sam || (members(gz3, d3, l3, g3) && f3.push(gz3 ? g3 : d3, l3)));
-            ok = ok && (!bam || (members(true, d4, l4, g4) && f4.push(g4, l4)));
+            batch([&] { return rsq_sim_adapter_only_pairs(sim, first, n, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, nullptr); },
+                  [&](TruthOut &t) { return t.adapter_only(sim, first, n, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)t.text.p, t.text.cap, &t.len, nullptr); }, false,
+                  "Simulation of adapter-only pairs failed", n);
         }
     }
     trace.at("last text handed to the writers");
     f1.close();
     f2.close();
-    f3.close();
-    f4.close();
+    for (TruthOut &t : truths) t.file.close();
     trace.at("files closed");
-    ok = ok && f1.good() && f2.good() && f3.good() && f4.good();
+    ok = ok && f1.good() && f2.good();
+    for (TruthOut &t : truths) ok = ok && t.file.good();
     rsq_sim_free(sim);
     rsq_ref_free(ref);
     rsq_profile_free(prof);
@@ -866,8 +860,7 @@ int illumina_pe(const Args &a) {
         ERR("An error occurred in the process: Terminating simulation");
         remove(out1.c_str());
         remove(out2.c_str());
-        if (!truth.empty()) remove(truth.c_str());
-        if (!truth_bam.empty()) remove(truth_bam.c_str());
+        for (const TruthOut &t : truths) remove(t.path.c_str());
         return 1;
     }
     INFO("Simulation finished succesfully");

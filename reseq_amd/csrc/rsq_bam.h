@@ -13,20 +13,19 @@
 //
 // bam_seq is the part with a shape of its own: a row word holds four base codes, one byte each; one byte permute turns them into four nibbles (the table of the
 // forward or of the complemented codes), a shift-or puts neighbouring nibbles into one byte, and a second permute gathers the four bytes of two row words into one
-// output word.  The reversed line takes the row from its last word down through the byte funnel of sam_line (a read length that is no multiple of four takes every
-// word from two neighbours), so the words arrive in OUTPUT order and the pairing of nibbles is always (0, 1), (2, 3), ... of the output, whatever read_len & 1:
-// an odd length leaves the last low nibble 0 in either orientation.
+// output word.  The words come from sam_line's row walk (RowRound, rsq_sam.h) in OUTPUT order, so the pairing of nibbles is always (0, 1), (2, 3), ... of the
+// output, whatever read_len & 1: an odd length leaves the last low nibble 0 in either orientation.
 //
-// Per lane, host and device (tests/hostemu/bam_trial.cpp runs them on the CPU): bam_record_size, bam_fixed, bam_cigar, bam_seq, bam_qual, bam_tags, bam_record.
-// Kernels: k_bam_sizes (one lane per raw row pair: both mates' walks, CIGAR element counts and name lengths into a side array of its own, the pair's bytes),
-// k_bam_write (one wave per 16 pairs, four lanes a pair, through the wave's LDS image: WaveImage and ImageSink of rsq_format.h -- records are not word-aligned,
-// the frame handles that as it does for text).  Not part of what hiprtc compiles for a profile (rsq_spec.h): nothing of the read kernel's text includes this file.
+// Per lane, host and device (tests/hostemu/truth_trial.h runs them on the CPU): bam_record_size, bam_fixed, bam_cigar, bam_seq, bam_qual, bam_tags, bam_record, bam_mate.
+// BamFormat makes them a format of rsq_sam.h: its kernels (k_truth_sizes, k_truth_write), frame and fallback are that file's, with a side array of BAM's own --
+// records are not word-aligned, the frame handles that as it does for text.  Not part of what hiprtc compiles for a profile (rsq_spec.h): nothing of the read
+// kernel's text includes this file.
 #pragma once
 #include "rsq_sam.h"
 
 namespace rsq {
 
-// a mate's walk and what its BAM record needs beside it (k_bam_sizes keeps them so that the writer neither walks the ops nor counts again)
+// a mate's walk and what its BAM record needs beside it (k_truth_sizes keeps them so that the writer neither walks the ops nor counts again)
 struct BamMate {
     SamMate w;                 // w.bytes: of the mate's BAM record, its block_size field included
     uint16_t n_cigar;          // elements of the CIGAR (0: unmapped, or "*")
@@ -123,28 +122,21 @@ RSQ_HD uint32_t bam_pack(uint32_t n0, uint32_t n1) {
     return (x0 & 0xFFu) | ((x0 >> 8) & 0xFF00u) | ((x1 & 0xFFu) << 16) | ((x1 << 8) & 0xFF000000u);
 #endif
 }
-// SEQ: the row's words in output order (sam_line's walk: as they lie, or from the last one down, funnelled and byte-reversed), two of them an output word.  What
-// lies behind the row's last code becomes nibble 0.
+// SEQ: the row's words in output order (sam_line's walk), two of them an output word.  What lies behind the row's last code becomes nibble 0.
 template <class Sink>
 RSQ_HD void bam_seq(const WordColumn &row, uint32_t read_len, bool reverse, Sink &t) {
-    const uint32_t words = (read_len + 3u) >> 2, odd = read_len & 3u;
-    constexpr uint32_t kAhead = 10u;                                     // loads in flight (even: an output word never spans two rounds)
-    for (uint32_t i = 0; i < words; i += kAhead) {
-        uint32_t w[kAhead + 1u], nib[kAhead];
+    static_assert(kRowAhead % 2u == 0u, "an output word never spans two rounds");
+    const uint32_t words = (read_len + 3u) >> 2;
+    for (uint32_t i = 0; i < words; i += kRowAhead) {
+        const RowRound round(row, read_len, reverse, i);
+        uint32_t nib[kRowAhead];
 #pragma unroll
-        for (uint32_t k = 0; k <= kAhead; ++k) {
-            const uint32_t j = i + k;                                    // code word j reads row word j, or (reverse) words - 1 - j and the one below it
-            w[k] = j < words && (k < kAhead || (reverse && odd)) ? row.at(reverse ? words - 1u - j : j) : 0u;
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < kAhead; ++k) {
-            uint32_t v = w[k];
-            if (reverse) v = sam_byte_reverse(odd ? sam_funnel(w[k], w[k + 1u], odd) : v);
+        for (uint32_t k = 0; k < kRowAhead; ++k) {
             const uint32_t at = 4u * (i + k), left = at < read_len ? read_len - at : 0u;
-            nib[k] = bam_nibbles(v, reverse) & (left >= 4u ? 0xFFFFFFFFu : (1u << (8u * left)) - 1u);
+            nib[k] = bam_nibbles(round.at(k), reverse) & (left >= 4u ? 0xFFFFFFFFu : (1u << (8u * left)) - 1u);
         }
 #pragma unroll
-        for (uint32_t k = 0; k < kAhead; k += 2u) {
+        for (uint32_t k = 0; k < kRowAhead; k += 2u) {
             if (i + k >= words) break;
             const uint32_t left = read_len - 4u * (i + k);
             t.bytes(bam_pack(nib[k], nib[k + 1u]), left >= 8u ? 4u : (left + 1u) >> 1);
@@ -195,74 +187,33 @@ RSQ_HD BamMate bam_mate(const DevSim &S, const NameTable &names, bool has_f, con
     return b;
 }
 
-#if RSQ_DEVICE_BUILD
-// One lane per raw row pair, as k_sam_sizes: both mates' entries into side[row], the pair's bytes into sizes[pair]
-__global__ void __launch_bounds__(256) k_bam_sizes(DevSim S, NameTable names, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_only_first, RawLayout raw, const uint32_t *perm,
-                                                   BamPair *side, uint32_t *sizes) {
-    const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= n_pairs) return;
-    const uint64_t pair = perm ? perm[row] : row;
-    Fragment f{};
-    if (frags) f = frags[pair];
-    const bool has_f = frags != nullptr;
-    const ReadMeta m0 = raw.meta[row], m1 = raw.meta[n_pairs + row];
-    const WordColumn ops0 = raw.ops_of(row), ops1 = raw.ops_of(n_pairs + row);
-    const SamMate w0 = sam_walk(ops0, m0), w1 = sam_walk(ops1, m1);
-    const uint64_t ao_number = adapter_only_first + pair + 1u;
-    BamPair p;
-    p.mate[0] = bam_mate(S, names, has_f, f, ao_number, m0, ops0, w0, sam_align(has_f, f, 0u, w0, w1));
-    p.mate[1] = bam_mate(S, names, has_f, f, ao_number, m1, ops1, w1, sam_align(has_f, f, 1u, w0, w1));
-    side[row] = p;
-    sizes[pair] = p.mate[0].w.bytes + p.mate[1].w.bytes;
-}
 
-// One wave per 16 consecutive raw rows = 16 pairs, four lanes a pair, through the wave's image, with k_sam_write's frame, capacity checks and fallback: lanes 0-15
-// write mate 0's record up to and with its packed SEQ, lanes 16-31 its QUAL and tags, lanes 32-47 and 48-63 the same of mate 1.  Nothing is written when any of
-// the call's three outputs exceeds its capacity so far.
-template <bool PERM>
-__global__ void __launch_bounds__(64) k_bam_write(DevSim S, NameTable names, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_only_first, RawLayout raw, const BamPair *side,
-                                                 const uint64_t *offsets, char *dst, uint64_t cap, const uint64_t *fastq_end0, const uint64_t *fastq_end1, uint64_t fastq_cap0,
-                                                 uint64_t fastq_cap1, const uint32_t *perm, uint32_t lds_bytes) {
-    extern __shared__ __attribute__((aligned(16))) char s_bam[];
-    using Image = WaveImage<PERM, kSamPairs>;
-    const uint32_t lane = threadIdx.x, part = lane / kSamPairs, seg = part >> 1, half = part & 1u;
-    if (Image::first() >= n_pairs) return;
-    if (offsets[n_pairs] > cap || *fastq_end0 > fastq_cap0 || *fastq_end1 > fastq_cap1) return;      // a buffer of the call is too small: write nothing (RSQ_ENOSPC)
-    const Image im(offsets, n_pairs, dst, lds_bytes, perm, lane);
-    const uint64_t pair = im.item;
-    ReadMeta m{};
-    Fragment f{};
-    BamPair p{};
-    uint64_t r = 0;
-    if (im.active) {
-        r = (uint64_t)seg * n_pairs + im.row;
-        m = raw.meta[r];
-        p = side[im.row];
-        if (frags) f = frags[pair];
+// BAM records as a format (rsq_sam.h states what a format is)
+struct BamFormat {
+    using Mate = BamMate;
+    using Pair = BamPair;
+    static RSQ_HD const SamMate &walk(const Mate &e) { return e.w; }
+    static RSQ_HD uint32_t bytes(const Mate &e) { return e.w.bytes; }
+    static RSQ_HD Mate mate(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &ops, const SamMate &w,
+                            const SamAlign &a) {
+        return bam_mate(S, names, has_f, f, adapter_only_number, m, ops, w, a);
     }
-    const bool has_f = frags != nullptr;
-    const WordColumn seq = raw.seq_of(r), qual = raw.qual_of(r), ops = raw.ops_of(r);
-    const uint64_t ao_number = adapter_only_first + pair + 1u;
-    const BamMate b = seg ? p.mate[1] : p.mate[0];
-    const SamAlign a = sam_align(has_f, f, seg, p.mate[0].w, p.mate[1].w);
-    const uint32_t rec_at = seg ? p.mate[0].w.bytes : 0u;              // of the record within its pair's bytes
-    if (!im.through_lds) {
-        if (im.active && half == 0u) bam_record(S, names, has_f, f, ao_number, m, seq, qual, ops, b, a, dst + offsets[pair] + rec_at);
-        return;
+    template <class Sink>
+    static RSQ_HD void head(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &seq,
+                            const WordColumn &ops, const Mate &e, const SamAlign &a, Sink &t) {
+        bam_head(S, names, has_f, f, adapter_only_number, m, seq, ops, e, a, t);
     }
-    im.clear(s_bam, lds_bytes);
-    if (im.active) {
-        const uint32_t qual_at = b.w.bytes - bam_tags_size(m) - m.read_len;
-        ImageSink t(im.item_text(s_bam) + rec_at + (half ? qual_at : 0u));
-        if (half == 0u) bam_head(S, names, has_f, f, ao_number, m, seq, ops, b, a, t);
-        else {
-            bam_qual(qual, m.read_len, a.reverse != 0u, S.phred_offset, t);
-            bam_tags(m, ops, t);
-        }
-        t.finish();
+    template <class Sink>
+    static RSQ_HD void tail(const DevSim &S, const ReadMeta &m, const WordColumn &qual, const WordColumn &ops, const SamAlign &a, Sink &t) {
+        bam_qual(qual, m.read_len, a.reverse != 0u, S.phred_offset, t);
+        bam_tags(m, ops, t);
     }
-    im.store_out(s_bam);
-}
-#endif
+    static RSQ_HD uint32_t tail_at(const Mate &e, const ReadMeta &m) { return e.w.bytes - bam_tags_size(m) - m.read_len; }
+    template <class P>
+    static RSQ_HD uint32_t record(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &seq,
+                                  const WordColumn &qual, const WordColumn &ops, const Mate &e, const SamAlign &a, P dst) {
+        return bam_record(S, names, has_f, f, adapter_only_number, m, seq, qual, ops, e, a, dst);
+    }
+};
 
 }  // namespace rsq

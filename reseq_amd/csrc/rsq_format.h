@@ -447,7 +447,7 @@ __global__ void __launch_bounds__(256) k_variant_templates(DevSim S, const Fragm
     variant_template(S, frags[pair], fvars[pair], seg, raw.templates + r * raw.template_words, raw.template_words);
 }
 
-// Text through an LDS image: the frame of the kernels that write text (k_format_write and k_record_text_waves below, k_sam_write in rsq_sam.h).  One wave
+// Text through an LDS image: the frame of the kernels that write text (k_format_write and k_record_text_waves below, k_truth_write in rsq_sam.h).  One wave
 // takes ITEMS consecutive raw rows, 64 / ITEMS lanes an item (lane & (ITEMS - 1) is the item, lane / ITEMS the lane's part of it).  The items' texts occupy one
 // contiguous byte range of the output, so the wave formats them into an LDS image of that range (laid out with the same alignment modulo 16 as the destination)
 // and then copies the image out with aligned 16-byte stores, all lanes over the range.  PERM (the read kernel ran binned by tile): the wave's items are those

@@ -10,16 +10,20 @@
 // reference's left end moves POS).  A forward mate (segment == strand) covers [start, start + t), a reverse mate [end - t, end): its CIGAR is replayed from the
 // last op down, its bases are the reverse complement, its qualities reversed.  Adapter-only pairs are unmapped (flags 77 / 141).
 //
-// Per lane, host and device (tests/hostemu/sam_trial.cpp runs them on the CPU): sam_walk, sam_align, sam_cigar, sam_line, sam_record_size, sam_record.
-// Kernels: k_sam_sizes (one lane per pair: both mates' walks into a side array, the pair's bytes), k_sam_write (one wave per 16 pairs, four lanes a pair, through
-// the wave's LDS image, WaveImage in rsq_format.h).  Not part of what hiprtc compiles for a profile (rsq_spec.h): nothing of the read
-// kernel's text includes this file.
+// Per lane, host and device (tests/hostemu/truth_trial.h runs them on the CPU): sam_walk, sam_align, sam_cigar, RowRound, sam_line, sam_record_size, sam_record.
+//
+// A truth-record FORMAT is a type of static members (SamFormat below, BamFormat in rsq_bam.h): the side array's entry per mate (Mate; Pair holds a row's two,
+// one load), walk(entry) and bytes(entry), mate(...) -- the entry from a walk and an alignment --, head(..., sink) -- everything in front of QUAL --,
+// tail(..., sink) -- QUAL and the tags --, tail_at(entry, meta), the offset at which the tail begins, and record(..., dst), the whole record through one sink
+// (sam_record, bam_record: the straight-to-HBM fallback).  Everything that is not a record's bytes is written once over a format: the kernels k_truth_sizes<Format> (one lane per pair: both
+// mates' entries into the side array, the pair's bytes) and k_truth_write<Format, PERM> (one wave per 16 pairs, four lanes a pair, through the wave's LDS image,
+// WaveImage in rsq_format.h).  Not part of what hiprtc compiles for a profile (rsq_spec.h): nothing of the read kernel's text includes this file.
 #pragma once
 #include "rsq_format.h"
 
 namespace rsq {
 
-// what the ops of one mate's template part come to (k_sam_sizes keeps it so that the writer does not walk them again)
+// what the ops of one mate's template part come to (k_truth_sizes keeps it so that the writer does not walk them again)
 struct SamMate {
     uint16_t q, t;             // read bases (M + I) and template bases (M + D) of the template part
     uint16_t lead, trail;      // D iterations at its first and last end in READ order: dropped from the CIGAR
@@ -258,23 +262,31 @@ RSQ_HD uint32_t sam_funnel(uint32_t hi, uint32_t lo, uint32_t bytes) {   // (hi:
     return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8u * bytes));
 #endif
 }
+// A round of up to kRowAhead of a row's words, loaded together and handed out oriented for output: at(k) is output word i + k -- row word i + k, or (reverse) the
+// row from its last word down, funnelled over two neighbours when read_len & 3, byte-reversed.  Words behind the row's last are 0.
+constexpr uint32_t kRowAhead = 10u;                                      // loads in flight (even: bam_seq pairs the words of a round)
+struct RowRound {
+    uint32_t w[kRowAhead + 1u], odd;
+    bool reverse;
+    RSQ_HD RowRound(const WordColumn &row, uint32_t read_len, bool reverse_, uint32_t i) : odd(read_len & 3u), reverse(reverse_) {
+        const uint32_t words = (read_len + 3u) >> 2;
+        uint64_t at = (uint64_t)(reverse ? words - 1u - i : i) * row.pitch;      // output word j reads row word j, or (reverse) words - 1 - j and the one below it:
+        const uint64_t step = reverse ? 0u - row.pitch : row.pitch;              // a step of the pitch up or down (modulo 2^64) in place of a product per load
+#pragma unroll
+        for (uint32_t k = 0; k <= kRowAhead; ++k, at += step) w[k] = i + k < words && (k < kRowAhead || (reverse && odd)) ? row.p[at] : 0u;
+    }
+    RSQ_HD uint32_t at(uint32_t k) const { return reverse ? sam_byte_reverse(odd ? sam_funnel(w[k], w[k + 1u], odd) : w[k]) : w[k]; }
+};
 template <class Sink>
 RSQ_HD void sam_line(const WordColumn &row, uint32_t read_len, bool is_qual, bool reverse, uint32_t phred_offset, Sink &t) {
-    const uint32_t words = (read_len + 3u) >> 2, odd = read_len & 3u;
+    const uint32_t words = (read_len + 3u) >> 2;
     const uint32_t shift = ((phred_offset - 33u) & 0xFFu) * 0x01010101u;      // one packed subtract: no character is below the offset, so no byte borrows from a character
-    constexpr uint32_t kAhead = 10u;                                     // loads in flight
-    for (uint32_t i = 0; i < words; i += kAhead) {
-        uint32_t w[kAhead + 1u];
+    for (uint32_t i = 0; i < words; i += kRowAhead) {
+        const RowRound round(row, read_len, reverse, i);
 #pragma unroll
-        for (uint32_t k = 0; k <= kAhead; ++k) {
-            const uint32_t j = i + k;                                    // output word j reads row word j, or (reverse) words - 1 - j and the one below it
-            w[k] = j < words && (k < kAhead || (reverse && odd)) ? row.at(reverse ? words - 1u - j : j) : 0u;
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < kAhead; ++k) {
+        for (uint32_t k = 0; k < kRowAhead; ++k) {
             if (i + k >= words) break;
-            uint32_t v = w[k];
-            if (reverse) v = sam_byte_reverse(odd ? sam_funnel(w[k], w[k + 1u], odd) : v);
+            const uint32_t v = round.at(k);
             const uint32_t text = is_qual ? v - shift : reverse ? sam_complement_letters(v) : base_letters(v), left = read_len - 4u * (i + k);
             t.bytes(text, left < 4u ? left : 4u);
         }
@@ -310,40 +322,75 @@ RSQ_HD uint32_t sam_record(const DevSim &S, const NameTable &names, bool has_f, 
     return t.n;
 }
 
+// SAM text as a format (the header comment states what a format is); an entry is the walk itself, with the record's bytes
+struct SamFormat {
+    using Mate = SamMate;
+    using Pair = SamPair;
+    static RSQ_HD const SamMate &walk(const Mate &e) { return e; }
+    static RSQ_HD uint32_t bytes(const Mate &e) { return e.bytes; }
+    static RSQ_HD Mate mate(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &, const SamMate &w,
+                            const SamAlign &a) {
+        Mate e = w;
+        e.bytes = sam_record_size(S, names, has_f, f, adapter_only_number, m, w, a);
+        return e;
+    }
+    template <class Sink>
+    static RSQ_HD void head(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &seq,
+                            const WordColumn &ops, const Mate &e, const SamAlign &a, Sink &t) {
+        sam_head(S, names, has_f, f, adapter_only_number, m, ops, e, a, t);
+        sam_line(seq, m.read_len, false, a.reverse != 0u, S.phred_offset, t);
+        t.ch('\t');
+    }
+    template <class Sink>
+    static RSQ_HD void tail(const DevSim &S, const ReadMeta &m, const WordColumn &qual, const WordColumn &ops, const SamAlign &a, Sink &t) {
+        sam_line(qual, m.read_len, true, a.reverse != 0u, S.phred_offset, t);
+        sam_tags(m, ops, t);
+    }
+    static RSQ_HD uint32_t tail_at(const Mate &e, const ReadMeta &m) { return e.bytes - sam_tags_size(m) - m.read_len; }
+    template <class P>
+    static RSQ_HD uint32_t record(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &seq,
+                                  const WordColumn &qual, const WordColumn &ops, const Mate &e, const SamAlign &a, P dst) {
+        return sam_record(S, names, has_f, f, adapter_only_number, m, seq, qual, ops, e, a, dst);
+    }
+};
+
 #if RSQ_DEVICE_BUILD
-// One lane per raw row pair (row i of both segments: the two mates of pair perm[i], or of pair i): the walks into side[row], the pair's bytes into sizes[pair]
-__global__ void __launch_bounds__(256) k_sam_sizes(DevSim S, NameTable names, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_only_first, RawLayout raw, const uint32_t *perm,
-                                                   SamPair *side, uint32_t *sizes) {
+// One lane per raw row pair (row i of both segments: the two mates of pair perm[i], or of pair i): both mates' entries into side[row], the pair's bytes into
+// sizes[pair]
+template <class Format>
+__global__ void __launch_bounds__(256) k_truth_sizes(DevSim S, NameTable names, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_only_first, RawLayout raw, const uint32_t *perm,
+                                                     typename Format::Pair *side, uint32_t *sizes) {
     const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= n_pairs) return;
     const uint64_t pair = perm ? perm[row] : row;
     Fragment f{};
     if (frags) f = frags[pair];
+    const bool has_f = frags != nullptr;
     const ReadMeta m0 = raw.meta[row], m1 = raw.meta[n_pairs + row];
-    SamPair p;
-    p.mate[0] = sam_walk(raw.ops_of(row), m0);
-    p.mate[1] = sam_walk(raw.ops_of(n_pairs + row), m1);
+    const WordColumn ops0 = raw.ops_of(row), ops1 = raw.ops_of(n_pairs + row);
+    const SamMate w0 = sam_walk(ops0, m0), w1 = sam_walk(ops1, m1);
     const uint64_t ao_number = adapter_only_first + pair + 1u;
-    p.mate[0].bytes = sam_record_size(S, names, frags != nullptr, f, ao_number, m0, p.mate[0], sam_align(frags != nullptr, f, 0u, p.mate[0], p.mate[1]));
-    p.mate[1].bytes = sam_record_size(S, names, frags != nullptr, f, ao_number, m1, p.mate[1], sam_align(frags != nullptr, f, 1u, p.mate[0], p.mate[1]));
+    typename Format::Pair p;
+    p.mate[0] = Format::mate(S, names, has_f, f, ao_number, m0, ops0, w0, sam_align(has_f, f, 0u, w0, w1));
+    p.mate[1] = Format::mate(S, names, has_f, f, ao_number, m1, ops1, w1, sam_align(has_f, f, 1u, w0, w1));
     side[row] = p;
-    sizes[pair] = p.mate[0].bytes + p.mate[1].bytes;
+    sizes[pair] = Format::bytes(p.mate[0]) + Format::bytes(p.mate[1]);
 }
 
 // One wave per 16 consecutive raw rows = 16 pairs, four lanes a pair, through the wave's image (WaveImage, rsq_format.h; the wave's 32 records are one
-// contiguous byte range of the output, PERM: a slot per pair): lanes 0-15 write mate 0's record up to and with the tab behind SEQ, lanes 16-31 its QUAL and
-// tags, lanes 32-47 and 48-63 the same of mate 1.  Nothing is written when any of the call's three texts exceeds its capacity so far (fastq_end: the FASTQ
-// offsets' last entries).
+// contiguous byte range of the output, PERM: a slot per pair): lanes 0-15 write the head of mate 0's record (everything in front of QUAL), lanes 16-31 its tail
+// (QUAL and the tags), lanes 32-47 and 48-63 the same of mate 1.  Nothing is written when any of the call's three outputs exceeds its capacity so far
+// (fastq_end: the FASTQ offsets' last entries).  A wave whose records do not fit the image writes them straight to dst, a lane a record (Format::record).
 constexpr uint32_t kSamPairs = 16, kSamLdsMax = 32u * 1024u, kSamLdsMin = 2048u;
 RSQ_HD uint32_t sam_lds_bytes(uint64_t pair_bytes, bool slots) {        // the image for pairs of at most pair_bytes; slots: each its own alignment
     const uint64_t want = (kSamPairs * (pair_bytes + (slots ? 16u : 0u)) + 16u + 127u) & ~(uint64_t)127u;
     return (uint32_t)(want < kSamLdsMin ? kSamLdsMin : want > kSamLdsMax ? kSamLdsMax : want);
 }
-template <bool PERM>
-__global__ void __launch_bounds__(64) k_sam_write(DevSim S, NameTable names, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_only_first, RawLayout raw, const SamPair *side,
-                                                 const uint64_t *offsets, char *dst, uint64_t cap, const uint64_t *fastq_end0, const uint64_t *fastq_end1, uint64_t fastq_cap0,
-                                                 uint64_t fastq_cap1, const uint32_t *perm, uint32_t lds_bytes) {
-    extern __shared__ __attribute__((aligned(16))) char s_sam[];
+template <class Format, bool PERM>
+__global__ void __launch_bounds__(64) k_truth_write(DevSim S, NameTable names, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_only_first, RawLayout raw,
+                                                   const typename Format::Pair *side, const uint64_t *offsets, char *dst, uint64_t cap, const uint64_t *fastq_end0,
+                                                   const uint64_t *fastq_end1, uint64_t fastq_cap0, uint64_t fastq_cap1, const uint32_t *perm, uint32_t lds_bytes) {
+    extern __shared__ __attribute__((aligned(16))) char s_truth[];
     using Image = WaveImage<PERM, kSamPairs>;
     const uint32_t lane = threadIdx.x, part = lane / kSamPairs, seg = part >> 1, half = part & 1u;
     if (Image::first() >= n_pairs) return;
@@ -352,7 +399,7 @@ __global__ void __launch_bounds__(64) k_sam_write(DevSim S, NameTable names, con
     const uint64_t pair = im.item;
     ReadMeta m{};
     Fragment f{};
-    SamPair p{};
+    typename Format::Pair p{};
     uint64_t r = 0;
     if (im.active) {
         r = (uint64_t)seg * n_pairs + im.row;
@@ -363,28 +410,21 @@ __global__ void __launch_bounds__(64) k_sam_write(DevSim S, NameTable names, con
     const bool has_f = frags != nullptr;
     const WordColumn seq = raw.seq_of(r), qual = raw.qual_of(r), ops = raw.ops_of(r);
     const uint64_t ao_number = adapter_only_first + pair + 1u;
-    const SamMate w = seg ? p.mate[1] : p.mate[0];
-    const SamAlign a = sam_align(has_f, f, seg, p.mate[0], p.mate[1]);
-    const uint32_t rec_at = seg ? p.mate[0].bytes : 0u;                // of the record within its pair's text
+    const typename Format::Mate e = seg ? p.mate[1] : p.mate[0];
+    const SamAlign a = sam_align(has_f, f, seg, Format::walk(p.mate[0]), Format::walk(p.mate[1]));
+    const uint32_t rec_at = seg ? Format::bytes(p.mate[0]) : 0u;       // of the record within its pair's bytes
     if (!im.through_lds) {
-        if (im.active && half == 0u) sam_record(S, names, has_f, f, ao_number, m, seq, qual, ops, w, a, dst + offsets[pair] + rec_at);
+        if (im.active && half == 0u) Format::record(S, names, has_f, f, ao_number, m, seq, qual, ops, e, a, dst + offsets[pair] + rec_at);
         return;
     }
-    im.clear(s_sam, lds_bytes);
+    im.clear(s_truth, lds_bytes);
     if (im.active) {
-        const uint32_t qual_at = w.bytes - sam_tags_size(m) - m.read_len;
-        ImageSink t(im.item_text(s_sam) + rec_at + (half ? qual_at : 0u));
-        if (half == 0u) {
-            sam_head(S, names, has_f, f, ao_number, m, ops, w, a, t);
-            sam_line(seq, m.read_len, false, a.reverse != 0u, S.phred_offset, t);
-            t.ch('\t');
-        } else {
-            sam_line(qual, m.read_len, true, a.reverse != 0u, S.phred_offset, t);
-            sam_tags(m, ops, t);
-        }
+        ImageSink t(im.item_text(s_truth) + rec_at + (half ? Format::tail_at(e, m) : 0u));
+        if (half == 0u) Format::head(S, names, has_f, f, ao_number, m, seq, ops, e, a, t);
+        else Format::tail(S, m, qual, ops, a, t);
         t.finish();
     }
-    im.store_out(s_sam);
+    im.store_out(s_truth);
 }
 #endif
 

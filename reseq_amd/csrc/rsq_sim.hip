@@ -654,52 +654,45 @@ static void text_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint
     s.timers["format_write"].stop(st);
     HIP_CHECK(hipGetLastError());
 }
-// What a call that also writes the truth alignments hands down: the caller's SAM (or BAM) buffer.  nullptr: the call launches no kernel of rsq_sam.h or rsq_bam.h.
+// What a call that also writes the truth alignments hands down: the caller's SAM (or BAM) buffer.  nullptr: the call launches no kernel of rsq_sam.h.
 struct SamOut {
     char *dst;
     size_t cap;
     size_t *len;
-    bool bam = false;      // BAM records (rsq_bam.h: k_bam_sizes, k_bam_write) in place of SAM text; the call then launches neither kernel of rsq_sam.h
+    bool bam = false;      // BAM records (rsq_bam.h BamFormat) in place of SAM text (SamFormat): a call launches the kernels of one format
 };
-// SAM text of the pairs of reads_stage, behind their text_stage on the same stream (it reads the FASTQ offsets' totals: nothing is written unless all three texts
-// fit so far).  Offsets continue at sam_totals[part]; where the part ends goes to sam_totals[part + 1].  BAM records (sam.bam) take the same route with
-// k_bam_sizes / k_bam_write and their own side array; sizes, offsets and totals live in the same buffers (a call writes one kind).
-static void sam_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_first, const ReadsDone &rd, char *r1, size_t r1_cap, char *r2, size_t r2_cap, const SamOut &sam,
-                      uint32_t part, hipStream_t st) {
+// The truth records of the pairs of reads_stage in one format, behind their text_stage on the same stream (it reads the FASTQ offsets' totals: nothing is written
+// unless all three outputs fit so far).  Offsets continue at sam_totals[part]; where the part ends goes to sam_totals[part + 1].  A format has its own side array,
+// timer keys and image size; sizes, offsets and totals live in the same buffers (a call writes one kind).
+template <class Format>
+static void truth_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_first, const ReadsDone &rd, char *r1, size_t r1_cap, char *r2, size_t r2_cap, const SamOut &sam,
+                        uint32_t part, hipStream_t st) {
+    using Pair = typename Format::Pair;
+    constexpr bool bam = std::is_same<Format, BamFormat>::value;
+    const char *sizes_timer = bam ? "bam_sizes" : "sam_sizes", *write_timer = bam ? "bam_write" : "sam_write";
     rsq_sim::Workspace &w = *s.cur;
+    DevBuf &side = bam ? w.bam_side : w.sam_side;
     w.sam_sizes.reserve(n_pairs * 4 + 16);
     w.off_sam.reserve((n_pairs + 1) * 8);
+    side.reserve(n_pairs * sizeof(Pair) + 16);
     uint64_t *totals = s.sam_totals.as<uint64_t>();
     const uint64_t cap = sam.dst ? sam.cap : 0, cap1 = r1 ? r1_cap : 0, cap2 = r2 ? r2_cap : 0;
-    if (sam.bam) {
-        w.bam_side.reserve(n_pairs * sizeof(BamPair) + 16);
-        s.timers["bam_sizes"].start(st);
-        hipLaunchKernelGGL(k_bam_sizes, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw, rd.row_order, w.bam_side.as<BamPair>(),
-                           w.sam_sizes.as<uint32_t>());
-        s.timers["bam_sizes"].stop(st);
-        exclusive_scan(s, w.sam_sizes.as<uint32_t>(), n_pairs, w.off_sam.as<uint64_t>(), st, totals + part, totals + part + 1);
-        hipLaunchKernelGGL(k_max_size, dim3(std::min<uint64_t>(1024, cdiv(n_pairs, 256))), dim3(256), 0, st, w.sam_sizes.as<uint32_t>(), n_pairs, s.sam_longest.as<uint32_t>());
-        const uint32_t lds = sam_lds_bytes(s.bam_pair_bytes, rd.row_order != nullptr);
-        s.timers["bam_write"].start(st);
-        launch_text_waves(k_bam_write<true>, k_bam_write<false>, rd.row_order, dim3(cdiv(n_pairs, kSamPairs)), lds, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw,
-                          w.bam_side.as<BamPair>(), w.off_sam.as<uint64_t>(), sam.dst, cap, w.off_r1.as<uint64_t>() + n_pairs, w.off_r2.as<uint64_t>() + n_pairs, cap1, cap2, rd.row_order, lds);
-        s.timers["bam_write"].stop(st);
-        HIP_CHECK(hipGetLastError());
-        return;
-    }
-    w.sam_side.reserve(n_pairs * sizeof(SamPair) + 16);
-    s.timers["sam_sizes"].start(st);
-    hipLaunchKernelGGL(k_sam_sizes, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw, rd.row_order, w.sam_side.as<SamPair>(),
+    s.timers[sizes_timer].start(st);
+    hipLaunchKernelGGL(k_truth_sizes<Format>, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw, rd.row_order, side.as<Pair>(),
                        w.sam_sizes.as<uint32_t>());
-    s.timers["sam_sizes"].stop(st);
+    s.timers[sizes_timer].stop(st);
     exclusive_scan(s, w.sam_sizes.as<uint32_t>(), n_pairs, w.off_sam.as<uint64_t>(), st, totals + part, totals + part + 1);
     hipLaunchKernelGGL(k_max_size, dim3(std::min<uint64_t>(1024, cdiv(n_pairs, 256))), dim3(256), 0, st, w.sam_sizes.as<uint32_t>(), n_pairs, s.sam_longest.as<uint32_t>());
-    const uint32_t lds = sam_lds_bytes(s.sam_pair_bytes, rd.row_order != nullptr);
-    s.timers["sam_write"].start(st);
-    launch_text_waves(k_sam_write<true>, k_sam_write<false>, rd.row_order, dim3(cdiv(n_pairs, kSamPairs)), lds, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw,
-                      w.sam_side.as<SamPair>(), w.off_sam.as<uint64_t>(), sam.dst, cap, w.off_r1.as<uint64_t>() + n_pairs, w.off_r2.as<uint64_t>() + n_pairs, cap1, cap2, rd.row_order, lds);
-    s.timers["sam_write"].stop(st);
+    const uint32_t lds = sam_lds_bytes(bam ? s.bam_pair_bytes : s.sam_pair_bytes, rd.row_order != nullptr);
+    s.timers[write_timer].start(st);
+    launch_text_waves(k_truth_write<Format, true>, k_truth_write<Format, false>, rd.row_order, dim3(cdiv(n_pairs, kSamPairs)), lds, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw,
+                      side.as<Pair>(), w.off_sam.as<uint64_t>(), sam.dst, cap, w.off_r1.as<uint64_t>() + n_pairs, w.off_r2.as<uint64_t>() + n_pairs, cap1, cap2, rd.row_order, lds);
+    s.timers[write_timer].stop(st);
     HIP_CHECK(hipGetLastError());
+}
+static void sam_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_first, const ReadsDone &rd, char *r1, size_t r1_cap, char *r2, size_t r2_cap, const SamOut &sam,
+                      uint32_t part, hipStream_t st) {
+    (sam.bam ? truth_stage<BamFormat> : truth_stage<SamFormat>)(s, frags, n_pairs, adapter_first, rd, r1, r1_cap, r2, r2_cap, sam, part, st);
 }
 static void begin_sam_totals(rsq_sim &s, uint32_t parts, hipStream_t st) {
     s.sam_totals.reserve((size_t)(parts + 1) * 8 + 16);
@@ -1788,22 +1781,15 @@ int rsq_sim_pairs(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev
     REQUIRE(s && r1_len && r2_len && n_pairs, "null argument");
     return guard([&] { return sim_pairs(*s, block_lo, block_hi, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, n_pairs, frags_dev, frags_cap, (hipStream_t)stream); });
 }
-// truth alignments: coordinates through an allele's insertions and deletions are not worked out
-#define REQUIRE_NO_VARIANTS(s) REQUIRE(!(s)->has_variants, "truth alignments (SAM) are not available for a reference with variants (rsq_ref_read_variants)")
-int rsq_sim_pairs_sam(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len, char *sam_dev,
-                      size_t sam_cap, size_t *sam_len, uint64_t *n_pairs, rsq_fragment *frags_dev, size_t frags_cap, void *stream) {
-    REQUIRE(s && r1_len && r2_len && sam_len && n_pairs, "null argument");
-    REQUIRE_NO_VARIANTS(s);
-    const SamOut sam{sam_dev, sam_cap, sam_len};
-    return guard([&] { return sim_pairs(*s, block_lo, block_hi, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, n_pairs, frags_dev, frags_cap, (hipStream_t)stream, &sam); });
-}
-// ... as BAM records (rsq_bam.h).  What BAM cannot hold is refused here, before anything is launched: l_read_name is a byte, so no QNAME may exceed 254 characters
-// (the base identifier, the longest reference name, every number at its widest), and the bins cover 2^29 bases.
-static bool bam_refusal(const rsq_sim &s) {
+// Truth alignments, as SAM text or (bam) as BAM records.  Coordinates through an allele's insertions and deletions are not worked out: a reference with variants is
+// refused.  What BAM cannot hold is refused as well, before anything is launched: l_read_name is a byte, so no QNAME may exceed 254 characters (the base
+// identifier, the longest reference name, every number at its widest), and the bins cover 2^29 bases.
+static bool truth_refusal(const rsq_sim &s, bool bam) {
     if (s.has_variants) {
-        g_last_error = "truth alignments (BAM) are not available for a reference with variants (rsq_ref_read_variants)";
+        g_last_error = std::string("truth alignments (") + (bam ? "BAM" : "SAM") + ") are not available for a reference with variants (rsq_ref_read_variants)";
         return true;
     }
+    if (!bam) return false;
     size_t longest_name = 0;
     uint32_t longest_seq = 0;
     for (const std::string &n : s.ref_first_names) longest_name = std::max(longest_name, n.size());
@@ -1821,12 +1807,20 @@ static bool bam_refusal(const rsq_sim &s) {
     }
     return false;
 }
+static int pairs_truth(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len, char *out_dev,
+                       size_t out_cap, size_t *out_len, uint64_t *n_pairs, rsq_fragment *frags_dev, size_t frags_cap, void *stream, bool bam) {
+    REQUIRE(s && r1_len && r2_len && out_len && n_pairs, "null argument");
+    if (truth_refusal(*s, bam)) return RSQ_EINVAL;
+    const SamOut out{out_dev, out_cap, out_len, bam};
+    return guard([&] { return sim_pairs(*s, block_lo, block_hi, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, n_pairs, frags_dev, frags_cap, (hipStream_t)stream, &out); });
+}
+int rsq_sim_pairs_sam(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len, char *sam_dev,
+                      size_t sam_cap, size_t *sam_len, uint64_t *n_pairs, rsq_fragment *frags_dev, size_t frags_cap, void *stream) {
+    return pairs_truth(s, block_lo, block_hi, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, sam_dev, sam_cap, sam_len, n_pairs, frags_dev, frags_cap, stream, false);
+}
 int rsq_sim_pairs_bam(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len, char *bam_dev,
                       size_t bam_cap, size_t *bam_len, uint64_t *n_pairs, rsq_fragment *frags_dev, size_t frags_cap, void *stream) {
-    REQUIRE(s && r1_len && r2_len && bam_len && n_pairs, "null argument");
-    if (bam_refusal(*s)) return RSQ_EINVAL;
-    const SamOut bam{bam_dev, bam_cap, bam_len, true};
-    return guard([&] { return sim_pairs(*s, block_lo, block_hi, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, n_pairs, frags_dev, frags_cap, (hipStream_t)stream, &bam); });
+    return pairs_truth(s, block_lo, block_hi, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, bam_dev, bam_cap, bam_len, n_pairs, frags_dev, frags_cap, stream, true);
 }
 
 // ---- a rank's share, generated once and kept (include/reseq_amd.h rsq_sim_job_*)
@@ -2276,25 +2270,23 @@ int rsq_sim_adapter_only_pairs(rsq_sim *s, uint64_t first, uint64_t n, char *r1_
         return adapter_only_pairs(*s, n, first, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, (hipStream_t)stream);
     });
 }
-int rsq_sim_adapter_only_pairs_sam(rsq_sim *s, uint64_t first, uint64_t n, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len, char *sam_dev,
-                                   size_t sam_cap, size_t *sam_len, void *stream) {
-    REQUIRE(s && r1_len && r2_len && sam_len && s->prepared, "simulator not prepared");
-    REQUIRE_NO_VARIANTS(s);
-    const SamOut sam{sam_dev, sam_cap, sam_len};
+static int adapter_only_pairs_truth(rsq_sim *s, uint64_t first, uint64_t n, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len, char *out_dev,
+                                    size_t out_cap, size_t *out_len, void *stream, bool bam) {
+    REQUIRE(s && r1_len && r2_len && out_len && s->prepared, "simulator not prepared");
+    if (truth_refusal(*s, bam)) return RSQ_EINVAL;
+    const SamOut out{out_dev, out_cap, out_len, bam};
     return guard([&] {
         HIP_CHECK(hipSetDevice(s->device));
-        return adapter_only_pairs(*s, n, first, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, (hipStream_t)stream, &sam);
+        return adapter_only_pairs(*s, n, first, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, (hipStream_t)stream, &out);
     });
+}
+int rsq_sim_adapter_only_pairs_sam(rsq_sim *s, uint64_t first, uint64_t n, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len, char *sam_dev,
+                                   size_t sam_cap, size_t *sam_len, void *stream) {
+    return adapter_only_pairs_truth(s, first, n, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, sam_dev, sam_cap, sam_len, stream, false);
 }
 int rsq_sim_adapter_only_pairs_bam(rsq_sim *s, uint64_t first, uint64_t n, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len, char *bam_dev,
                                    size_t bam_cap, size_t *bam_len, void *stream) {
-    REQUIRE(s && r1_len && r2_len && bam_len && s->prepared, "simulator not prepared");
-    if (bam_refusal(*s)) return RSQ_EINVAL;
-    const SamOut bam{bam_dev, bam_cap, bam_len, true};
-    return guard([&] {
-        HIP_CHECK(hipSetDevice(s->device));
-        return adapter_only_pairs(*s, n, first, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, (hipStream_t)stream, &bam);
-    });
+    return adapter_only_pairs_truth(s, first, n, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, bam_dev, bam_cap, bam_len, stream, true);
 }
 
 // A profile with several read lengths draws a record's read length from tables over the fragment length (draw_read_length): a length outside them ends the call

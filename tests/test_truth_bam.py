@@ -1,18 +1,17 @@
 """Truth alignments as BAM (reseq_amd/csrc/rsq_bam.h; include/reseq_amd.h rsq_sim_pairs_bam) without a GPU: the header, and the per-lane functions -- record
-size, fixed fields, CIGAR words, packed SEQ, QUAL, tags -- run on the CPU (tests/hostemu/bam_trial.cpp, built here with g++) on crafted rows.  A BAM record is a
+size, fixed fields, CIGAR words, packed SEQ, QUAL, tags -- run on the CPU (tests/hostemu/bam_trial.cpp over truth_trial.h, built here with g++) on crafted rows.  A BAM record is a
 pure re-encoding of its SAM line: `decode_bam` below (pure Python, `struct`) turns the records back into SAM text, checking block_size, l_read_name and
 bin == reg2bin on the way, and that text must equal `sam_pair` of tests/test_truth_sam.py, the statement the SAM writer is pinned to, byte for byte.
 tests/test_truth_bam_gpu.py applies the same decoder to the device's output."""
 import ctypes as C
 import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from reseq_amd import api
-from test_truth_sam import CRAFTED, D, GOLDEN, HERE, I, M, NAMES, TrialMate, TrialPair, fragment, make_mate, random_template, sam_text, template_bases
+from test_truth_sam import CRAFTED, D, GOLDEN, HERE, I, M, NAMES, TrialPair, build_trial, fill_trial, fragment, make_mate, random_template, sam_text, template_bases
 
 MARKER = 0xA7
 UNMAPPED_BIN = 4680
@@ -145,10 +144,7 @@ def test_abi_symbols():
 # ------------------------------------------------------------------------------------------------ the per-lane functions on the host
 @pytest.fixture(scope="module")
 def trial_lib(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("bam_trial") / "libbam_trial.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-shared", "-o", out,
-                    os.path.join(HERE, "hostemu", "bam_trial.cpp")], check=True)
-    L = C.CDLL(out)
+    L = build_trial(tmp_path_factory, "bam_trial")
     L.bam_trial.argtypes = [C.POINTER(TrialPair), C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]
     return L
 
@@ -156,16 +152,7 @@ def trial_lib(tmp_path_factory):
 def run_pair(L, mates, frag, phred_offset, adapter_only_number=0, tile=1101, base=b"ReseqRead_", names=NAMES, at=0):
     """(fastq record 1, fastq record 2, the pair's two BAM records) from the trial library, the records written `at` bytes into a marked buffer: bam_record_size
     is what bam_record wrote, nothing around the records is touched, and (inside the trial) the writer kernel's two sinks a mate give the same bytes"""
-    name_ptr = np.concatenate([[0], np.cumsum([len(n) for n in names])]).astype(np.uint32)
-    t = TrialPair(has_fragment=0 if frag is None else 1, adapter_only_number=adapter_only_number, phred_offset=phred_offset, tile=tile, base_identifier=base,
-                  names=b"".join(names), name_ptr=name_ptr.ctypes.data)
-    if frag is not None:
-        t.seq, t.start, t.len, t.strand, t.block, t.number = (int(frag[k]) for k in ("seq", "start", "len", "strand", "block", "number"))
-    keep = []
-    for seg, m in enumerate(mates):
-        arrays = [np.ascontiguousarray(m[k]) if len(m[k]) else np.zeros(1, np.uint8) for k in ("seq", "qual", "ops")]
-        keep.append(arrays)
-        t.mate[seg] = TrialMate(m["read_len"], m["n_iter_m"], m["n_iter_s"], m["hard_clip"], m["num_errors"], *(a.ctypes.data for a in arrays))
+    t, keep = fill_trial(mates, frag, phred_offset, adapter_only_number, tile, base, names)
     cap = 8192
     f1, f2 = (C.create_string_buffer(cap) for _ in range(2))
     bam = C.create_string_buffer(bytes([MARKER]) * cap, cap)

@@ -1,5 +1,5 @@
 """Truth alignments (reseq_amd/csrc/rsq_sam.h; include/reseq_amd.h rsq_sim_pairs_sam) without a GPU: the header, and the per-lane functions -- ops walk,
-alignment, CIGAR writer, reversed data lines, record size, record -- run on the CPU (tests/hostemu/sam_trial.cpp, built here with g++) on crafted rows and
+alignment, CIGAR writer, reversed data lines, record size, record -- run on the CPU (tests/hostemu/sam_trial.cpp over truth_trial.h, built here with g++) on crafted rows and
 compared with `sam_pair`, this module's own statement of the record's rules, applied to the FASTQ records the same rows give.  The statement works from the
 FASTQ text and the fragment alone (the SAM text is a pure function of the two); tests/test_truth_sam_gpu.py applies it to the device's output."""
 import ctypes as C
@@ -136,12 +136,17 @@ NAMES = [b"chrA", b"NC_000913.3_1-500", b"s"]
 M, D, I = 0, 1, 2          # the 2-bit ops: the part's own op (M in the template part, S in the adapter part), D, I
 
 
+def build_trial(tmp_path_factory, name):
+    """tests/hostemu/<name>.cpp as a shared library (both formats' trials are tests/hostemu/truth_trial.h; tests/test_truth_bam.py builds bam_trial)"""
+    out = str(tmp_path_factory.mktemp(name) / ("lib%s.so" % name))
+    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-shared", "-o", out,
+                    os.path.join(HERE, "hostemu", name + ".cpp")], check=True)
+    return C.CDLL(out)
+
+
 @pytest.fixture(scope="module")
 def trial_lib(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("sam_trial") / "libsam_trial.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-shared", "-o", out,
-                    os.path.join(HERE, "hostemu", "sam_trial.cpp")], check=True)
-    L = C.CDLL(out)
+    L = build_trial(tmp_path_factory, "sam_trial")
     L.sam_trial.argtypes = [C.POINTER(TrialPair), C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_void_p]
     return L
 
@@ -157,18 +162,25 @@ def make_mate(rng, template_ops, adapter_ops, hard_clip, phred_offset, with_n=Fa
     return dict(read_len=read_len, n_iter_m=len(template_ops), n_iter_s=len(adapter_ops), hard_clip=hard_clip, num_errors=int(rng.integers(0, 12)), seq=seq, qual=qual, ops=ops)
 
 
-def run_pair(L, mates, frag, phred_offset, adapter_only_number=0, tile=1101, base=b"ReseqRead_"):
-    """(fastq record 1, fastq record 2, SAM text of the pair) from the trial library; checks sam_record_size against what sam_record wrote"""
-    name_ptr = np.concatenate([[0], np.cumsum([len(n) for n in NAMES])]).astype(np.uint32)
+def fill_trial(mates, frag, phred_offset, adapter_only_number, tile, base, names):
+    """(the trial's input, the arrays it points to: to be kept alive over the call)"""
+    name_ptr = np.concatenate([[0], np.cumsum([len(n) for n in names])]).astype(np.uint32)
     t = TrialPair(has_fragment=0 if frag is None else 1, adapter_only_number=adapter_only_number, phred_offset=phred_offset, tile=tile, base_identifier=base,
-                  names=b"".join(NAMES), name_ptr=name_ptr.ctypes.data)
+                  names=b"".join(names), name_ptr=name_ptr.ctypes.data)
     if frag is not None:
         t.seq, t.start, t.len, t.strand, t.block, t.number = (int(frag[k]) for k in ("seq", "start", "len", "strand", "block", "number"))
-    keep = []
+    keep = [name_ptr]
     for seg, m in enumerate(mates):
         arrays = [np.ascontiguousarray(m[k]) if len(m[k]) else np.zeros(1, np.uint8) for k in ("seq", "qual", "ops")]
         keep.append(arrays)
         t.mate[seg] = TrialMate(m["read_len"], m["n_iter_m"], m["n_iter_s"], m["hard_clip"], m["num_errors"], *(a.ctypes.data for a in arrays))
+    return t, keep
+
+
+def run_pair(L, mates, frag, phred_offset, adapter_only_number=0, tile=1101, base=b"ReseqRead_"):
+    """(fastq record 1, fastq record 2, SAM text of the pair) from the trial library; checks sam_record_size against what the record function wrote, and (inside
+    the trial) that the writer kernel's two sinks a mate give the same bytes"""
+    t, keep = fill_trial(mates, frag, phred_offset, adapter_only_number, tile, base, NAMES)
     cap = 8192
     f1, f2, sam = (C.create_string_buffer(cap) for _ in range(3))
     sizes = np.zeros(6, np.uint32)

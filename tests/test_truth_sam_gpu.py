@@ -273,3 +273,51 @@ def test_read_length_150(workdir):
         assert n == 2 * len(frags) and seen["without_m"] == 0 and residues == {150 % 4}
     finally:
         c.close()
+
+
+# ------------------------------------------------------------------------------------------------ the writers' straight-to-HBM fallback
+# The image a FRESH simulator gives its first writing call holds pairs of this many bytes: the initial values of rsq_sim::sam_pair_bytes and bam_pair_bytes in
+# reseq_amd/csrc/rsq_sim.hip.  The test below takes the fallback only while its pairs are larger: whoever raises those two values raises these, and the test then
+# says whether its records still are.
+FRESH_IMAGE_PAIR_BYTES = {"sam": 1100, "bam": 700}
+
+
+def long_name_case(workdir):
+    """test_read_length_150's inputs with a reference name of 150 characters: a pair is about 1.45 KB of SAM and 1.0 KB of BAM, more than the image of a fresh
+    simulator holds (pairs of 1100 and 700 bytes); the QNAME stays below BAM's 254"""
+    return Case(workdir, "truth_long_name", synth.P0, [20000], 11, 1500, no_substitutions=True, prof_seed=103741084, ref_seed=2, names=["n" * 150 + " rest of the id"])
+
+
+@pytest.fixture(scope="module")
+def long_name_expected(workdir):
+    """pairs_sam / pairs_bam size with a first call that writes nothing but already sizes the image for the second: these bytes went through the image"""
+    c = long_name_case(workdir)
+    try:
+        return dict(sam=c.sim.pairs_sam(1, c.tb + 1), bam=c.sim.pairs_bam(1, c.tb + 1))
+    finally:
+        c.close()
+
+
+@pytest.mark.parametrize("kind", ["sam", "bam"])
+def test_records_larger_than_the_image_go_straight_to_the_output(workdir, long_name_expected, kind):
+    """a fresh simulator's first writing call meets records its image cannot hold (every wave writes a lane a record, no LDS); its second call has the image sized"""
+    from test_truth_bam import decode_bam
+    frags, f1, f2, want = long_name_expected[kind]
+    assert 1000 < len(frags) < 2000 and len(want) / len(frags) > FRESH_IMAGE_PAIR_BYTES[kind] + 16      # (16: the skew of a wave's text against its image)
+    c = long_name_case(workdir)
+    arrays = [api.DeviceArray(c.sim.device, n) for n in (len(f1), len(f2), len(want), (len(frags) + 1) * api.FRAGMENT_DTYPE.itemsize)]
+    r1, r2, out, fr = arrays
+    try:
+        for route in ("fallback", "image"):
+            n, l1, l2, ls, rc = getattr(c.sim, "pairs_%s_device" % kind)(1, c.tb + 1, r1, r2, out, fr)
+            assert rc == api.RSQ_OK and (n, l1, l2, ls) == (len(frags), len(f1), len(f2), len(want)), route
+            assert c.sim.last_kernel_launches(kind + "_write") == 1
+            assert out.to_numpy(np.uint8, ls).tobytes() == want, route
+            assert r1.to_numpy(np.uint8, l1).tobytes() == f1 and r2.to_numpy(np.uint8, l2).tobytes() == f2 and fr.to_numpy(api.FRAGMENT_DTYPE, n).tobytes() == frags.tobytes()
+        text = want if kind == "sam" else decode_bam(want, c.names)[0]
+        assert text == c.statement(frags, f1, f2) and text == long_name_expected["sam"][3]
+        assert max(len(line.split(b"\t")[0]) for line in text.splitlines()) < 254
+    finally:
+        for d in arrays:
+            d.free()
+        c.close()
