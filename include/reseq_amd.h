@@ -342,6 +342,34 @@ int rsq_sim_pairs_bam(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1
 int rsq_sim_adapter_only_pairs_bam(rsq_sim *s, uint64_t first, uint64_t n, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len,
                                    char *bam_dev, size_t bam_cap, size_t *bam_len, void *stream);
 
+/* The truth BAM sorted by coordinate, with its .bai index (reseq_amd/csrc/rsq_bamsort.h; SAM specification 5.2).  The records are those of rsq_sim_pairs_bam over
+ * the same blocks, byte for byte; the sorted stream is the mapped ones stably sorted by (refID, pos) -- ties keep the order of rsq_sim_pairs_bam's stream --, then
+ * the unmapped ones of the block calls in their order, then whatever the caller appends (the records of rsq_sim_adapter_only_pairs_bam, which are unmapped).  It
+ * does not depend on how the blocks are cut into calls, nor on options overlap and image_tiles.  Fragments leave the sieve in reference order, so a call hands
+ * out every record below its last block's end and holds the rest back for the next call: the longest fragment times the coverage, never the whole file.
+ *   rsq_ref_bam_header_so: coordinate = 0: the bytes of rsq_ref_bam_header; 1: the same with "@HD VN:1.6 SO:coordinate" (no GO:), the header of the sorted file.
+ *   rsq_sim_bam_sorted_begin starts a run: held records and index state of an earlier run are dropped.  first_record_offset: the uncompressed offset in the file of
+ * the first record (the header's length).  The calls of a run are contiguous and rising: a call's block_lo is the block_hi of the call before, else RSQ_ESTATE.
+ *   rsq_sim_pairs_bam_sorted: the arguments of rsq_sim_pairs_bam and *n_records; the FASTQ texts and the fragments are exactly that call's.  bam_dev receives the
+ * records that are final, *n_records of them in *bam_len bytes, which follow the call before's in the stream.  RSQ_ENOSPC as for the other calls -- all three
+ * needed sizes are reported, no record is written -- and the held records and the index state stay as they were: the call can be repeated with larger buffers.
+ * The refusals of rsq_sim_pairs_bam apply.  A record that lies below the end of the call before's blocks (the rules of rsq_sam.h exclude it) fails the call with
+ * RSQ_EINVAL rather than leaving an unsorted file.
+ *   rsq_sim_bam_sorted_flush writes what is still held: *n_mapped mapped records in order, then *n_unmapped unmapped ones.  Only unmapped records may follow.
+ *   rsq_sim_bam_sorted_index: the bytes of the .bai for the run so far, from the file's BGZF block table: block k holds the uncompressed bytes from block_u[k] to
+ * block_u[k + 1] and begins at byte block_c[k] of the file; the end-of-file member is the table's last entry (block_u = all uncompressed bytes).  Whoever writes
+ * the file reads the table off the members (BSIZE at bytes 16-17, ISIZE in the last four).  n_no_coor: the unmapped records of the file.  A record's interval is
+ * [pos, pos + max(reference bases, 1)), the one its bin is taken from; a chunk is a maximal run of records of one bin that are consecutive in the file; the
+ * linear index has the first record overlapping each 16 kb window, a window without one the next window's value; the metadata pseudo-bin 37450 is left out.
+ * `need` / RSQ_ENOSPC as for rsq_ref_bam_header.  Kernel times: "bam_sort_keys", "bam_sort", "bam_gather", "bam_index" beside "bam_sizes" and "bam_write"; no
+ * other call launches them. */
+int rsq_ref_bam_header_so(const rsq_ref *ref, int coordinate, char *out, size_t cap, size_t *need);
+int rsq_sim_bam_sorted_begin(rsq_sim *s, uint64_t first_record_offset);
+int rsq_sim_pairs_bam_sorted(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len,
+                             char *bam_dev, size_t bam_cap, size_t *bam_len, uint64_t *n_pairs, uint64_t *n_records, rsq_fragment *frags_dev, size_t frags_cap, void *stream);
+int rsq_sim_bam_sorted_flush(rsq_sim *s, char *bam_dev, size_t bam_cap, size_t *bam_len, uint64_t *n_mapped, uint64_t *n_unmapped, void *stream);
+int rsq_sim_bam_sorted_index(rsq_sim *s, const uint64_t *block_u, const uint64_t *block_c, size_t n_blocks, uint64_t n_no_coor, char *out, size_t cap, size_t *need);
+
 /* Simulator::ApplyErrorsAndQualityToFastaInput with the FASTA header already parsed (reseq/Simulator.cpp:2403-2512):
  * n records of `read_len` template bases each.  Inputs (device): seqs[n][read_len] base codes 0..3, seg[n] template
  * segment 0/1, frag_len[n], dom[n][read_len] dominant-error base codes 0..4, rate[n][read_len] error percent.

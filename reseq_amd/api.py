@@ -59,6 +59,7 @@ SYMBOLS = {
     "rsq_ref_sequence_name": (C.c_int, [_vp, _u32, C.c_char_p, _sz]),
     "rsq_ref_sam_header": (C.c_int, [_vp, C.c_char_p, _sz, _psz]),
     "rsq_ref_bam_header": (C.c_int, [_vp, C.c_char_p, _sz, _psz]),
+    "rsq_ref_bam_header_so": (C.c_int, [_vp, C.c_int, C.c_char_p, _sz, _psz]),
     "rsq_ref_load_fasta": (C.c_int, [C.c_char_p, _pp]),
     "rsq_ref_replace_n": (C.c_int, [_vp, _u64]),
     "rsq_ref_free": (None, [_vp]),
@@ -107,6 +108,10 @@ SYMBOLS = {
     "rsq_sim_adapter_only_pairs_sam": (C.c_int, [_vp, _u64, _u64, _vp, _sz, _psz, _vp, _sz, _psz, _vp, _sz, _psz, _vp]),
     "rsq_sim_pairs_bam": (C.c_int, [_vp, _u32, _u32, _vp, _sz, _psz, _vp, _sz, _psz, _vp, _sz, _psz, C.POINTER(_u64), _vp, _sz, _vp]),
     "rsq_sim_adapter_only_pairs_bam": (C.c_int, [_vp, _u64, _u64, _vp, _sz, _psz, _vp, _sz, _psz, _vp, _sz, _psz, _vp]),
+    "rsq_sim_bam_sorted_begin": (C.c_int, [_vp, _u64]),
+    "rsq_sim_pairs_bam_sorted": (C.c_int, [_vp, _u32, _u32, _vp, _sz, _psz, _vp, _sz, _psz, _vp, _sz, _psz, C.POINTER(_u64), C.POINTER(_u64), _vp, _sz, _vp]),
+    "rsq_sim_bam_sorted_flush": (C.c_int, [_vp, _vp, _sz, _psz, C.POINTER(_u64), C.POINTER(_u64), _vp]),
+    "rsq_sim_bam_sorted_index": (C.c_int, [_vp, _vp, _vp, _sz, _u64, C.c_char_p, _sz, _psz]),
     "rsq_sim_job_generate": (C.c_int, [_vp, _u32, _u32, _u32, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), _vp]),
     "rsq_sim_job_write": (C.c_int, [_vp, C.c_char_p, _u64, C.c_char_p, _u64, _u32]),
     "rsq_sim_job_compress": (C.c_int, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
@@ -324,6 +329,10 @@ class Reference:
     def bam_header(self):
         """the same header as the first bytes of a BAM file (rsq_ref_bam_header): magic, the text of sam_header(), the sequences' names and lengths; uncompressed"""
         return self._header(lib().rsq_ref_bam_header)
+
+    def bam_header_so(self, coordinate):
+        """rsq_ref_bam_header_so: bam_header() (coordinate 0), or the header of the coordinate-sorted file (1: "@HD VN:1.6 SO:coordinate")"""
+        return self._header(lambda h, out, cap, need: lib().rsq_ref_bam_header_so(h, coordinate, out, cap, need))
 
     def read_variants(self, path):
         """Reference::PrepareVariantFile + ReadFirstVariants: returns the number of alleles"""
@@ -617,6 +626,71 @@ class Simulator:
     def adapter_only_pairs_bam(self, first, n, stream=None):
         """adapter_only_pairs() and the (unmapped) BAM records of the same pairs: (fastq1 bytes, fastq2 bytes, BAM bytes)"""
         return self._adapter_only_pairs_truth(lib().rsq_sim_adapter_only_pairs_bam, first, n, stream)
+
+    def bam_sorted_begin(self, first_record_offset):
+        """rsq_sim_bam_sorted_begin: starts a run of pairs_bam_sorted calls; first_record_offset = the uncompressed offset of the first record (the header's length)"""
+        _check(lib().rsq_sim_bam_sorted_begin(self.h, first_record_offset))
+
+    def pairs_bam_sorted_device(self, block_lo, block_hi, r1, r2, bam, frags=None, stream=None):
+        """rsq_sim_pairs_bam_sorted into caller-owned DeviceArrays (None: only the sizes).  Returns (n_pairs, len1, len2, bam_len, n_records, rc)."""
+        l1, l2, ls, n, nr = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_uint64(), C.c_uint64()
+        rc = lib().rsq_sim_pairs_bam_sorted(self.h, block_lo, block_hi, r1.ptr if r1 else None, r1.nbytes if r1 else 0, C.byref(l1), r2.ptr if r2 else None,
+                                            r2.nbytes if r2 else 0, C.byref(l2), bam.ptr if bam else None, bam.nbytes if bam else 0, C.byref(ls), C.byref(n), C.byref(nr),
+                                            frags.ptr if frags else None, frags.nbytes // FRAGMENT_DTYPE.itemsize if frags else 0, stream)
+        return n.value, l1.value, l2.value, ls.value, nr.value, rc
+
+    def pairs_bam_sorted(self, block_lo, block_hi, stream=None):
+        """the next call of a sorted run: (fragments, fastq1 bytes, fastq2 bytes, the final records' bytes, their number); sized by a first call, which leaves the
+        run's state as it was"""
+        n, l1, l2, ls, nr, rc = self.pairs_bam_sorted_device(block_lo, block_hi, None, None, None, None, stream)
+        if rc == RSQ_OK:                                           # no pairs and no record to hand out: the call is done
+            return np.zeros(0, FRAGMENT_DTYPE), b"", b"", b"", 0
+        if rc != RSQ_ENOSPC:
+            _check(rc)
+        r1, r2, out = DeviceArray(self.device, max(l1, 16)), DeviceArray(self.device, max(l2, 16)), DeviceArray(self.device, max(ls, 16))
+        fr = DeviceArray(self.device, (n + 1) * FRAGMENT_DTYPE.itemsize)
+        try:
+            n2, l1b, l2b, lsb, nrb, rc = self.pairs_bam_sorted_device(block_lo, block_hi, r1, r2, out, fr, stream)
+            _check(rc)
+            assert (n2, l1b, l2b, lsb, nrb) == (n, l1, l2, ls, nr)
+            return fr.to_numpy(FRAGMENT_DTYPE, n), r1.to_numpy(np.uint8, l1).tobytes(), r2.to_numpy(np.uint8, l2).tobytes(), out.to_numpy(np.uint8, ls).tobytes(), nr
+        finally:
+            for d in (r1, r2, out, fr):
+                d.free()
+
+    def bam_sorted_flush_device(self, bam, stream=None):
+        """rsq_sim_bam_sorted_flush into a caller-owned DeviceArray (None: only the size).  Returns (bam_len, n_mapped, n_unmapped, rc)."""
+        ls, nm, nu = C.c_size_t(), C.c_uint64(), C.c_uint64()
+        rc = lib().rsq_sim_bam_sorted_flush(self.h, bam.ptr if bam else None, bam.nbytes if bam else 0, C.byref(ls), C.byref(nm), C.byref(nu), stream)
+        return ls.value, nm.value, nu.value, rc
+
+    def bam_sorted_flush(self, stream=None):
+        """the records a sorted run still holds: (their bytes -- the mapped in order, then the unmapped --, mapped records, unmapped records)"""
+        ls, nm, nu, rc = self.bam_sorted_flush_device(None, stream)
+        if rc == RSQ_OK:
+            return b"", nm, nu
+        if rc != RSQ_ENOSPC:
+            _check(rc)
+        out = DeviceArray(self.device, ls)
+        try:
+            ls, nm, nu, rc = self.bam_sorted_flush_device(out, stream)
+            _check(rc)
+            return out.to_numpy(np.uint8, ls).tobytes(), nm, nu
+        finally:
+            out.free()
+
+    def bam_sorted_index(self, block_u, block_c, n_no_coor):
+        """rsq_sim_bam_sorted_index: the .bai bytes of the run from the file's BGZF block table (per block its uncompressed and its compressed start; the
+        end-of-file member last)"""
+        u, c = np.ascontiguousarray(block_u, np.uint64), np.ascontiguousarray(block_c, np.uint64)
+        assert len(u) == len(c)
+        need = C.c_size_t(0)
+        rc = lib().rsq_sim_bam_sorted_index(self.h, u.ctypes.data, c.ctypes.data, len(u), n_no_coor, None, 0, C.byref(need))
+        if rc != RSQ_ENOSPC:
+            _check(rc)
+        buf = C.create_string_buffer(need.value + 1)
+        _check(lib().rsq_sim_bam_sorted_index(self.h, u.ctypes.data, c.ctypes.data, len(u), n_no_coor, buf, need.value, C.byref(need)))
+        return buf.raw[:need.value]
 
     def job_generate(self, block_lo, block_hi, batch_blocks=0, stream=None):
         """the rank's share of a job: simulated once, its FASTQ text kept in device memory; returns (pairs, bytes of file 1, bytes of file 2)"""

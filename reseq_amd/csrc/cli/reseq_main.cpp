@@ -20,6 +20,7 @@
 #include <chrono>
 
 #include <fstream>
+#include <functional>
 #include <iostream>
 #include <condition_variable>
 #include <deque>
@@ -65,7 +66,7 @@ const std::map<std::string, std::string> kShort = {{"-j", "threads"}, {"-h", "he
                                                    {"-v", "vcfIn"},   {"-p", "probabilitiesIn"}, {"-P", "probabilitiesOut"}, {"-1", "firstReadsOut"},
                                                    {"-2", "secondReadsOut"}, {"-c", "coverage"}, {"-R", "refSim"}, {"-V", "vcfSim"}, {"-i", "input"}, {"-o", "output"}};
 const std::set<std::string> kFlags = {"help", "version", "noBias", "noTiles", "statsOnly", "tiles", "stopAfterEstimation", "noInDelErrors", "noSubstitutionErrors", "maxLenDeletion", "maxReadLength",
-                                      "dumpArchiveLayout", "traceStages", "hostGzip"};
+                                      "dumpArchiveLayout", "traceStages", "hostGzip", "truthBamSort"};
 
 bool parse(int argc, char **argv, int first, Args &a) {
     for (int i = first; i < argc; ++i) {
@@ -237,6 +238,7 @@ struct DevBuffer {
 struct AsyncOut {
     TextOut out;
     std::string tail;                                   // written behind the last text when the file is closed (the BGZF end-of-file member)
+    std::function<void(const unsigned char *, size_t)> on_bytes;      // sees every chunk once it is in host memory, in file order (the calling thread)
     void *buf[2] = {nullptr, nullptr};
     size_t cap[2] = {0, 0}, len[2] = {0, 0};
     bool full[2] = {false, false};
@@ -284,6 +286,7 @@ struct AsyncOut {
                 cap[k] = kChunk;
             }
             if (!check(rsq_dev_download(d.device, buf[k], static_cast<const char *>(d.p) + done, n), "download")) return false;
+            if (on_bytes) on_bytes(static_cast<const unsigned char *>(buf[k]), n);
             {
                 std::lock_guard<std::mutex> lock(m);
                 len[k] = n;
@@ -334,6 +337,59 @@ struct TruthOut {
     AsyncOut file;
     DevBuffer text, packed;                             // a call's records, and their members
     size_t len = 0;
+    // --truthBamSort: the records leave in coordinate order (rsq_sim_pairs_bam_sorted) and the file gets its .bai, for which the file's BGZF block table is read
+    // off the members where the writer has them in host memory anyway (AsyncOut::on_bytes): per block its uncompressed and its compressed start.  A member may be
+    // cut by a chunk's end: its first part waits in `cut_member`.
+    bool sorted = false;
+    bool batch_done = false;                            // the batch's sorted call has handed out its records: it is not repeated when another call asks for room
+    std::vector<uint64_t> block_u, block_c;
+    uint64_t u_at = 0, c_at = 0, n_no_coor = 0;
+    std::vector<unsigned char> cut_member;
+    bool members_ok = true;
+    void note_member(const unsigned char *m, size_t size) {
+        uint32_t isize = 0;
+        memcpy(&isize, m + size - 4, 4);
+        block_u.push_back(u_at);
+        block_c.push_back(c_at);
+        u_at += isize;
+        c_at += size;
+    }
+    static size_t member_size(const unsigned char *m) { return (size_t)(m[16] | (m[17] << 8)) + 1; }      // BSIZE
+    void scan_members(const unsigned char *p, size_t n) {
+        size_t at = 0;
+        if (!cut_member.empty()) {                      // the rest of the member the chunk before ended in
+            if (cut_member.size() < 18) {
+                const size_t take = std::min(n, 18 - cut_member.size());
+                cut_member.insert(cut_member.end(), p, p + take);
+                at = take;
+                if (cut_member.size() < 18) return;
+            }
+            const size_t size = member_size(cut_member.data());
+            if (size < 26 || size < cut_member.size()) {
+                members_ok = false;
+                return;
+            }
+            const size_t take = std::min(n - at, size - cut_member.size());
+            cut_member.insert(cut_member.end(), p + at, p + at + take);
+            at += take;
+            if (cut_member.size() < size) return;
+            note_member(cut_member.data(), size);
+            cut_member.clear();
+        }
+        while (at < n) {
+            const size_t size = n - at >= 18 ? member_size(p + at) : 0;
+            if (n - at >= 18 && size < 26) {
+                members_ok = false;
+                return;
+            }
+            if (n - at < 18 || at + size > n) {
+                cut_member.assign(p + at, p + n);
+                return;
+            }
+            note_member(p + at, size);
+            at += size;
+        }
+    }
     decltype(&rsq_ref_sam_header) header;
     decltype(&rsq_sim_pairs_sam) pairs;
     decltype(&rsq_sim_adapter_only_pairs_sam) adapter_only;
@@ -631,6 +687,13 @@ int illumina_pe(const Args &a) {
             return 1;
         }
     }
+    if (a.has("truthBamSort")) {
+        if (truths.empty() || !truths.back().bam) {
+            ERR("--truthBamSort sorts the file of --truthBam: give --truthBam truth.bam as well");
+            return 1;
+        }
+        truths.back().sorted = true;
+    }
     const bool any_truth = !truths.empty();
     const char *truth_option = any_truth ? truths.front().option : "";
     rsq_profile *prof = nullptr;
@@ -789,16 +852,19 @@ int illumina_pe(const Args &a) {
             len = packed;
             return check(rc, "Compressing the output failed");
         };
-        auto push_truth = [&](TruthOut &t) { return members(t.gz, t.text, t.len, t.packed) && t.file.push(t.gz ? t.packed : t.text, t.len); };
+        auto push_truth = [&](TruthOut &t) { return members(t.gz, t.text, t.len, t.packed) && t.file.push(t.gz ? t.packed : t.text, t.len) && t.members_ok; };
+        for (TruthOut &t : truths)
+            if (t.sorted) t.file.on_bytes = [&t](const unsigned char *p, size_t n) { t.scan_members(p, n); };
         for (TruthOut &t : truths) {                             // the header, through the same route as the records (BAM: the first bytes of the stream they continue)
             if (!ok) break;
             size_t need = 0;
-            t.header(ref, nullptr, 0, &need);
+            auto header_of = [&](char *out, size_t cap) { return t.sorted ? rsq_ref_bam_header_so(ref, 1, out, cap, &need) : t.header(ref, out, cap, &need); };
+            header_of(nullptr, 0);
             std::string header(need, '\0');
-            ok = check(t.header(ref, &header[0], need, &need), t.bam ? "BAM header" : "SAM header") && t.text.ensure(need + 4096) &&
+            ok = check(header_of(&header[0], need), t.bam ? "BAM header" : "SAM header") && t.text.ensure(need + 4096) &&
                  check(rsq_dev_upload((int)device, t.text.p, header.data(), need), "upload");
             t.len = need;
-            ok = ok && push_truth(t);
+            ok = ok && push_truth(t) && (!t.sorted || check(rsq_sim_bam_sorted_begin(sim, need), "sorted BAM"));
         }
         // One batch.  Without a truth output the plain call; else a call per output, SAM first (with both a batch is simulated once for each: the calls write the
         // same FASTQ text into the same buffers): a hard error ends the batch, RSQ_ENOSPC from either lets the other state its size too, then all buffers grow
@@ -809,9 +875,11 @@ int illumina_pe(const Args &a) {
                 if (truths.empty()) return (int)plain();
                 int rc = RSQ_OK;
                 for (TruthOut &t : truths) {
+                    if (t.batch_done) continue;                  // (a sorted call that returned RSQ_OK has moved its run on: the same range is not asked for twice)
                     const int one = with_truth(t);
                     if (one != RSQ_OK && one != RSQ_ENOSPC) return one;
                     if (one == RSQ_ENOSPC) rc = RSQ_ENOSPC;
+                    t.batch_done = t.sorted && one == RSQ_OK;
                 }
                 return rc;
             };
@@ -819,30 +887,70 @@ int illumina_pe(const Args &a) {
             int rc = calls();
             if (rc == RSQ_ENOSPC) {
                 ok = d1.ensure(grown(l1)) && d2.ensure(grown(l2));
-                for (TruthOut &t : truths) ok = ok && t.text.ensure(grown(t.len));
+                for (TruthOut &t : truths) ok = ok && (t.batch_done || t.text.ensure(grown(t.len)));      // (a finished call's records stay where they are)
                 if (ok) rc = calls();
             }
+            // The FASTQ buffers may have moved: their text is written again by whichever call is repeated.  With the sorted call the only one there is none
+            // to repeat unless it asked for room itself, so nothing is lost.
             ok = ok && check(rc, failed) && (n == 0 || (members(gz1, d1, l1, g1) && members(gz2, d2, l2, g2) && flush_pair(gz1 ? g1 : d1, l1, gz2 ? g2 : d2, l2, f1, f2)));
-            for (TruthOut &t : truths) ok = ok && (n == 0 || push_truth(t));
+            for (TruthOut &t : truths) {
+                ok = ok && ((n == 0 && !t.sorted) || push_truth(t));      // (a sorted call may hand out held records without simulating a pair)
+                t.batch_done = false;
+            }
         };
         // about 12 M pairs per call: large launches keep the persistent read kernel's tail short (one call of 14.5 M pairs runs at 179 M pairs/s, calls of 2.4 M at
         // 154 M), and sparse coverage needs long block ranges
         const double pairs_per_block = (double)info.total_pairs / std::max<uint32_t>(1u, info.total_blocks);
-        const uint32_t step = (uint32_t)std::min(400000.0, std::max(2000.0, 12e6 / std::max(1e-9, pairs_per_block)));
+        uint32_t step = (uint32_t)std::min(400000.0, std::max(2000.0, 12e6 / std::max(1e-9, pairs_per_block)));
+        if (a.has("batchBlocks")) step = (uint32_t)std::max(1, atoi(a.get("batchBlocks").c_str()));      // (the tests make the batches small)
         for (uint32_t lo = 1; ok && lo <= info.total_blocks; lo += step) {
             const uint32_t hi = std::min(info.total_blocks + 1, lo + step);
             uint64_t n = 0;
             batch([&] { return rsq_sim_pairs(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, &n, nullptr, 0, nullptr); },
-                  [&](TruthOut &t) { return t.pairs(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)t.text.p, t.text.cap, &t.len, &n, nullptr, 0, nullptr); }, true,
+                  [&](TruthOut &t) {
+                      uint64_t n_records = 0;
+                      if (t.sorted)
+                          return rsq_sim_pairs_bam_sorted(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)t.text.p, t.text.cap, &t.len, &n, &n_records, nullptr, 0, nullptr);
+                      return t.pairs(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)t.text.p, t.text.cap, &t.len, &n, nullptr, 0, nullptr);
+                  },
+                  true,
                   "Simulation failed", n);
             written += n;
             if (ok && n) INFO("Generated " << written << " read pairs (" << (info.total_pairs ? (written * 100 + info.total_pairs / 2) / info.total_pairs : 0) << "%).");
+        }
+        for (TruthOut &t : truths) {                             // what the sorted run still holds: the last mapped records, then the unmapped ones of the block calls
+            if (!ok || !t.sorted) continue;
+            uint64_t n_mapped = 0, n_unmapped = 0;
+            int rc = rsq_sim_bam_sorted_flush(sim, (char *)t.text.p, t.text.cap, &t.len, &n_mapped, &n_unmapped, nullptr);
+            if (rc == RSQ_ENOSPC && t.text.ensure(t.len + 4096)) rc = rsq_sim_bam_sorted_flush(sim, (char *)t.text.p, t.text.cap, &t.len, &n_mapped, &n_unmapped, nullptr);
+            ok = check(rc, "Sorting the truth alignments failed") && push_truth(t);
+            t.n_no_coor = n_unmapped + 2 * info.adapter_only_pairs;
         }
         for (uint64_t first = 0; ok && first < info.adapter_only_pairs; first += 100000) {       // Simulator.cpp:2359-2382
             const uint64_t n = std::min<uint64_t>(100000, info.adapter_only_pairs - first);
             batch([&] { return rsq_sim_adapter_only_pairs(sim, first, n, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, nullptr); },
                   [&](TruthOut &t) { return t.adapter_only(sim, first, n, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)t.text.p, t.text.cap, &t.len, nullptr); }, false,
                   "Simulation of adapter-only pairs failed", n);
+        }
+    }
+    for (TruthOut &t : truths) {                                 // truth.bam.bai: the block table ends with the end-of-file member
+        if (!ok || !t.sorted) continue;
+        if (!t.cut_member.empty() || !t.members_ok) {
+            ERR("The members of '" << t.path << "' are not whole BGZF blocks.");
+            ok = false;
+            continue;
+        }
+        t.block_u.push_back(t.u_at);
+        t.block_c.push_back(t.c_at);
+        size_t need = 0;
+        rsq_sim_bam_sorted_index(sim, t.block_u.data(), t.block_c.data(), t.block_u.size(), t.n_no_coor, nullptr, 0, &need);
+        std::string bai(need, '\0');
+        ok = check(rsq_sim_bam_sorted_index(sim, t.block_u.data(), t.block_c.data(), t.block_u.size(), t.n_no_coor, &bai[0], need, &need), "BAM index");
+        if (ok) {
+            FILE *f = fopen((t.path + ".bai").c_str(), "wb");
+            ok = f && fwrite(bai.data(), 1, bai.size(), f) == bai.size();
+            if (f) ok = fclose(f) == 0 && ok;
+            if (!ok) ERR("Could not write '" << t.path << ".bai'.");
         }
     }
     trace.at("last text handed to the writers");
@@ -860,7 +968,10 @@ int illumina_pe(const Args &a) {
         ERR("An error occurred in the process: Terminating simulation");
         remove(out1.c_str());
         remove(out2.c_str());
-        for (const TruthOut &t : truths) remove(t.path.c_str());
+        for (const TruthOut &t : truths) {
+            remove(t.path.c_str());
+            if (t.sorted) remove((t.path + ".bai").c_str());
+        }
         return 1;
     }
     INFO("Simulation finished succesfully");
@@ -1081,6 +1192,7 @@ const char *kUsage =
     "Commands:\n"
     "  illuminaPE\t\tsimulates illumina paired-end data from a fitted profile (-s) and a reference (-R)\n"
     "                 \t--truthBam truth.bam: the same records as BAM (BGZF blocks made on the device; unsorted, no index; may be given beside --truthSam; not with -V or --hostGzip, one worker)\n"
+    "                 \t--truthBamSort: with --truthBam, the records sorted by coordinate on the device (@HD SO:coordinate) and the index truth.bam.bai beside the file\n"
     "                 \t--truthSam truth.sam[.gz]: where every read really came from, as SAM records (header, two records per pair in the files' order; not with -V, one worker)\n"
     "  seqToIllumina\t\tapplies illumina quality and error model to input sequences (alias: replaceQuals)\n"
     "                 \t-i in.fa[.gz|.bz2] (stdin) -o out.fq[.gz|.bz2] (stdout) -s profile; --readThreads N, --traceStages;\n"

@@ -29,6 +29,7 @@
 #include "rsq_format.h"
 #include "rsq_sam.h"
 #include "rsq_bam.h"
+#include "rsq_bamsort.h"
 #include "rsq_pack.h"
 #include "rsq_prepass.h"
 #include "rsq_spec.h"
@@ -78,6 +79,15 @@ class DevBuf {
         }
         p_ = nullptr;
         bytes_ = 0;
+    }
+    void reserve_keeping(size_t bytes, size_t keep, hipStream_t st) {      // grow-only, the first `keep` bytes kept: copied on `st`, which is idle afterwards
+        if (bytes <= bytes_) return;
+        DevBuf bigger;
+        bigger.reserve(bytes);
+        if (keep) HIP_CHECK(hipMemcpyAsync(bigger.p_, p_, keep, hipMemcpyDeviceToDevice, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        std::swap(p_, bigger.p_);
+        std::swap(bytes_, bigger.bytes_);
     }
     template <class T>
     T *as() const { return reinterpret_cast<T *>(p_); }
@@ -245,6 +255,21 @@ struct rsq_sim : PrepassSim {
     DevBuf sam_totals, sam_longest;          // rsq_sim_pairs_sam: [sub-ranges + 1] bytes of SAM text in front of a sub-range; the call's longest pair of records
     uint64_t sam_pair_bytes = 1100;          // that of the last call and a few bytes (sam_stage sizes the writer's LDS image with it)
     uint64_t bam_pair_bytes = 700;           // the same for a call that writes BAM records
+    // rsq_sim_bam_sorted_*: a run of calls whose BAM records leave in coordinate order (rsq_bamsort.h)
+    struct BamSorted {
+        bool active = false;
+        uint64_t stream_at = 0;              // the uncompressed offset in the file of the next final record
+        uint32_t next_block = 0;             // where the next call begins (0: the run's first call begins where it likes)
+        uint64_t prev_cut = 0;               // the cut of the call before: no record of a later call lies below it
+        BamSortPlan plan{};
+        DevBuf stage[2], dir[2];             // staging bytes and directory, [held | the call's]; `cur` holds the held ones, the gather moves them to the other
+        int cur = 0;
+        uint64_t n_held = 0, held_bytes = 0;
+        uint64_t call_pairs = 0;             // pairs of the running call's parts so far
+        uint32_t call_parts = 1;             // its sub-ranges (option overlap): the staging buffer grows once, for all of them
+        DevBuf keys[2], idx[2], hist, hist_at, sizes, at, flags, run_of, runs, result, out_of_order, windows, window_first;
+        BamIndexState index;
+    } bam_sorted;
     uint64_t record_text_bytes = 480;        // the same for the seqToIllumina records' text (error_model_text)
     int force_fill_mode = -1;      // RSQ_FILL_MODE=0: every draw in double precision from HBM (tests run both paths)
     // read kernels compiled for this simulator's profile (rsq_spec.h); `specialize`: option specialize when the simulator was created
@@ -660,10 +685,42 @@ struct SamOut {
     size_t cap;
     size_t *len;
     bool bam = false;      // BAM records (rsq_bam.h BamFormat) in place of SAM text (SamFormat): a call launches the kernels of one format
+    bool sorted = false;   // BAM records of a sorted run (rsq_bamsort.h): written to the run's staging buffer, with a directory entry each; dst and cap are not used
 };
 // The truth records of the pairs of reads_stage in one format, behind their text_stage on the same stream (it reads the FASTQ offsets' totals: nothing is written
 // unless all three outputs fit so far).  Offsets continue at sam_totals[part]; where the part ends goes to sam_totals[part + 1].  A format has its own side array,
 // timer keys and image size; sizes, offsets and totals live in the same buffers (a call writes one kind).
+// A sorted run's part (rsq_bamsort.h): its records go to the staging buffer behind the held ones and the parts in front.  The part's bytes are known on the
+// device only and the writer must not run past the buffer, so the host reads them here (the stream is idle afterwards: one wait per part, on a path whose
+// call ends with a wait anyway).  A buffer that has to grow grows with its contents kept, and at once to what the whole call will need if its other parts are
+// like this one, so a call copies what it kept at most once; the next call of the run finds the room.
+static char *sorted_stage_room(rsq_sim &s, uint64_t n_pairs, uint32_t part, hipStream_t st, uint64_t &cap) {
+    rsq_sim::BamSorted &b = s.bam_sorted;
+    uint64_t ends[2];                                                // the bytes of the call's records in front of this part, and with it
+    HIP_CHECK(hipMemcpyAsync(ends, s.sam_totals.as<uint64_t>() + part, 16, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    const uint64_t bytes = b.held_bytes + ends[1] + 32u, entries = b.n_held + 2u * (b.call_pairs + n_pairs);
+    const uint64_t left = b.call_parts > part + 1u ? b.call_parts - (part + 1u) : 0u;          // parts still to come
+    if (bytes > b.stage[b.cur].bytes()) {
+        const uint64_t whole = bytes + (ends[1] - ends[0]) * left;
+        b.stage[b.cur].reserve_keeping(whole + whole / 8u, b.held_bytes + ends[0], st);
+    }
+    if (entries * sizeof(BamDirEntry) > b.dir[b.cur].bytes()) {
+        const uint64_t whole = entries + 2u * n_pairs * left;
+        b.dir[b.cur].reserve_keeping((whole + whole / 8u) * sizeof(BamDirEntry), (b.n_held + 2u * b.call_pairs) * sizeof(BamDirEntry), st);
+    }
+    cap = b.stage[b.cur].bytes() - 32u - b.held_bytes;
+    return b.stage[b.cur].as<char>() + b.held_bytes;
+}
+static void sorted_directory(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, const ReadsDone &rd, const BamPair *side, const uint64_t *offsets, hipStream_t st) {
+    rsq_sim::BamSorted &b = s.bam_sorted;
+    s.timers["bam_sort_keys"].start(st);
+    hipLaunchKernelGGL(k_bam_sort_keys, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, frags, n_pairs, rd.row_order, side, offsets, b.held_bytes,
+                       b.dir[b.cur].as<BamDirEntry>() + b.n_held + 2u * b.call_pairs, s.dev.n_seqs, b.prev_cut, b.plan.pos_bits, b.out_of_order.as<uint32_t>());
+    s.timers["bam_sort_keys"].stop(st);
+    HIP_CHECK(hipGetLastError());
+    b.call_pairs += n_pairs;
+}
 template <class Format>
 static void truth_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_first, const ReadsDone &rd, char *r1, size_t r1_cap, char *r2, size_t r2_cap, const SamOut &sam,
                         uint32_t part, hipStream_t st) {
@@ -676,7 +733,9 @@ static void truth_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uin
     w.off_sam.reserve((n_pairs + 1) * 8);
     side.reserve(n_pairs * sizeof(Pair) + 16);
     uint64_t *totals = s.sam_totals.as<uint64_t>();
-    const uint64_t cap = sam.dst ? sam.cap : 0, cap1 = r1 ? r1_cap : 0, cap2 = r2 ? r2_cap : 0;
+    char *dst = sam.dst;
+    uint64_t cap = sam.dst ? sam.cap : 0;
+    const uint64_t cap1 = r1 ? r1_cap : 0, cap2 = r2 ? r2_cap : 0;
     s.timers[sizes_timer].start(st);
     hipLaunchKernelGGL(k_truth_sizes<Format>, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw, rd.row_order, side.as<Pair>(),
                        w.sam_sizes.as<uint32_t>());
@@ -684,11 +743,14 @@ static void truth_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uin
     exclusive_scan(s, w.sam_sizes.as<uint32_t>(), n_pairs, w.off_sam.as<uint64_t>(), st, totals + part, totals + part + 1);
     hipLaunchKernelGGL(k_max_size, dim3(std::min<uint64_t>(1024, cdiv(n_pairs, 256))), dim3(256), 0, st, w.sam_sizes.as<uint32_t>(), n_pairs, s.sam_longest.as<uint32_t>());
     const uint32_t lds = sam_lds_bytes(bam ? s.bam_pair_bytes : s.sam_pair_bytes, rd.row_order != nullptr);
+    if (sam.sorted) dst = sorted_stage_room(s, n_pairs, part, st, cap);
     s.timers[write_timer].start(st);
     launch_text_waves(k_truth_write<Format, true>, k_truth_write<Format, false>, rd.row_order, dim3(cdiv(n_pairs, kSamPairs)), lds, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw,
-                      side.as<Pair>(), w.off_sam.as<uint64_t>(), sam.dst, cap, w.off_r1.as<uint64_t>() + n_pairs, w.off_r2.as<uint64_t>() + n_pairs, cap1, cap2, rd.row_order, lds);
+                      side.as<Pair>(), w.off_sam.as<uint64_t>(), dst, cap, w.off_r1.as<uint64_t>() + n_pairs, w.off_r2.as<uint64_t>() + n_pairs, cap1, cap2, rd.row_order, lds);
     s.timers[write_timer].stop(st);
     HIP_CHECK(hipGetLastError());
+    if constexpr (bam)
+        if (sam.sorted) sorted_directory(s, frags, n_pairs, rd, side.as<Pair>(), w.off_sam.as<uint64_t>(), st);
 }
 static void sam_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_first, const ReadsDone &rd, char *r1, size_t r1_cap, char *r2, size_t r2_cap, const SamOut &sam,
                       uint32_t part, hipStream_t st) {
@@ -709,6 +771,7 @@ static void enqueue_sam_total(rsq_sim &s, uint32_t parts, hipStream_t text_strea
 static int finish_sam(rsq_sim &s, int rc, const SamOut &sam, size_t r1_len, size_t r2_len) {
     *sam.len = s.mailbox[6];
     if ((uint32_t)s.mailbox[7]) (sam.bam ? s.bam_pair_bytes : s.sam_pair_bytes) = (uint32_t)s.mailbox[7] + 16u;
+    if (sam.sorted) return rc;                                       // the staging buffer always fits; what the caller's must hold is known after the sort (sorted_finish)
     if (rc == RSQ_ENOSPC || (rc == RSQ_OK && (*sam.len > sam.cap || !sam.dst))) {
         g_last_error = "output buffers too small: need " + std::to_string(r1_len) + " and " + std::to_string(r2_len) + " bytes of FASTQ text and " + std::to_string(*sam.len) +
                        (sam.bam ? " of BAM records" : " of SAM text");
@@ -1022,6 +1085,107 @@ static int sim_pairs(rsq_sim &s, uint32_t block_lo, uint32_t block_hi, char *r1,
     return rc;
 }
 
+// The end of a sorted call (rsq_bamsort.h), behind its parts -- or, at the flush, over the held records alone: the sort of the directory's keys, the cut, and,
+// when every buffer of the call fits, the gather into the caller's buffer and the index material.  Until then nothing of the run's state has changed (the
+// held records and their entries lie untouched in front of the call's), so a call that ends with RSQ_ENOSPC can be repeated.  rc: what the parts came to.
+static int sorted_finish(rsq_sim &s, int rc, uint64_t cut, uint32_t block_hi, char *out, size_t cap, size_t *len, uint64_t *n_records, uint64_t *n_mapped, size_t r1_len, size_t r2_len,
+                         hipStream_t st) {
+    rsq_sim::BamSorted &b = s.bam_sorted;
+    const uint64_t n = b.n_held + 2u * b.call_pairs;
+    *len = 0;
+    *n_records = *n_mapped = 0;
+    if (n >= (1ull << 32)) throw Error("more than 2^32 BAM records in one sorted call: use smaller block ranges");
+    if (!n) {
+        if (rc == RSQ_OK) {
+            b.prev_cut = cut;
+            b.next_block = block_hi;
+        }
+        return rc;
+    }
+    s.cur = &s.ws[0];                                                // (the scans' scratch)
+    const BamDirEntry *dir = b.dir[b.cur].as<BamDirEntry>();
+    const uint32_t tiles = (uint32_t)cdiv(n, kBamSortTile), blocks = (uint32_t)cdiv(n, 256);
+    for (int k = 0; k < 2; ++k) {
+        b.keys[k].reserve(n * 8u);
+        b.idx[k].reserve(n * 4u);
+    }
+    b.hist.reserve((size_t)tiles * kBamSortBins * 4u);
+    b.hist_at.reserve(((size_t)tiles * kBamSortBins + 1u) * 8u);
+    b.sizes.reserve(n * 4u);
+    b.at.reserve((n + 1u) * 8u);
+    b.result.reserve(64);
+    int from = 0;
+    s.timers["bam_sort"].start(st);
+    hipLaunchKernelGGL(k_bam_sort_init, dim3(blocks), dim3(256), 0, st, dir, n, b.keys[0].as<uint64_t>(), b.idx[0].as<uint32_t>());
+    for (uint32_t pass = 0; pass < b.plan.passes; ++pass, from ^= 1) {
+        hipLaunchKernelGGL(k_bam_sort_hist, dim3(tiles), dim3(kBamSortBlock), 0, st, b.keys[from].as<uint64_t>(), n, pass, b.plan.pos_bits, b.hist.as<uint32_t>());
+        exclusive_scan(s, b.hist.as<uint32_t>(), (uint64_t)tiles * kBamSortBins, b.hist_at.as<uint64_t>(), st);
+        hipLaunchKernelGGL(k_bam_sort_scatter, dim3(tiles), dim3(kBamSortBlock), 0, st, b.keys[from].as<uint64_t>(), b.idx[from].as<uint32_t>(), n, pass, b.plan.pos_bits,
+                           b.hist_at.as<uint64_t>(), b.keys[from ^ 1].as<uint64_t>(), b.idx[from ^ 1].as<uint32_t>());
+    }
+    const uint64_t *keys = b.keys[from].as<uint64_t>();
+    const uint32_t *idx = b.idx[from].as<uint32_t>();
+    hipLaunchKernelGGL(k_bam_sorted_sizes, dim3(blocks), dim3(256), 0, st, dir, idx, n, b.sizes.as<uint32_t>());
+    exclusive_scan(s, b.sizes.as<uint32_t>(), n, b.at.as<uint64_t>(), st);
+    hipLaunchKernelGGL(k_bam_cut, dim3(1), dim3(1), 0, st, keys, n, cut, bam_unmapped_key(s.dev.n_seqs), b.at.as<uint64_t>(), b.out_of_order.as<uint32_t>(), b.result.as<uint64_t>());
+    s.timers["bam_sort"].stop(st);
+    HIP_CHECK(hipGetLastError());
+    uint64_t r[6];
+    HIP_CHECK(hipMemcpyAsync(r, b.result.as<uint64_t>(), sizeof r, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    const uint64_t n_final = r[0], mapped = r[1], final_bytes = r[2], mapped_bytes = r[3], all_bytes = r[4];
+    if (r[5]) {
+        g_last_error = "sorted BAM: " + std::to_string(r[5]) + " records lie below the cut of the call before or outside their sequence: the stream would not be sorted";
+        return RSQ_EINVAL;
+    }
+    *len = final_bytes;
+    *n_records = n_final;
+    *n_mapped = mapped;
+    if (rc == RSQ_ENOSPC || (rc == RSQ_OK && (final_bytes > cap || (!out && final_bytes)))) {
+        g_last_error = "output buffers too small: need " + std::to_string(r1_len) + " and " + std::to_string(r2_len) + " bytes of FASTQ text and " + std::to_string(final_bytes) +
+                       " of sorted BAM records";
+        return RSQ_ENOSPC;
+    }
+    if (rc != RSQ_OK) return rc;
+    const int other = b.cur ^ 1;
+    const uint64_t n_held = n - n_final, held_bytes = all_bytes - final_bytes;
+    b.stage[other].reserve(held_bytes + 32u);
+    b.dir[other].reserve(n_held * sizeof(BamDirEntry) + 8u);
+    s.timers["bam_gather"].start(st);
+    hipLaunchKernelGGL(k_bam_gather, dim3((uint32_t)cdiv(n, 16)), dim3(256), 0, st, dir, idx, b.at.as<uint64_t>(), n, n_final, b.stage[b.cur].as<char>(), out, b.stage[other].as<char>(),
+                       b.dir[other].as<BamDirEntry>());
+    s.timers["bam_gather"].stop(st);
+    HIP_CHECK(hipGetLastError());
+    if (mapped) {                                                    // the index material of the call's mapped final records
+        b.flags.reserve(mapped * 4u);
+        b.run_of.reserve((mapped + 1u) * 8u);
+        s.timers["bam_index"].start(st);
+        hipLaunchKernelGGL(k_bam_index_flags, dim3((uint32_t)cdiv(mapped, 256)), dim3(256), 0, st, dir, idx, b.at.as<uint64_t>(), mapped, b.stream_at, b.window_first.as<uint64_t>(),
+                           b.windows.as<unsigned long long>(), b.flags.as<uint32_t>());
+        exclusive_scan(s, b.flags.as<uint32_t>(), mapped, b.run_of.as<uint64_t>(), st);
+        uint64_t n_runs = 0;
+        HIP_CHECK(hipMemcpyAsync(&n_runs, b.run_of.as<uint64_t>() + mapped, 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        b.runs.reserve(n_runs * sizeof(BamRunStart));
+        hipLaunchKernelGGL(k_bam_index_runs, dim3((uint32_t)cdiv(mapped, 256)), dim3(256), 0, st, dir, idx, b.at.as<uint64_t>(), mapped, b.stream_at, b.flags.as<uint32_t>(),
+                           b.run_of.as<uint64_t>(), b.runs.as<BamRunStart>());
+        s.timers["bam_index"].stop(st);
+        HIP_CHECK(hipGetLastError());
+        std::vector<BamRunStart> starts(n_runs);
+        HIP_CHECK(hipMemcpyAsync(starts.data(), b.runs.as<BamRunStart>(), n_runs * sizeof(BamRunStart), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        b.index.add_runs(starts.data(), starts.size(), b.stream_at + mapped_bytes);
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    b.cur = other;
+    b.n_held = n_held;
+    b.held_bytes = held_bytes;
+    b.stream_at += final_bytes;
+    b.prev_cut = cut == kBamCutAll ? b.prev_cut : cut;
+    b.next_block = block_hi;
+    return RSQ_OK;
+}
+
 // The reads' bases and qualities as rows of out_stride bytes (word-aligned): sixteen lanes copy a row, a word each per step -- 64 bytes of a row in one store
 // instruction, where a lane per row wrote four bytes into each of 64 rows (10 ms per 8 M records of 150 bases).  Bytes past read_len inside the last word
 // are zero in the raw arrays.
@@ -1286,13 +1450,20 @@ int rsq_ref_sam_header(const rsq_ref *r, char *out, size_t cap, size_t *need) {
     return RSQ_OK;
 }
 
-// the same header in front of the BAM records (rsq_sim_pairs_bam; SAM specification 4.2): magic, the text, the sequences' names and lengths
-int rsq_ref_bam_header(const rsq_ref *r, char *out, size_t cap, size_t *need) {
+// the same header in front of the BAM records (rsq_sim_pairs_bam; SAM specification 4.2): magic, the text, the sequences' names and lengths; coordinate: of the
+// sorted file (rsq_sim_pairs_bam_sorted), whose @HD line says so
+int rsq_ref_bam_header(const rsq_ref *r, char *out, size_t cap, size_t *need) { return rsq_ref_bam_header_so(r, 0, out, cap, need); }
+int rsq_ref_bam_header_so(const rsq_ref *r, int coordinate, char *out, size_t cap, size_t *need) {
     REQUIRE(r && need, "null argument");
     size_t text_len = 0;
     (void)rsq_ref_sam_header(r, nullptr, 0, &text_len);
     std::string text(text_len, '\0'), h = "BAM\1";
     if (const int rc = rsq_ref_sam_header(r, &text[0], text_len, &text_len)) return rc;
+    if (coordinate) {                                                // the same text with another first line
+        const std::string unsorted = "@HD\tVN:1.6\tSO:unsorted\tGO:query\n";
+        REQUIRE(text.compare(0, unsorted.size(), unsorted) == 0, "the SAM header does not begin with the @HD line rsq_ref_bam_header_so replaces");
+        text = "@HD\tVN:1.6\tSO:coordinate\n" + text.substr(unsorted.size());
+    }
     auto put32 = [&](uint32_t v) {
         for (int k = 0; k < 4; ++k) h += (char)((v >> (8 * k)) & 0xFFu);
     };
@@ -1821,6 +1992,114 @@ int rsq_sim_pairs_sam(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1
 int rsq_sim_pairs_bam(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len, char *bam_dev,
                       size_t bam_cap, size_t *bam_len, uint64_t *n_pairs, rsq_fragment *frags_dev, size_t frags_cap, void *stream) {
     return pairs_truth(s, block_lo, block_hi, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, bam_dev, bam_cap, bam_len, n_pairs, frags_dev, frags_cap, stream, true);
+}
+
+// ---- the truth BAM sorted by coordinate (rsq_bamsort.h; include/reseq_amd.h rsq_sim_bam_sorted_*)
+int rsq_sim_bam_sorted_begin(rsq_sim *s, uint64_t first_record_offset) {
+    REQUIRE(s, "null argument");
+    if (!s->prepared || !s->has_ref) {
+        g_last_error = "rsq_sim_prepare with a reference must run before rsq_sim_bam_sorted_begin";
+        return RSQ_ESTATE;
+    }
+    if (truth_refusal(*s, true)) return RSQ_EINVAL;
+    return guard([&] {
+        HIP_CHECK(hipSetDevice(s->device));
+        rsq_sim::BamSorted &b = s->bam_sorted;
+        uint32_t longest = 0;
+        for (const uint32_t l : s->seq_len) longest = std::max(longest, l);
+        b.active = true;
+        b.stream_at = first_record_offset;
+        b.next_block = 0;
+        b.prev_cut = 0;
+        b.plan = bam_sort_plan(s->dev.n_seqs, longest);
+        b.cur = 0;
+        b.n_held = b.held_bytes = b.call_pairs = 0;
+        b.index.begin(s->seq_len);
+        b.window_first.upload(b.index.window_first);
+        b.windows.reserve(b.index.windows.size() * 8u + 8u);
+        HIP_CHECK(hipMemset(b.windows.as<void>(), 0xFF, b.index.windows.size() * 8u));
+        b.out_of_order.reserve(8);
+        b.result.reserve(64);
+        return (int)RSQ_OK;
+    });
+}
+int rsq_sim_pairs_bam_sorted(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len, char *bam_dev,
+                             size_t bam_cap, size_t *bam_len, uint64_t *n_pairs, uint64_t *n_records, rsq_fragment *frags_dev, size_t frags_cap, void *stream) {
+    REQUIRE(s && r1_len && r2_len && bam_len && n_pairs && n_records, "null argument");
+    if (truth_refusal(*s, true)) return RSQ_EINVAL;
+    rsq_sim::BamSorted &b = s->bam_sorted;
+    *r1_len = *r2_len = *bam_len = 0;
+    *n_pairs = *n_records = 0;
+    if (!b.active) {
+        g_last_error = "rsq_sim_bam_sorted_begin must run before rsq_sim_pairs_bam_sorted";
+        return RSQ_ESTATE;
+    }
+    if (const int rc = check_block_range(*s, block_lo, block_hi)) return rc;
+    if (b.next_block && block_lo != b.next_block) {
+        g_last_error = "sorted BAM: the calls of a run are contiguous and rising -- this one must begin at block " + std::to_string(b.next_block) + ", not at " + std::to_string(block_lo);
+        return RSQ_ESTATE;
+    }
+    return guard([&] {
+        HIP_CHECK(hipSetDevice(s->device));
+        const hipStream_t st = (hipStream_t)stream;
+        reset_call_timers(*s);
+        b.call_pairs = 0;
+        b.call_parts = block_hi > block_lo ? pairs_parts(*s, block_hi - block_lo) : 1u;
+        HIP_CHECK(hipMemsetAsync(b.out_of_order.as<uint32_t>(), 0, 4, st));
+        HIP_CHECK(hipStreamSynchronize(st));                         // (a pipelined call's parts run on other streams)
+        size_t unsorted_len = 0;
+        SamOut out{nullptr, 0, &unsorted_len, true, true};
+        const int rc = sim_pairs(*s, block_lo, block_hi, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, n_pairs, frags_dev, frags_cap, st, &out);
+        if (rc != RSQ_OK && rc != RSQ_ENOSPC) return rc;
+        if (rc == RSQ_ENOSPC && !*n_pairs) return rc;                // the fragment buffer was too small: the call ended in the middle of its parts, no size is known yet
+        const uint64_t cut = bam_cut_key(block_hi, s->total_blocks, s->dev.n_seqs, s->block_seq.data(), s->first_block.data(), kBlockSize);
+        uint64_t mapped = 0;
+        return sorted_finish(*s, rc, cut, block_hi, bam_dev, bam_cap, bam_len, n_records, &mapped, *r1_len, *r2_len, st);
+    });
+}
+int rsq_sim_bam_sorted_flush(rsq_sim *s, char *bam_dev, size_t bam_cap, size_t *bam_len, uint64_t *n_mapped, uint64_t *n_unmapped, void *stream) {
+    REQUIRE(s && bam_len && n_mapped && n_unmapped, "null argument");
+    rsq_sim::BamSorted &b = s->bam_sorted;
+    *bam_len = 0;
+    *n_mapped = *n_unmapped = 0;
+    if (!b.active) {
+        g_last_error = "rsq_sim_bam_sorted_begin must run before rsq_sim_bam_sorted_flush";
+        return RSQ_ESTATE;
+    }
+    return guard([&] {
+        HIP_CHECK(hipSetDevice(s->device));
+        const hipStream_t st = (hipStream_t)stream;
+        reset_call_timers(*s);
+        b.call_pairs = 0;
+        HIP_CHECK(hipMemsetAsync(b.out_of_order.as<uint32_t>(), 0, 4, st));
+        uint64_t n_records = 0;
+        const int rc = sorted_finish(*s, RSQ_OK, kBamCutAll, b.next_block, bam_dev, bam_cap, bam_len, &n_records, n_mapped, 0, 0, st);
+        *n_unmapped = n_records - *n_mapped;
+        return rc;
+    });
+}
+int rsq_sim_bam_sorted_index(rsq_sim *s, const uint64_t *block_u, const uint64_t *block_c, size_t n_blocks, uint64_t n_no_coor, char *out, size_t cap, size_t *need) {
+    REQUIRE(s && need && block_u && block_c && n_blocks, "null argument");
+    rsq_sim::BamSorted &b = s->bam_sorted;
+    if (!b.active) {
+        g_last_error = "rsq_sim_bam_sorted_begin must run before rsq_sim_bam_sorted_index";
+        return RSQ_ESTATE;
+    }
+    REQUIRE(block_u[0] == 0 && std::is_sorted(block_u, block_u + n_blocks) && std::is_sorted(block_c, block_c + n_blocks), "the block table begins at offset 0 and rises");
+    for (size_t k = 0; k + 1 < n_blocks; ++k) REQUIRE(block_u[k + 1] - block_u[k] <= 65536, "a BGZF block holds at most 64 KiB: the block table is not this file's");
+    REQUIRE(block_u[n_blocks - 1] >= b.stream_at, "the block table ends in front of the run's last record: its last entry is the end-of-file member");
+    return guard([&] {
+        HIP_CHECK(hipSetDevice(s->device));
+        HIP_CHECK(hipMemcpy(b.index.windows.data(), b.windows.as<void>(), b.index.windows.size() * 8u, hipMemcpyDeviceToHost));
+        const std::string bytes = bam_bai_bytes(b.index, block_u, block_c, n_blocks, n_no_coor);
+        *need = bytes.size();
+        if (!out || cap < bytes.size()) {
+            g_last_error = "index buffer too small: need " + std::to_string(bytes.size()) + " bytes";
+            return (int)RSQ_ENOSPC;
+        }
+        memcpy(out, bytes.data(), bytes.size());
+        return (int)RSQ_OK;
+    });
 }
 
 // ---- a rank's share, generated once and kept (include/reseq_amd.h rsq_sim_job_*)

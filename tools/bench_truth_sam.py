@@ -4,7 +4,10 @@ step, one call per step) through rsq_sim_pairs and through rsq_sim_pairs_sam: pa
 (of the last step), the bytes of the three texts and the two writers' bytes/s.  One JSON line.
 
 --bam: the same through rsq_sim_pairs_bam beside them -- its pairs/s, kernel ms of bam_sizes / bam_write, the bytes per pair of SAM and BAM, and what the device's
-deflater (rsq_sim_gzip_device) makes of both and of the BAM bytes' first 256 MiB against zlib level 1 on those same bytes."""
+deflater (rsq_sim_gzip_device) makes of both and of the BAM bytes' first 256 MiB against zlib level 1 on those same bytes.
+
+--bam --sorted: the sorted call beside them (rsq_sim_bam_sorted_begin + one rsq_sim_pairs_bam_sorted over all blocks, which hands out every mapped record) -- its
+pairs/s, kernel ms of bam_sort_keys / bam_sort / bam_gather / bam_index beside bam_write, and the bytes/s of bam_gather (the bytes it writes; it reads as many)."""
 import json
 import os
 import sys
@@ -17,8 +20,9 @@ sys.path.insert(0, ROOT)
 
 from reseq_amd import api, synth, workloads  # noqa: E402
 
-with_bam = "--bam" in sys.argv
-argv = [a for a in sys.argv[1:] if a != "--bam"]
+with_bam, with_sorted = "--bam" in sys.argv, "--sorted" in sys.argv
+assert with_bam or not with_sorted, "--sorted goes with --bam"
+argv = [a for a in sys.argv[1:] if a not in ("--bam", "--sorted")]
 pairs = int(argv[0]) if len(argv) > 0 else 10_000_000
 steps = int(argv[1]) if len(argv) > 1 else 3
 tmp = tempfile.mkdtemp(prefix="rsq_sam_")
@@ -89,6 +93,21 @@ if with_bam:
         "gzip_device": {"sam": sam_gz, "bam": bam_gz, "sam_ratio": round(sam_gz / ls, 4), "bam_ratio": round(bam_gz / lb, 4), "sam_ms": sam_gz_ms, "bam_ms": bam_gz_ms},
         "bam_first_bytes": {"bytes": head, "gzip_device": head_gz, "zlib_level_1": head_zlib},
     }
+    if with_sorted:
+        def sorted_call():
+            sim.bam_sorted_begin(0)
+            return sim.pairs_bam_sorted_device(lo, hi, r1, r2, bam)
+
+        sorted_s = timed(sorted_call)
+        final_bytes, n_records = sorted_call()[3:5]
+        sorted_kernels = kernels(("fill_reads", "format_write", "bam_sizes", "bam_write", "bam_sort_keys", "bam_sort", "bam_gather", "bam_index"))
+        held_bytes, n_mapped, n_unmapped, rc = sim.bam_sorted_flush_device(None)
+        bam_part.update({
+            "pairs_per_s_bam_sorted": round(n / sorted_s), "ms_per_call_bam_sorted": round(sorted_s * 1e3, 2), "kernels_of_a_sorted_call": sorted_kernels,
+            "sorted_call": {"records": n_records, "bytes": final_bytes, "held_for_the_flush_bytes": held_bytes},
+            "GB_per_s_bam_gather": gbps(final_bytes + held_bytes, sorted_kernels["bam_gather"]["ms"]),
+            "GB_per_s_bam_write_in_the_sorted_call": gbps(lb, sorted_kernels["bam_write"]["ms"]),
+        })
     packed.free()
     bam.free()
 print(json.dumps({
