@@ -435,7 +435,10 @@ int rsq_fasta_count_records(const char *path, uint64_t from, uint64_t to, uint32
  * over a large block range runs as several sub-ranges (blocks are independent, Simulator.cpp:2384-2401) whose sieve / reads / text stages are pipelined on
  * three streams: the time is the SUM over the call's launches of that kernel, rsq_sim_last_kernel_launches says how many there were.
  * names: "sieve" (screen + finish), "sieve_screen", "sieve_emit", "fill_reads", "format_write", "scan"; with variants of any kind also
- * "slot_table" and "variant_templates"; for a profile with tiles "bin_tiles". */
+ * "slot_table" and "variant_templates"; for a profile with tiles "bin_tiles".
+ * Counted, not timed (0 ms): which of two equivalent routes the call's sieve took -- "sieve_gaps_lds" or "sieve_gaps_mem" (the gap walk on LDS copies of its tables,
+ * or on the tables in memory: options sieve_lds, sieve_lds_bytes), and without variants "sieve_tracks" or "sieve_tracks_off" (the cells' surrounding factors from
+ * the tracks kept by the pre-pass, or computed: option sieve_tracks_mb). */
 int rsq_sim_last_kernel_ms(const rsq_sim *s, const char *kernel, double *ms);
 int rsq_sim_last_kernel_launches(const rsq_sim *s, const char *kernel, uint32_t *launches);
 

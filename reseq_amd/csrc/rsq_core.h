@@ -566,11 +566,11 @@ RSQ_HD uint32_t negative_binomial(double p, double r, double probability_chosen)
     }
     return count;
 }
-// :3615-3627 GetFragmentCounts with Reference::Bias (Reference.h:167-169,283-285)
-RSQ_HD uint32_t fragment_counts(const DevSim &S, uint32_t seq, uint32_t fragment_length, uint32_t gc, const uint32_t (&sur_start)[3],
-                                const uint32_t (&sur_end)[3], double probability_chosen) {
+// :3615-3627 GetFragmentCounts with Reference::Bias (Reference.h:167-169,283-285), from the two surrounding factors on: the candidate kernel of the sieve takes
+// them from the kept tracks where it has them (k_surrounding_bias_tracks: surrounding_bias of every position).  The product is general * gc * start * end, in this order.
+RSQ_HD uint32_t fragment_counts_from(const DevSim &S, uint32_t seq, uint32_t fragment_length, uint32_t gc, double start_factor, double end_factor, double probability_chosen) {
     double general = S.ref_seq_bias[seq] * S.insert_lengths_bias[fragment_length];
-    double bias = general * S.gc_bias[gc] * surrounding_bias(S.sur_bias, sur_start) * surrounding_bias(S.sur_bias, sur_end);
+    double bias = general * S.gc_bias[gc] * start_factor * end_factor;
     if (0.0 < bias) {
         double mean = bias * S.bias_normalization;
         double dispersion = get_dispersion(mean, S.dispersion[0], S.dispersion[1]) / S.num_alleles;
@@ -578,6 +578,11 @@ RSQ_HD uint32_t fragment_counts(const DevSim &S, uint32_t seq, uint32_t fragment
         return negative_binomial(mean / (mean + dispersion), dispersion, probability_chosen);
     }
     return 0;
+}
+RSQ_HD uint32_t fragment_counts(const DevSim &S, uint32_t seq, uint32_t fragment_length, uint32_t gc, const uint32_t (&sur_start)[3],
+                                const uint32_t (&sur_end)[3], double probability_chosen) {
+    const double start_factor = surrounding_bias(S.sur_bias, sur_start), end_factor = surrounding_bias(S.sur_bias, sur_end);
+    return fragment_counts_from(S, seq, fragment_length, gc, start_factor, end_factor, probability_chosen);
 }
 
 // ---------------------------------------------------------------------------------- FillRead state machine

@@ -4,7 +4,7 @@
 //   k_methylation_templates, k_variant_templates                one lane per read writes its template before the read kernel runs
 //   ImageSink, image_header, image_line_part, image_record_part what a lane writes into that image: aligned words ORed into zeroed LDS, no control flow per push (host/device)
 //   WaveImage                                                   the frame of the kernels that write text through an LDS image of the wave's byte range (also rsq_sam.h)
-//   k_max_size, k_format_write                                  FASTQ text: one wave per 16 records                 (Simulator.cpp:596-632, a5)
+//   k_format_write                                              FASTQ text: one wave per 16 records                 (Simulator.cpp:596-632, a5)
 //   k_record_text_sizes, k_record_text_waves                    seqToIllumina records: their FASTQ text             (Simulator.cpp:2497-2504)
 #pragma once
 #include <string.h>
@@ -512,13 +512,6 @@ RSQ_HD uint32_t format_lds_bytes(uint64_t record_bytes, bool slots) {
     const uint64_t want = (kFormatRecords * record_bytes + 16u + 127u) & ~(uint64_t)127u;
     const uint32_t image = (uint32_t)(want < kFormatLdsMin ? kFormatLdsMin : want > kFormatLdsMax ? kFormatLdsMax : want);
     return !slots ? image : image + 16u * kFormatRecords < kFormatLdsMax ? image + 16u * kFormatRecords : kFormatLdsMax;
-}
-// the longest of n record sizes (one atomic per wave)
-__global__ void __launch_bounds__(256) k_max_size(const uint32_t *sizes, uint64_t n, uint32_t *longest) {
-    uint32_t m = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) m = max(m, sizes[i]);
-    for (uint32_t d = 32; d; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, (int)d, 64));
-    if ((threadIdx.x & 63u) == 0 && m) atomicMax(longest, m);
 }
 // FASTQ text of the pairs: one wave per 16 consecutive records of one file (grid.y = template segment = output file), through the wave's image.  Four lanes
 // share a record: lanes 0-15 write the id line and the first half of the bases, lanes 16-31 the second half, lanes 32-47 and 48-63 the two halves of the

@@ -47,6 +47,9 @@ struct Options {
     int64_t gzip_route = -1;           // how the device's gzip searches a call's text: -1 the call's sample decides (gz::dense_pays); 0: FASTQ by its lines; 1: the dense route.  The inflated text is the same
     int64_t gzip_stretch = 0;          // > 0: pieces per pass of the device's gzip through its slots (default 8192: 535 MB of text); the members' bytes are the same
     int64_t hiprtc_by_name = 0;        // 1: libhiprtc is searched by name (whatever copy the process finds first, e.g. PyTorch's) instead of the system ROCm's by path; read once, at first use
+    int64_t sieve_lds = 1;             // 1: the sieve's gap walk reads its coverage group's tables from LDS copies (k_sieve_gaps_lds) where they fit; 0: always from memory
+    int64_t sieve_lds_bytes = 0;       // > 0: the LDS the staged gap tables may take (default 64 KB; tests: below the profile's need, so that the walk falls back to memory)
+    int64_t sieve_tracks_mb = 4096;    // the surrounding-bias tracks of the pre-pass (16 bytes per position) stay for the sieve's candidate kernel when they take no more MB than this; 0: never
     int64_t overlap = 0;               // n > 1: rsq_sim_pairs cuts its block range into n sub-ranges whose sieve / reads / text stages are pipelined on three streams
 };
 Options &options();                                               // the process-wide values

@@ -1,6 +1,7 @@
 // rsq_sieve.h -- the sieve: which (start position, fragment length) cells have fragments, and how many (library only; the host emulation runs the per-lane parts):
 //   k_slot_table     variants of any kind: one workgroup per block of start positions
 //   k_sieve_gaps     one lane per start position slot                                  (Simulator.cpp:2249-2357, a6)
+//   k_sieve_gaps_lds the same with the coverage group's gap tables staged in LDS
 //   k_sieve_finish   one lane per cell that passed the zero threshold
 //   k_sieve_emit     one lane per cell with fragments writes its Fragment records
 // The scans between them are rsq_scan.h's.
@@ -33,25 +34,36 @@ RSQ_HD uint32_t site_c1(const SieveSite &site) { return site.seq | (site.sub << 
 // behind cur-1 is the first one with q[len] <= u * q[cur-1] for one uniform u, found by bisection, and its probability_chosen is
 // thr1 + v * (1 - thr1) for a second one -- 1 + passes Philox blocks per start position instead of one per four cells.
 // Draw k of a start position: block (start, c1, k, 1<<28), u = u53(w0, w1), v = u53(w2, w3).  on_pass(length, probability_chosen).
-template <class F>
-RSQ_HD uint32_t sieve_gaps(const DevSim &S, const SieveSite &site, F &&on_pass) {
-    const double *q = S.gap_q + (size_t)site.group * S.insert_to;
-    const uint32_t *seg_end = S.gap_seg_end + (size_t)site.group * S.insert_to;
+// The walk reads three tables of the sequence's coverage group through `tab`: q(len), seg_end(len) and thr1(len) for insert_from <= len < insert_to.
+// GapTables reads them where the pre-pass put them (the host emulation, the oracle port, the device's fallback); k_sieve_gaps_lds hands in its LDS copies.
+struct GapTables {
+    const double *q_;                  // DevSim::gap_q of the group
+    const uint32_t *seg_end_;          // DevSim::gap_seg_end of the group
+    const double *thr_;                // the group's thresholds, [insert_to][2]
+    RSQ_HD double q(uint32_t len) const { return q_[len]; }
+    RSQ_HD uint32_t seg_end(uint32_t len) const { return seg_end_[len]; }
+    RSQ_HD double thr1(uint32_t len) const { return thr_[2u * len + 1u]; }
+};
+RSQ_HD GapTables gap_tables(const DevSim &S, const SieveSite &site) {
+    return GapTables{S.gap_q + (size_t)site.group * S.insert_to, S.gap_seg_end + (size_t)site.group * S.insert_to, site.thr};
+}
+template <class T, class F>
+RSQ_HD uint32_t sieve_gaps_in(const DevSim &S, const SieveSite &site, const T &tab, F &&on_pass) {
     const uint32_t c1 = site_c1(site);
     uint32_t cur = S.insert_from, k = 0, n = 0;
     while (cur < S.insert_to) {
         const Words w = philox(S.seed, site.start, c1, k++, kDomSieve << 28);
-        const uint32_t e = seg_end[cur];
-        const double base = (cur == S.insert_from || seg_end[cur - 1u] == cur) ? 1.0 : q[cur - 1u];      // a segment starts from 1
+        const uint32_t e = tab.seg_end(cur);
+        const double base = (cur == S.insert_from || tab.seg_end(cur - 1u) == cur) ? 1.0 : tab.q(cur - 1u);      // a segment starts from 1
         const double target = u53_to_unit(w.w0, w.w1) * base;
         uint32_t lo = cur, hi = e;                                  // q does not increase inside a segment
         while (lo < hi) {
             const uint32_t mid = (lo + hi) >> 1;
-            if (q[mid] <= target) hi = mid;
+            if (tab.q(mid) <= target) hi = mid;
             else lo = mid + 1u;
         }
         if (lo < e) {
-            const double thr1 = site.thr[2u * lo + 1u];
+            const double thr1 = tab.thr1(lo);
             on_pass(lo, thr1 + u53_to_unit(w.w2, w.w3) * (1 - thr1));
             ++n;
             cur = lo + 1u;
@@ -59,8 +71,25 @@ RSQ_HD uint32_t sieve_gaps(const DevSim &S, const SieveSite &site, F &&on_pass) 
     }
     return n;
 }
+template <class F>
+RSQ_HD uint32_t sieve_gaps(const DevSim &S, const SieveSite &site, F &&on_pass) {
+    return sieve_gaps_in(S, site, gap_tables(S, site), on_pass);
+}
 
-RSQ_HD uint32_t sieve_cell(const DevSim &S, SieveSite &site, uint32_t len, double probability_chosen, uint32_t (&cnt)[2], uint32_t (&strand_of)[2]) {
+// the two surrounding factors of a cell from the reference: the start's surrounding is found once per site
+RSQ_HD void surrounding_factors(const DevSim &S, SieveSite &site, uint32_t end, double &start_factor, double &end_factor) {
+    if (!site.have_start) {
+        surrounding_forward(S.ref_words, site.word_off, site.L, site.start, site.sur_start);
+        site.have_start = true;
+    }
+    uint32_t sur_end[3];
+    surrounding_reverse(S.ref_words, site.word_off, site.L, end - 1u, sur_end);     // :1820-1832
+    start_factor = surrounding_bias(S.sur_bias, site.sur_start);
+    end_factor = surrounding_bias(S.sur_bias, sur_end);
+}
+// factors(site, end, start_factor, end_factor): where the cell's surrounding factors come from
+template <class Factors>
+RSQ_HD uint32_t sieve_cell_with(const DevSim &S, SieveSite &site, uint32_t len, double probability_chosen, uint32_t (&cnt)[2], uint32_t (&strand_of)[2], Factors &&factors) {
     cnt[0] = cnt[1] = 0;
     strand_of[0] = strand_of[1] = 0;
     const double thr0 = site.thr[2u * len], thr1 = site.thr[2u * len + 1u];
@@ -78,21 +107,21 @@ RSQ_HD uint32_t sieve_cell(const DevSim &S, SieveSite &site, uint32_t len, doubl
         strand_of[1] = 1;
         n_chosen = 2;
     }
-    if (!site.have_start) {
-        surrounding_forward(S.ref_words, site.word_off, site.L, site.start, site.sur_start);
-        site.have_start = true;
-    }
-    uint32_t sur_end[3];
-    surrounding_reverse(S.ref_words, site.word_off, site.L, end - 1u, sur_end);     // :1820-1832
+    double start_factor, end_factor;
+    factors(site, end, start_factor, end_factor);
     const uint32_t gc = percent_u32(ref_gc_count_prefix(S.ref_words, S.gc_prefix, site.word_off, site.start, end), len);   // :1858-1873
     uint32_t n_here = 0;
     for (uint32_t j = 0; j < n_chosen; ++j) {
         const double u = j ? u53_to_unit(w2.w2, w2.w3) : u53_to_unit(w2.w0, w2.w1);
         const double adjusted_random = thr0 + u * (1 - thr0);                       // :2322
-        cnt[j] = fragment_counts(S, site.seq, len, gc, site.sur_start, sur_end, adjusted_random);
+        cnt[j] = fragment_counts_from(S, site.seq, len, gc, start_factor, end_factor, adjusted_random);
         n_here += cnt[j];
     }
     return n_here;
+}
+RSQ_HD uint32_t sieve_cell(const DevSim &S, SieveSite &site, uint32_t len, double probability_chosen, uint32_t (&cnt)[2], uint32_t (&strand_of)[2]) {
+    return sieve_cell_with(S, site, len, probability_chosen, cnt, strand_of,
+                           [&S](SieveSite &st, uint32_t end, double &start_factor, double &end_factor) { surrounding_factors(S, st, end, start_factor, end_factor); });
 }
 
 // ---- the cell with variants (substitutions only): every allele is a copy of the packed reference with its substitutions applied, so
@@ -391,6 +420,19 @@ __global__ void __launch_bounds__(256) k_slot_table(DevSim S, uint32_t block_lo,
     }
 }
 
+// one lane's walk: the count of its start position slot, or its candidates from cand_off[slot] on
+template <bool FILL, class T>
+__device__ __forceinline__ void sieve_gaps_lane(const DevSim &S, const SieveSite &site, const T &tab, uint32_t slot, uint32_t *counts, const uint64_t *cand_off, SieveCand *cands,
+                                                uint64_t cand_cap) {
+    if constexpr (FILL) {
+        uint64_t at = cand_off[slot];
+        sieve_gaps_in(S, site, tab, [&](uint32_t len, double probability_chosen) {
+            if (at < cand_cap) cands[at] = SieveCand{slot, len, probability_chosen};
+            ++at;
+        });
+    } else counts[slot] = sieve_gaps_in(S, site, tab, [](uint32_t, double) {});
+}
+
 template <int VM, bool FILL>
 __global__ void __launch_bounds__(kSieveBlock) k_sieve_gaps(DevSim S, uint32_t block_lo, uint32_t block_hi, uint32_t n_slots, uint32_t *counts, const uint64_t *cand_off,
                                                             SieveCand *cands, uint64_t cand_cap, const SlotInfo *slots) {
@@ -402,14 +444,68 @@ __global__ void __launch_bounds__(kSieveBlock) k_sieve_gaps(DevSim S, uint32_t b
         if constexpr (!FILL) counts[slot] = 0;
         return;
     }
-    if constexpr (FILL) {
-        uint64_t at = cand_off[slot];
-        sieve_gaps(S, site, [&](uint32_t len, double probability_chosen) {
-            if (at < cand_cap) cands[at] = SieveCand{slot, len, probability_chosen};
-            ++at;
-        });
-    } else counts[slot] = sieve_gaps(S, site, [](uint32_t, double) {});
+    sieve_gaps_lane<FILL>(S, site, gap_tables(S, site), slot, counts, cand_off, cands, cand_cap);
 }
+
+// The same walk on LDS copies of the group's tables.  A lane's walk is a chain of about fourteen loads per draw, each at the lane's own length: from memory every
+// one of them occupies the CU's vector-memory path for a wave-level load, from LDS a few cycles.  A workgroup stages q, thr1 and seg_end of one coverage group over
+// [insert_from, insert_to) -- 20 bytes per length, dynamic LDS -- and serves kSieveTilesPerGroup consecutive tiles of 256 slots with them; it stages again where a
+// tile begins in a sequence of another group.  Lanes of a tile whose sequence belongs to another group than the tile's first slot (a tile can straddle two
+// sequences) walk the tables in memory, as k_sieve_gaps does.  Draws, bisection and candidate order are sieve_gaps_in's in both.
+constexpr uint32_t kSieveTilesPerGroup = 4;
+constexpr uint32_t kSieveLdsPerLength = 20;
+constexpr size_t kSieveLdsLimit = 64u << 10;                     // what a workgroup can have without asking for more
+struct GapTablesLds {
+    const double *q_, *thr1_;          // [insert_to - insert_from]
+    const uint32_t *seg_end_;
+    uint32_t from;
+    __device__ double q(uint32_t len) const { return q_[len - from]; }
+    __device__ uint32_t seg_end(uint32_t len) const { return seg_end_[len - from]; }
+    __device__ double thr1(uint32_t len) const { return thr1_[len - from]; }
+};
+template <int VM, bool FILL>
+__global__ void __launch_bounds__(kSieveBlock) k_sieve_gaps_lds(DevSim S, uint32_t block_lo, uint32_t block_hi, uint32_t n_slots, uint32_t *counts, const uint64_t *cand_off,
+                                                                SieveCand *cands, uint64_t cand_cap, const SlotInfo *slots) {
+    extern __shared__ double s_gap_tables[];                        // q | thr1 | seg_end
+    const uint32_t from = S.insert_from, n_len = S.insert_to - from;
+    double *s_q = s_gap_tables, *s_thr1 = s_gap_tables + n_len;
+    uint32_t *s_seg_end = reinterpret_cast<uint32_t *>(s_gap_tables + 2u * n_len);
+    const GapTablesLds lds{s_q, s_thr1, s_seg_end, from};
+    const uint32_t n_tiles = (n_slots + kSieveBlock - 1u) / kSieveBlock;
+    const uint32_t tile_lo = blockIdx.x * kSieveTilesPerGroup, tile_hi = tile_lo + kSieveTilesPerGroup < n_tiles ? tile_lo + kSieveTilesPerGroup : n_tiles;
+    uint32_t staged = 0xFFFFFFFFu;                                  // the group whose tables are in LDS; the same in every lane of the workgroup
+    for (uint32_t tile = tile_lo; tile < tile_hi; ++tile) {
+        SieveSite first;
+        init_site_slot<VM, false>(S, block_lo, block_hi, tile * kSieveBlock, first, nullptr, slots);
+        if (first.group != staged) {
+            __syncthreads();                                        // the tile before is walked to its end
+            const GapTables mem = gap_tables(S, first);
+            for (uint32_t i = threadIdx.x; i < n_len; i += kSieveBlock) {
+                s_q[i] = mem.q(from + i);
+                s_thr1[i] = mem.thr1(from + i);
+                s_seg_end[i] = mem.seg_end(from + i);
+            }
+            staged = first.group;
+            __syncthreads();
+        }
+        const uint32_t slot = tile * kSieveBlock + threadIdx.x;
+        if (slot >= n_slots) continue;
+        SieveSite site;
+        init_site_slot<VM, false>(S, block_lo, block_hi, slot, site, nullptr, slots);
+        if (!(site.start < site.L)) {                               // the last block of a sequence is shorter
+            if constexpr (!FILL) counts[slot] = 0;
+        } else if (site.group == staged) sieve_gaps_lane<FILL>(S, site, lds, slot, counts, cand_off, cands, cand_cap);
+        else sieve_gaps_lane<FILL>(S, site, gap_tables(S, site), slot, counts, cand_off, cands, cand_cap);
+    }
+}
+
+// The surrounding factors of every position of [lo, hi) of the concatenated sequences, kept from the pre-pass (k_surrounding_bias_tracks): surrounding_bias itself of the
+// position's start and end surroundings.  Without variants the candidate kernel takes a cell's two factors from them -- two loads that neighbouring lanes make near each
+// other in place of six gathers in the 24 MB sur_bias table and two exp -- and computes them where the cell lies outside (lo == hi: no tracks).
+struct BiasTracks {
+    const double *start_bias, *end_bias;
+    uint64_t lo, hi;
+};
 
 // The cells with fragments go into the hit list.  Their order in the list is free (k_sieve_emit places fragments by the scan of pairs_of), so places are taken with an
 // atomic counter -- ONE reservation per workgroup: a counter bumped once per wave (557 k times per 10 M pairs) is a queue at one L2 channel, about 10 ns per
@@ -418,7 +514,7 @@ __global__ void __launch_bounds__(kSieveBlock) k_sieve_gaps(DevSim S, uint32_t b
 template <int VM, uint32_t CAP = kMaxDevAlleles>
 __global__ void __launch_bounds__(kSieveBlock) k_sieve_finish(DevSim S, uint32_t block_lo, uint32_t block_hi, uint32_t n_slots, const uint64_t *cand_off, const SieveCand *cands,
                                                               uint64_t cand_cap, uint32_t *pairs_of, SieveHit *hits, uint32_t hit_cap, uint32_t *hit_count, const SlotInfo *slots,
-                                                              uint32_t *cell_info) {
+                                                              uint32_t *cell_info, BiasTracks tracks) {
     __shared__ uint32_t s_records, s_base;
     if (threadIdx.x == 0) s_records = 0;
     __syncthreads();
@@ -436,7 +532,13 @@ __global__ void __launch_bounds__(kSieveBlock) k_sieve_finish(DevSim S, uint32_t
         else if constexpr (VM == 1) n_here = sieve_cell_var(S, site, cand.len, cand.probability_chosen, cell);
         else {
             uint32_t cnt[2], strand_of[2];
-            n_here = sieve_cell(S, site, cand.len, cand.probability_chosen, cnt, strand_of);
+            n_here = sieve_cell_with(S, site, cand.len, cand.probability_chosen, cnt, strand_of, [&](SieveSite &st, uint32_t end, double &start_factor, double &end_factor) {
+                const uint64_t at = S.seq_base_off[st.seq] + st.start, at_end = S.seq_base_off[st.seq] + end - 1u;      // k_sum_bias's indices
+                if (at >= tracks.lo && at_end < tracks.hi) {
+                    start_factor = tracks.start_bias[at - tracks.lo];
+                    end_factor = tracks.end_bias[at_end - tracks.lo];
+                } else surrounding_factors(S, st, end, start_factor, end_factor);
+            });
             cell.n = n_here ? 2u : 0u;
             for (uint32_t e = 0; e < 2u; ++e) {
                 cell.cnt[e] = (uint16_t)cnt[e];

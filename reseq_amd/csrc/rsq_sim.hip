@@ -13,6 +13,7 @@
 #include <chrono>
 #include <map>
 #include <thread>
+#include <type_traits>
 #include <memory>
 #include <string>
 #include <utility>
@@ -105,6 +106,7 @@ namespace rsq {
 struct Timer {                                     // HIP events on the stream the kernels are launched on; a call may time several launches (sub-ranges)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     size_t used = 0;
+    size_t marks = 0;                              // launches counted without being timed: which of two routes a call took (rsq_sim_last_kernel_launches)
     Timer() = default;
     Timer(const Timer &) = delete;
     Timer &operator=(const Timer &) = delete;
@@ -114,7 +116,8 @@ struct Timer {                                     // HIP events on the stream t
             (void)hipEventDestroy(e.second);
         }
     }
-    void reset() { used = 0; }
+    void reset() { used = marks = 0; }
+    void mark() { ++marks; }
     void start(hipStream_t st) {
         if (used == events.size()) {
             hipEvent_t a, b;
@@ -136,7 +139,7 @@ struct Timer {                                     // HIP events on the stream t
         }
         return sum;
     }
-    size_t launches() const { return used; }
+    size_t launches() const { return used + marks; }
 };
 
 }  // namespace rsq
@@ -281,6 +284,17 @@ struct rsq_sim : PrepassSim {
     struct ChainBufs {
         DevBuf chains, chunk_chain, used, out[2], changed, list;
     } chain_bufs;
+    // The surrounding-bias tracks of the pre-pass's share, kept for the sieve's candidate kernel (BiasTracks, rsq_sieve.h): they depend on the reference and the
+    // profile's sur_bias alone, so they serve every call until the next pre-pass or reference.  [lo, hi) of the concatenated sequences; lo == hi: none kept.
+    struct SieveTracks {
+        DevBuf start_bias, end_bias;
+        uint64_t lo = 0, hi = 0;
+        void drop() {
+            lo = hi = 0;
+            start_bias.release();
+            end_bias.release();
+        }
+    } sieve_tracks;
 };
 
 static bool fill_is_binned(const rsq_sim &s) { return effective_fill_mask(s.dev.lds.mask, s.force_fill_mode) != 0 && s.dev.lds.binned; }
@@ -320,7 +334,7 @@ struct DevicePrepass : PrepassBackend {
         };
         const uint32_t n_chunks = bias_chunks(plan);
         if (!n_chunks) return;
-        DevBuf d_params, d_chunk_param, d_chunk_ptr, d_sum, d_max, d_start_bias, d_end_bias;
+        DevBuf d_params, d_chunk_param, d_chunk_ptr, d_sum, d_max, own_start_bias, own_end_bias;
         d_params.upload(plan.params);
         d_chunk_param.upload(plan.chunk_param);
         d_chunk_ptr.upload(plan.chunk_ptr);
@@ -336,6 +350,10 @@ struct DevicePrepass : PrepassBackend {
         uint64_t window = kBiasWindow;
         if (s.opt.bias_window > 0) window = (uint64_t)s.opt.bias_window;
         const uint64_t reach = (uint64_t)kBiasBlock * kBiasRun + s.dev.insert_to, track_len = std::min(hi - lo, window) + reach;
+        // without variants, one window over the whole share and within option sieve_tracks_mb: the tracks stay for the sieve (rsq_sim::SieveTracks)
+        s.sieve_tracks.drop();
+        const bool keep = 0 == s.variants_mode && hi - lo <= window && s.opt.sieve_tracks_mb > 0 && track_len * 16 <= ((uint64_t)s.opt.sieve_tracks_mb << 20);
+        DevBuf &d_start_bias = keep ? s.sieve_tracks.start_bias : own_start_bias, &d_end_bias = keep ? s.sieve_tracks.end_bias : own_end_bias;
         d_start_bias.reserve(track_len * 8 + 16);
         d_end_bias.reserve(track_len * 8 + 16);
         lap("track buffers");
@@ -346,6 +364,10 @@ struct DevicePrepass : PrepassBackend {
             hipLaunchKernelGGL(k_sum_bias, dim3(n_chunks), dim3(kBiasBlock), 0, st, s.dev, d_params.as<BiasParam>(), d_chunk_param.as<uint32_t>(), d_chunk_ptr.as<uint32_t>(),
                                d_start_bias.as<double>(), d_end_bias.as<double>(), a, d_sum.as<double>(), d_max.as<double>(), a, b);
             HIP_CHECK(hipGetLastError());
+        }
+        if (keep) {
+            s.sieve_tracks.lo = lo;
+            s.sieve_tracks.hi = std::min<uint64_t>(s.total_ref_size, hi + reach);
         }
         lap("track and sum kernels");
         HIP_CHECK(hipMemcpyAsync(h_sum.data(), d_sum.as<double>(), h_sum.size() * 8, hipMemcpyDeviceToHost, st));
@@ -423,15 +445,21 @@ struct DevicePrepass : PrepassBackend {
 
 // --------------------------------------------------------------------------------------------- hot path
 // out[i] = *init + in[0] + ... + in[i-1] for i = 0 .. n (init nullptr: 0); the total also goes to *total_out if given
-static void exclusive_scan(rsq_sim &s, const uint32_t *in, uint64_t n, uint64_t *out, hipStream_t st, const uint64_t *init = nullptr, uint64_t *total_out = nullptr) {
+// `arrays` (1 or 2) of n elements each in one set of launches; longest (nullptr: not wanted) takes the largest element by atomicMax
+static void exclusive_scans(rsq_sim &s, ScanArrays a, uint32_t arrays, uint64_t n, hipStream_t st, uint32_t *longest = nullptr) {
     const uint32_t tiles = cdiv(n, kScanTile);
-    s.cur->tile_sums.reserve((size_t)(tiles + 1) * 8);
-    s.cur->scan_total.reserve(8);
-    uint64_t *total = total_out ? total_out : s.cur->scan_total.as<uint64_t>();
-    hipLaunchKernelGGL(k_scan_tile_sums, dim3(tiles), dim3(kScanBlock), 0, st, in, n, s.cur->tile_sums.as<uint64_t>());
-    hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(kScanTilesBlock), 0, st, s.cur->tile_sums.as<uint64_t>(), tiles, total, init);
-    hipLaunchKernelGGL(k_scan_apply, dim3(tiles), dim3(kScanBlock), 0, st, in, n, s.cur->tile_sums.as<uint64_t>(), total, out);
+    s.cur->tile_sums.reserve((size_t)arrays * (tiles + 1) * 8);
+    s.cur->scan_total.reserve(16);
+    for (uint32_t i = 0; i < arrays; ++i)
+        if (!a.total[i]) a.total[i] = s.cur->scan_total.as<uint64_t>() + i;
+    uint64_t *tile_sums = s.cur->tile_sums.as<uint64_t>();
+    hipLaunchKernelGGL(k_scan_tile_sums, dim3(tiles, arrays), dim3(kScanBlock), 0, st, a, n, tile_sums, longest);
+    hipLaunchKernelGGL(k_scan_tiles, dim3(arrays), dim3(kScanTilesBlock), 0, st, a, tile_sums, tiles);
+    hipLaunchKernelGGL(k_scan_apply, dim3(tiles, arrays), dim3(kScanBlock), 0, st, a, n, (const uint64_t *)tile_sums);
     HIP_CHECK(hipGetLastError());
+}
+static void exclusive_scan(rsq_sim &s, const uint32_t *in, uint64_t n, uint64_t *out, hipStream_t st, const uint64_t *init = nullptr, uint64_t *total_out = nullptr, uint32_t *longest = nullptr) {
+    exclusive_scans(s, ScanArrays{{in, nullptr}, {out, nullptr}, {init, nullptr}, {total_out, nullptr}}, 1, n, st, longest);
 }
 
 static RawLayout raw_layout(rsq_sim &s, uint64_t n_reads) {
@@ -666,13 +694,14 @@ static void text_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint
     w.off_r2.reserve((n_pairs + 1) * 8);
     uint64_t *totals = s.totals.as<uint64_t>();
     s.timers["scan"].start(st);
-    exclusive_scan(s, w.sizes.as<uint32_t>(), n_pairs, w.off_r1.as<uint64_t>(), st, totals + 2 * part, totals + 2 * (part + 1));
-    exclusive_scan(s, w.sizes.as<uint32_t>() + n_pairs, n_pairs, w.off_r2.as<uint64_t>(), st, totals + 2 * part + 1, totals + 2 * (part + 1) + 1);
+    // both files' record sizes in one set of launches; the call's longest record (the next call's image size, below) comes out of the tile sums' pass
+    exclusive_scans(s, ScanArrays{{w.sizes.as<uint32_t>(), w.sizes.as<uint32_t>() + n_pairs}, {w.off_r1.as<uint64_t>(), w.off_r2.as<uint64_t>()},
+                                  {totals + 2 * part, totals + 2 * part + 1}, {totals + 2 * (part + 1), totals + 2 * (part + 1) + 1}},
+                    2, n_pairs, st, s.longest_record.as<uint32_t>());
     s.timers["scan"].stop(st);
     // the wave's LDS image: sized by the longest record of the call before (the first call takes room for records of 480 bytes); binned rows have a slot per
     // record, each with its own alignment.  This call's longest record goes to totals' last word for the next one.
     const uint32_t lds = format_lds_bytes(s.format_record_bytes, rd.row_order != nullptr);
-    hipLaunchKernelGGL(k_max_size, dim3(std::min<uint64_t>(1024, cdiv(2 * n_pairs, 256))), dim3(256), 0, st, w.sizes.as<uint32_t>(), 2 * n_pairs, s.longest_record.as<uint32_t>());
     s.timers["format_write"].start(st);
     launch_text_waves(k_format_write<true>, k_format_write<false>, rd.row_order, dim3(cdiv(n_pairs, kFormatRecords), 2), lds, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw,
                       w.off_r1.as<uint64_t>(), w.off_r2.as<uint64_t>(), r1, r2, (uint64_t)(r1 ? r1_cap : 0), (uint64_t)(r2 ? r2_cap : 0), fvars, rd.row_order, lds);
@@ -740,8 +769,7 @@ static void truth_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uin
     hipLaunchKernelGGL(k_truth_sizes<Format>, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw, rd.row_order, side.as<Pair>(),
                        w.sam_sizes.as<uint32_t>());
     s.timers[sizes_timer].stop(st);
-    exclusive_scan(s, w.sam_sizes.as<uint32_t>(), n_pairs, w.off_sam.as<uint64_t>(), st, totals + part, totals + part + 1);
-    hipLaunchKernelGGL(k_max_size, dim3(std::min<uint64_t>(1024, cdiv(n_pairs, 256))), dim3(256), 0, st, w.sam_sizes.as<uint32_t>(), n_pairs, s.sam_longest.as<uint32_t>());
+    exclusive_scan(s, w.sam_sizes.as<uint32_t>(), n_pairs, w.off_sam.as<uint64_t>(), st, totals + part, totals + part + 1, s.sam_longest.as<uint32_t>());
     const uint32_t lds = sam_lds_bytes(bam ? s.bam_pair_bytes : s.sam_pair_bytes, rd.row_order != nullptr);
     if (sam.sorted) dst = sorted_stage_room(s, n_pairs, part, st, cap);
     s.timers[write_timer].start(st);
@@ -852,36 +880,52 @@ static void sieve_attempt(rsq_sim &s, SieveRun &r, int attempt, uint64_t *mail, 
     const uint32_t block_lo = r.block_lo, block_hi = r.block_hi;
     const uint64_t n_slots = r.n_slots, cand_cap = r.cand_cap;
     const dim3 ggrid(cdiv(n_slots, kSieveBlock)), gblock(kSieveBlock);
+    // the gap walk on LDS copies of the group's tables where they fit (k_sieve_gaps_lds), else on the tables in memory
+    const size_t lds_bytes = (size_t)(s.dev.insert_to - s.dev.insert_from) * kSieveLdsPerLength;
+    const bool in_lds = s.opt.sieve_lds != 0 && lds_bytes <= (s.opt.sieve_lds_bytes > 0 ? (size_t)s.opt.sieve_lds_bytes : kSieveLdsLimit);
+    const dim3 lgrid(cdiv(ggrid.x, kSieveTilesPerGroup));
+    const SlotInfo *slot_table = r.slot_table;
+    auto gaps = [&](auto vm_tag, auto fill_tag, uint32_t *counts, const uint64_t *cand_off, SieveCand *cands) {
+        constexpr int kVm = decltype(vm_tag)::value;
+        constexpr bool kFill = decltype(fill_tag)::value;
+        if (in_lds)
+            hipLaunchKernelGGL((k_sieve_gaps_lds<kVm, kFill>), lgrid, gblock, lds_bytes, st, s.dev, block_lo, block_hi, (uint32_t)n_slots, counts, cand_off, cands, cand_cap, slot_table);
+        else
+            hipLaunchKernelGGL((k_sieve_gaps<kVm, kFill>), ggrid, gblock, 0, st, s.dev, block_lo, block_hi, (uint32_t)n_slots, counts, cand_off, cands, cand_cap, slot_table);
+    };
+    using Vm0 = std::integral_constant<int, 0>;
+    using Vm2 = std::integral_constant<int, 2>;
     if (!attempt) {
         if (2 == vm) {
             w.slot_table.reserve(n_slots * sizeof(SlotInfo) + 16);
             s.timers["slot_table"].start(st);
             hipLaunchKernelGGL(k_slot_table, dim3(block_hi - block_lo), dim3(256), 0, st, s.dev, block_lo, w.slot_table.as<SlotInfo>());
             s.timers["slot_table"].stop(st);
-            r.slot_table = w.slot_table.as<SlotInfo>();
+            slot_table = r.slot_table = w.slot_table.as<SlotInfo>();
         }
         s.timers["sieve_screen"].start(st);
-        if (2 == vm)
-            hipLaunchKernelGGL((k_sieve_gaps<2, false>), ggrid, gblock, 0, st, s.dev, block_lo, block_hi, (uint32_t)n_slots, w.counts.as<uint32_t>(), (const uint64_t *)nullptr,
-                               (SieveCand *)nullptr, cand_cap, r.slot_table);
-        else
-            hipLaunchKernelGGL((k_sieve_gaps<0, false>), ggrid, gblock, 0, st, s.dev, block_lo, block_hi, (uint32_t)n_slots, w.counts.as<uint32_t>(), (const uint64_t *)nullptr,
-                               (SieveCand *)nullptr, cand_cap, r.slot_table);
+        if (2 == vm) gaps(Vm2{}, std::false_type{}, w.counts.as<uint32_t>(), nullptr, nullptr);
+        else gaps(Vm0{}, std::false_type{}, w.counts.as<uint32_t>(), nullptr, nullptr);
         s.timers["sieve_screen"].stop(st);
         exclusive_scan(s, w.counts.as<uint32_t>(), n_slots, w.offsets.as<uint64_t>(), st);
     }
-    const SlotInfo *slot_table = r.slot_table;
-    if (2 == vm)
-        hipLaunchKernelGGL((k_sieve_gaps<2, true>), ggrid, gblock, 0, st, s.dev, block_lo, block_hi, (uint32_t)n_slots, (uint32_t *)nullptr, w.offsets.as<uint64_t>(),
-                           w.cands.as<SieveCand>(), cand_cap, slot_table);
-    else
-        hipLaunchKernelGGL((k_sieve_gaps<0, true>), ggrid, gblock, 0, st, s.dev, block_lo, block_hi, (uint32_t)n_slots, (uint32_t *)nullptr, w.offsets.as<uint64_t>(),
-                           w.cands.as<SieveCand>(), cand_cap, slot_table);
+    s.timers[in_lds ? "sieve_gaps_lds" : "sieve_gaps_mem"].mark();                    // which walk the call took (rsq_sim_last_kernel_launches)
+    if (2 == vm) gaps(Vm2{}, std::true_type{}, nullptr, w.offsets.as<uint64_t>(), w.cands.as<SieveCand>());
+    else gaps(Vm0{}, std::true_type{}, nullptr, w.offsets.as<uint64_t>(), w.cands.as<SieveCand>());
     const dim3 fgrid(cdiv(cand_cap, kSieveBlock)), fblock(kSieveBlock);
+    // the kept surrounding-bias tracks where they cover every start and end of the call's blocks; else the candidate kernel computes the factors as before
+    BiasTracks tracks{nullptr, nullptr, 0, 0};
+    if (0 == vm && s.sieve_tracks.hi > s.sieve_tracks.lo) {
+        auto global_of_block = [&](uint32_t b) { return s.seq_base_off[s.block_seq[b]] + (uint64_t)(b - s.first_block[s.block_seq[b]]) * kBlockSize; };
+        const uint64_t first = global_of_block(block_lo), last = std::min<uint64_t>(s.total_ref_size, global_of_block(block_hi - 1u) + kBlockSize + s.dev.insert_to);
+        if (first >= s.sieve_tracks.lo && last <= s.sieve_tracks.hi)
+            tracks = BiasTracks{s.sieve_tracks.start_bias.as<double>(), s.sieve_tracks.end_bias.as<double>(), s.sieve_tracks.lo, s.sieve_tracks.hi};
+    }
+    if (0 == vm) s.timers[tracks.hi > tracks.lo ? "sieve_tracks" : "sieve_tracks_off"].mark();      // which of the two the call took (rsq_sim_last_kernel_launches)
 #define RSQ_FINISH(VM, CAP)                                                                                                                                   \
     hipLaunchKernelGGL((k_sieve_finish<VM, CAP>), fgrid, fblock, 0, st, s.dev, block_lo, block_hi, (uint32_t)n_slots, w.offsets.as<uint64_t>(), w.cands.as<SieveCand>(),  \
                        cand_cap, w.pairs_of.as<uint32_t>(), w.hits.as<SieveHit>(), (uint32_t)std::min<uint64_t>(r.hit_cap, 0xFFFFFFFFull), w.hit_count.as<uint32_t>(), slot_table, \
-                       w.cell_info.as<uint32_t>())
+                       w.cell_info.as<uint32_t>(), tracks)
     if (2 == vm && s.num_alleles <= 8) RSQ_FINISH(2, 8);        // few alleles: the cell's (allele, strand) slots stay in registers
     else if (2 == vm) RSQ_FINISH(2, kMaxDevAlleles);
     else if (1 == vm) RSQ_FINISH(1, 8);                         // allele copies exist for at most eight alleles
@@ -1634,6 +1678,7 @@ int rsq_sim_prepare(rsq_sim *s, uint64_t seed, uint64_t num_read_pairs, double c
     return guard([&] {
         HIP_CHECK(hipSetDevice(s->device));
         DevicePrepass be(*s, stream);
+        s->sieve_tracks.drop();
         prepare(*s, s->up, be, seed, num_read_pairs, coverage, ref_bias_mode, record_base_identifier);
         return RSQ_OK;
     });
@@ -1644,6 +1689,7 @@ int rsq_sim_prepare_plan(rsq_sim *s, uint64_t seed, uint64_t num_read_pairs, dou
     REQUIRE(s, "null argument");
     return guard([&] {
         HIP_CHECK(hipSetDevice(s->device));
+        s->sieve_tracks.drop();
         prepare_plan(*s, s->up, seed, num_read_pairs, coverage, ref_bias_mode, record_base_identifier);
         return RSQ_OK;
     });
@@ -1777,6 +1823,7 @@ int rsq_sim_import_reference(rsq_sim *s, const char *path) {
     return guard([&] {
         HIP_CHECK(hipSetDevice(s->device));
         MappedFile m(path);
+        s->sieve_tracks.drop();
         import_reference(*s, s->up, m.data, m.size, path);
         return RSQ_OK;
     });
@@ -2668,11 +2715,10 @@ static int error_model_text(rsq_sim *s, const RawLayout &raw, uint64_t n, const 
     s->cur->off_r1.reserve((n + 1) * 8);
     s->timers["format_write"].start(st);
     hipLaunchKernelGGL(k_record_text_sizes, dim3(cdiv(n, 256)), dim3(256), 0, st, raw, n, ids, s->cur->sizes.as<uint32_t>());
-    exclusive_scan(*s, s->cur->sizes.as<uint32_t>(), n, s->cur->off_r1.as<uint64_t>(), st);
-    // the waves' LDS image is sized by the longest record of the call before (this call's goes to longest_record for the next one)
+    // the waves' LDS image is sized by the longest record of the call before (this call's goes to longest_record for the next one, out of the scan's first pass)
     s->longest_record.reserve(8);
     HIP_CHECK(hipMemsetAsync(s->longest_record.as<uint32_t>(), 0, 4, st));
-    hipLaunchKernelGGL(k_max_size, dim3(std::min<uint64_t>(1024, cdiv(n, 256))), dim3(256), 0, st, s->cur->sizes.as<uint32_t>(), n, s->longest_record.as<uint32_t>());
+    exclusive_scan(*s, s->cur->sizes.as<uint32_t>(), n, s->cur->off_r1.as<uint64_t>(), st, nullptr, nullptr, s->longest_record.as<uint32_t>());
     const uint32_t lds = format_lds_bytes(s->record_text_bytes, raw.order != nullptr);
     launch_text_waves(k_record_text_waves<true>, k_record_text_waves<false>, raw.order, dim3(cdiv(n, kFormatRecords)), lds, st, raw, n, ids, s->cur->off_r1.as<uint64_t>(), text_dev,
                       (uint64_t)text_cap, lds);
