@@ -318,8 +318,8 @@ int rsq_sim_adapter_only_pairs(rsq_sim *s, uint64_t first, uint64_t n, char *r1_
  * aligned base, positive for the mate with the smaller POS (segment 0 on a tie); flags 99 / 147 (strand 0), 83 / 163 (strand 1).  Adapter-only pairs (fragment
  * length 0, and all pairs of rsq_sim_adapter_only_pairs_sam) are unmapped: flags 77 / 141, "*" / 0 fields, SEQ and QUAL as in the FASTQ.
  * rsq_ref_sam_header gives the header.  RSQ_ENOSPC: all three needed sizes are reported; the SAM text is written only if all three texts fit, each FASTQ text as by
- * rsq_sim_pairs.  A simulator whose reference has variants (rsq_ref_read_variants) is refused with RSQ_EINVAL: coordinates through an allele's insertions and
- * deletions are not worked out.  Methylation is fine (only bases change).  Kernel times: "sam_sizes", "sam_write".  rsq_sim_pairs, rsq_sim_adapter_only_pairs and
+ * rsq_sim_pairs.  A simulator whose reference has variants (rsq_ref_read_variants) is refused with RSQ_EINVAL unless rsq_sim_truth_variants (below) has chosen
+ * the record's coordinate system.  Methylation is fine (only bases change).  Kernel times: "sam_sizes", "sam_write".  rsq_sim_pairs, rsq_sim_adapter_only_pairs and
  * the job calls launch neither. */
 int rsq_sim_pairs_sam(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len,
                       char *sam_dev, size_t sam_cap, size_t *sam_len, uint64_t *n_pairs, rsq_fragment *frags_dev, size_t frags_cap, void *stream);
@@ -334,7 +334,7 @@ int rsq_sim_adapter_only_pairs_sam(rsq_sim *s, uint64_t first, uint64_t n, char 
  * gives that ("BAM\1", l_text, the text of rsq_ref_sam_header, n_ref, then l_name, name NUL, l_ref per sequence; the `need` / RSQ_ENOSPC contract of
  * rsq_ref_sam_header), and rsq_sim_gzip_device makes the BGZF blocks of a .bam file from header and records as one byte stream (rsq_gzip_eof_member ends it).
  * RSQ_ENOSPC as above: all three sizes are reported, the records are written only if all three buffers fit.  Refused with RSQ_EINVAL before anything is launched:
- * a reference with variants; a reference name and base identifier with which a read name could exceed 254 characters (l_read_name is a byte); a sequence of more
+ * a reference with variants (unless rsq_sim_truth_variants is set); a reference name and base identifier with which a read name could exceed 254 characters (l_read_name is a byte); a sequence of more
  * than 2^29 bases (the bins' range).  Kernel times: "bam_sizes", "bam_write"; the plain calls and the _sam calls launch neither, these launch neither of the
  * _sam calls' kernels. */
 int rsq_sim_pairs_bam(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len,
@@ -369,6 +369,27 @@ int rsq_sim_pairs_bam_sorted(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, c
                              char *bam_dev, size_t bam_cap, size_t *bam_len, uint64_t *n_pairs, uint64_t *n_records, rsq_fragment *frags_dev, size_t frags_cap, void *stream);
 int rsq_sim_bam_sorted_flush(rsq_sim *s, char *bam_dev, size_t bam_cap, size_t *bam_len, uint64_t *n_mapped, uint64_t *n_unmapped, void *stream);
 int rsq_sim_bam_sorted_index(rsq_sim *s, const uint64_t *block_u, const uint64_t *block_c, size_t n_blocks, uint64_t n_no_coor, char *out, size_t cap, size_t *need);
+
+/* Truth alignments of a reference with variants, in REFERENCE coordinates.  Valid after rsq_sim_create.  on != 0: the three truth calls above, their adapter-only
+ * calls and rsq_sim_bam_sorted_begin accept a simulator whose reference has variants; on == 0 (the default): they refuse it as ever.  A simulator without variants
+ * writes the same bytes and launches the same kernels whatever this is set to.  Allele coordinates are not offered.  The record's rules:
+ *   An allele is the reference with each of its variants at position p replacing base p by var_seq: length 0 deletes the base, 1 substitutes it, n > 1 leaves one
+ * base standing at p followed by n - 1 inserted bases.  Every allele base is of class R(p) (it stands at p) or X(p) (base k >= 1 of the replacement at p).  A
+ * fragment is the allele stretch [hs, hs + len), hs the allele coordinate of (start, start_var_pos); a mate's template part of t template bases is [hs, hs + t)
+ * (forward) or [hs + len - t, hs + len) (reverse).
+ *   Columns, in ascending allele order (the ops in read order, a reverse mate's from the last op down): M on R -> M, M on X -> I, D on R -> D, D on X -> nothing,
+ * I -> I, and in front of an allele base one D per reference position the allele deleted between it and the base before it in the stretch.  Deleted positions
+ * that touch only the outside of the stretch are not part of the alignment.
+ *   CIGAR: equal neighbours merged, D runs at either end dropped, the non-template part ONE S element as ever; it may begin or end with I.
+ *   POS = 1 + the position of the first remaining column that consumes the reference.  A mate without one lies wholly inside the inserted bases of the variant at
+ * p: CIGAR nI and the clip, POS = p + 2 (the base behind the insertion), flagged mapped, 0 reference bases (BAM: bin of max(reference bases, 1)).  (A mate without
+ * template bases stands where its first one would.)
+ *   FLAG, MAPQ, RNEXT, PNEXT as ever, TLEN by the same rule from these POS and last aligned positions; SEQ, QUAL, XC:Z, XE:i unchanged.  QNAME is still the id up
+ * to its first blank: it carries "_allele<a>" when the id does, and the id's end position.  One tag follows XE: XI:i:<n> (BAM: type I), the bases of the
+ * replacement at the fragment's start position that lie in front of the fragment (the id does not tell) -- 0 almost always, the same on both mates.  It is
+ * written by simulators with variants only.  Substitution-only variant sets (allele copies) take the arithmetic of the calls above, with "_allele<a>" and XI:i:0.
+ * BAM's QNAME limit counts "_allele<a>". */
+int rsq_sim_truth_variants(rsq_sim *s, int on);
 
 /* Simulator::ApplyErrorsAndQualityToFastaInput with the FASTA header already parsed (reseq/Simulator.cpp:2403-2512):
  * n records of `read_len` template bases each.  Inputs (device): seqs[n][read_len] base codes 0..3, seg[n] template

@@ -108,6 +108,7 @@ SYMBOLS = {
     "rsq_sim_adapter_only_pairs_sam": (C.c_int, [_vp, _u64, _u64, _vp, _sz, _psz, _vp, _sz, _psz, _vp, _sz, _psz, _vp]),
     "rsq_sim_pairs_bam": (C.c_int, [_vp, _u32, _u32, _vp, _sz, _psz, _vp, _sz, _psz, _vp, _sz, _psz, C.POINTER(_u64), _vp, _sz, _vp]),
     "rsq_sim_adapter_only_pairs_bam": (C.c_int, [_vp, _u64, _u64, _vp, _sz, _psz, _vp, _sz, _psz, _vp, _sz, _psz, _vp]),
+    "rsq_sim_truth_variants": (C.c_int, [_vp, C.c_int]),
     "rsq_sim_bam_sorted_begin": (C.c_int, [_vp, _u64]),
     "rsq_sim_pairs_bam_sorted": (C.c_int, [_vp, _u32, _u32, _vp, _sz, _psz, _vp, _sz, _psz, _vp, _sz, _psz, C.POINTER(_u64), C.POINTER(_u64), _vp, _sz, _vp]),
     "rsq_sim_bam_sorted_flush": (C.c_int, [_vp, _vp, _sz, _psz, C.POINTER(_u64), C.POINTER(_u64), _vp]),
@@ -602,6 +603,10 @@ class Simulator:
         finally:
             for d in (r1, r2, out):
                 d.free()
+
+    def truth_variants(self, on=True):
+        """rsq_sim_truth_variants: the truth calls accept a reference with variants and write their records in reference coordinates (with the XI:i tag)"""
+        _check(lib().rsq_sim_truth_variants(self.h, 1 if on else 0))
 
     def pairs_sam_device(self, block_lo, block_hi, r1, r2, sam, frags=None, stream=None):
         """rsq_sim_pairs_sam into caller-owned DeviceArrays (None: only the sizes).  Returns (n_pairs, len1, len2, sam_len, rc)."""

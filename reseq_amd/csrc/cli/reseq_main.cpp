@@ -66,7 +66,7 @@ const std::map<std::string, std::string> kShort = {{"-j", "threads"}, {"-h", "he
                                                    {"-v", "vcfIn"},   {"-p", "probabilitiesIn"}, {"-P", "probabilitiesOut"}, {"-1", "firstReadsOut"},
                                                    {"-2", "secondReadsOut"}, {"-c", "coverage"}, {"-R", "refSim"}, {"-V", "vcfSim"}, {"-i", "input"}, {"-o", "output"}};
 const std::set<std::string> kFlags = {"help", "version", "noBias", "noTiles", "statsOnly", "tiles", "stopAfterEstimation", "noInDelErrors", "noSubstitutionErrors", "maxLenDeletion", "maxReadLength",
-                                      "dumpArchiveLayout", "traceStages", "hostGzip", "truthBamSort"};
+                                      "dumpArchiveLayout", "traceStages", "hostGzip", "truthBamSort", "truthVariants"};
 
 bool parse(int argc, char **argv, int first, Args &a) {
     for (int i = first; i < argc; ++i) {
@@ -674,8 +674,8 @@ int illumina_pe(const Args &a) {
             ERR("--truthSam: bzip2 output is not supported (write .gz or plain SAM)");
             return 1;
         }
-        if (!vcf_path.empty()) {
-            ERR(t.option << ": truth alignments are not available for a reference with variants (-V)");
+        if (!vcf_path.empty() && !a.has("truthVariants")) {
+            ERR(t.option << ": truth alignments are not available for a reference with variants (-V) unless --truthVariants chooses reference coordinates for them");
             return 1;
         }
         if (bam && a.has("hostGzip")) {
@@ -695,6 +695,10 @@ int illumina_pe(const Args &a) {
         truths.back().sorted = true;
     }
     const bool any_truth = !truths.empty();
+    if (a.has("truthVariants") && !any_truth) {
+        ERR("--truthVariants chooses the coordinates of --truthSam / --truthBam: give one of them as well");
+        return 1;
+    }
     const char *truth_option = any_truth ? truths.front().option : "";
     rsq_profile *prof = nullptr;
     rsq_ref *ref = nullptr;
@@ -766,6 +770,7 @@ int illumina_pe(const Args &a) {
     uint64_t device = 0;                                         // --device D: the one worker's device (with --gpus N the workers take devices 0 .. N - 1)
     if (ok && a.has("device")) ok = parse_u64(a, "device", device);
     ok = ok && check(rsq_sim_create(prof, ref, (int)device, &sim), "Could not set up the simulator");
+    if (ok && a.has("truthVariants")) ok = check(rsq_sim_truth_variants(sim, 1), "--truthVariants");
     trace.at("simulator created");
     if (ok && !sys_write.empty()) {
         INFO("Writing systematic error profile to " << sys_write);
@@ -1191,9 +1196,10 @@ const char *kUsage =
     "Usage:  reseq <command> [options]\n"
     "Commands:\n"
     "  illuminaPE\t\tsimulates illumina paired-end data from a fitted profile (-s) and a reference (-R)\n"
-    "                 \t--truthBam truth.bam: the same records as BAM (BGZF blocks made on the device; unsorted, no index; may be given beside --truthSam; not with -V or --hostGzip, one worker)\n"
+    "                 \t--truthBam truth.bam: the same records as BAM (BGZF blocks made on the device; unsorted, no index; may be given beside --truthSam; with -V only with --truthVariants; not with --hostGzip, one worker)\n"
     "                 \t--truthBamSort: with --truthBam, the records sorted by coordinate on the device (@HD SO:coordinate) and the index truth.bam.bai beside the file\n"
-    "                 \t--truthSam truth.sam[.gz]: where every read really came from, as SAM records (header, two records per pair in the files' order; not with -V, one worker)\n"
+    "                 \t--truthVariants: with -V, --truthSam / --truthBam [--truthBamSort] write their records in reference coordinates (inserted bases as I, deleted ones as D, tag XI:i)\n"
+    "                 \t--truthSam truth.sam[.gz]: where every read really came from, as SAM records (header, two records per pair in the files' order; with -V only with --truthVariants; one worker)\n"
     "  seqToIllumina\t\tapplies illumina quality and error model to input sequences (alias: replaceQuals)\n"
     "                 \t-i in.fa[.gz|.bz2] (stdin) -o out.fq[.gz|.bz2] (stdout) -s profile; --readThreads N, --traceStages;\n"
     "                 \t--inputFrom / --inputTo BYTE, --firstRecord K: a share of a plain input (python -m reseq_amd.simulate seqToIllumina works them out)\n"

@@ -17,6 +17,7 @@
 // output, whatever read_len & 1: an odd length leaves the last low nibble 0 in either orientation.
 //
 // Per lane, host and device (tests/hostemu/truth_trial.h runs them on the CPU): bam_record_size, bam_fixed, bam_cigar, bam_seq, bam_qual, bam_tags, bam_record, bam_mate.
+// BamVarFormat (the end of this file) is the same encoding of SamVarFormat's record, for a reference with variants: "XI" 'I' u32 follows XE.
 // BamFormat makes them a format of rsq_sam.h: its kernels (k_truth_sizes, k_truth_write), frame and fallback are that file's, with a side array of BAM's own --
 // records are not word-aligned, the frame handles that as it does for text.  Not part of what hiprtc compiles for a profile (rsq_spec.h): nothing of the read
 // kernel's text includes this file.
@@ -85,8 +86,8 @@ RSQ_HD uint32_t bam_record_size(const ReadMeta &m, uint32_t l_read_name, uint32_
 
 // block_size and the 32 bytes of fixed fields: nine words
 template <class Sink>
-RSQ_HD void bam_fixed(const Fragment &f, const ReadMeta &m, const SamMate &w, const SamAlign &a, uint32_t l_read_name, uint32_t n_cigar, uint32_t block_size, Sink &t) {
-    const uint32_t none = 0xFFFFFFFFu, span = (uint32_t)w.t - w.lead - w.trail;
+RSQ_HD void bam_fixed_span(const Fragment &f, const ReadMeta &m, uint32_t span, const SamAlign &a, uint32_t l_read_name, uint32_t n_cigar, uint32_t block_size, Sink &t) {
+    const uint32_t none = 0xFFFFFFFFu;
     const uint32_t ref_id = a.mapped ? f.seq : none, pos = a.mapped ? a.pos - 1u : none, pnext = a.mapped ? a.pnext - 1u : none;
     const uint32_t bin = a.mapped ? bam_reg2bin(pos, pos + (span ? span : 1u)) : kBamUnmappedBin, mapq = a.mapped ? 60u : 0u;
     t.bytes(block_size, 4u);
@@ -98,6 +99,10 @@ RSQ_HD void bam_fixed(const Fragment &f, const ReadMeta &m, const SamMate &w, co
     t.bytes(ref_id, 4u);
     t.bytes(pnext, 4u);
     t.bytes((uint32_t)a.tlen, 4u);
+}
+template <class Sink>
+RSQ_HD void bam_fixed(const Fragment &f, const ReadMeta &m, const SamMate &w, const SamAlign &a, uint32_t l_read_name, uint32_t n_cigar, uint32_t block_size, Sink &t) {
+    bam_fixed_span(f, m, (uint32_t)w.t - w.lead - w.trail, a, l_read_name, n_cigar, block_size, t);
 }
 
 // four base codes, one per byte (0..3 ACGT, 4 N) -> their 4-bit codes, one per byte; complement: of the complementary bases
@@ -190,6 +195,7 @@ RSQ_HD BamMate bam_mate(const DevSim &S, const NameTable &names, bool has_f, con
 
 // BAM records as a format (rsq_sam.h states what a format is)
 struct BamFormat {
+    static constexpr bool kVariants = false;
     using Mate = BamMate;
     using Pair = BamPair;
     static RSQ_HD const SamMate &walk(const Mate &e) { return e.w; }
@@ -213,6 +219,66 @@ struct BamFormat {
     static RSQ_HD uint32_t record(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &seq,
                                   const WordColumn &qual, const WordColumn &ops, const Mate &e, const SamAlign &a, P dst) {
         return bam_record(S, names, has_f, f, adapter_only_number, m, seq, qual, ops, e, a, dst);
+    }
+};
+
+// ------------------------------------------------------------------------------------------------ a reference with variants (rsq_sam.h SamVarFormat)
+// The same re-encoding of the same record: POS, the bin and the CIGAR's words come from the variant entry, the QNAME carries the id's "_allele<a>" and end position,
+// and "XI" 'I' u32 follows XE.
+struct BamVarMate {
+    SamVarMate v;              // v.w.bytes: of the mate's BAM record, its block_size field included
+    uint16_t n_cigar;
+    uint16_t l_read_name;
+    uint32_t pad;
+};
+static_assert(sizeof(BamVarMate) == 40, "the side array's entry");
+struct BamVarPair {
+    BamVarMate mate[2];
+};
+constexpr uint32_t kBamVarTag = 7u;                                     // "XI" 'I' u32
+struct BamVarFormat {
+    static constexpr bool kVariants = true;
+    using Mate = BamVarMate;
+    using Pair = BamVarPair;
+    static RSQ_HD const SamVarMate &var(const Mate &e) { return e.v; }
+    static RSQ_HD uint32_t bytes(const Mate &e) { return e.v.w.bytes; }
+    static RSQ_HD Mate mate(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, const SamVarId &id, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &ops,
+                            const SamVarMate &w, uint32_t n_cigar, const SamAlign &a) {
+        Mate b{};
+        b.v = w;
+        b.n_cigar = (uint16_t)(w.w.pad ? (a.mapped ? n_cigar : 0u) : bam_cigar_ops(ops, m, w.w, a));
+        b.l_read_name = (uint16_t)(sam_qname_size_at(S, names, has_f, f, id.end, id.allele != 0u, adapter_only_number, m) + 1u);
+        b.v.w.bytes = bam_record_size(m, b.l_read_name, b.n_cigar) + kBamVarTag;
+        return b;
+    }
+    template <class Sink>
+    static RSQ_HD void head(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, const SamVarId &id, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &seq,
+                            const WordColumn &ops, const Mate &e, const SamAlign &a, Sink &t) {
+        bam_fixed_span(f, m, e.v.ref_bases, a, e.l_read_name, e.n_cigar, e.v.w.bytes - 4u, t);
+        sam_qname_at(S, names, has_f, f, id.end, id.allele != 0u, adapter_only_number, m, t);
+        t.ch(0);
+        if (a.mapped) {
+            BamCigarWords<Sink> c{t};
+            sam_var_cigar(S, f, ops, m, e.v, a.reverse != 0u, c);
+        }
+        bam_seq(seq, m.read_len, a.reverse != 0u, t);
+    }
+    template <class Sink>
+    static RSQ_HD void tail(const DevSim &S, const ReadMeta &m, const SamVarId &id, const WordColumn &qual, const WordColumn &ops, const SamAlign &a, Sink &t) {
+        bam_qual(qual, m.read_len, a.reverse != 0u, S.phred_offset, t);
+        bam_tags(m, ops, t);
+        t.bytes(chars4('X', 'I', 'I'), 3u);
+        t.bytes(id.xi, 4u);
+    }
+    static RSQ_HD uint32_t tail_at(const Mate &e, const ReadMeta &m, const SamVarId &) { return e.v.w.bytes - bam_tags_size(m) - kBamVarTag - m.read_len; }
+    template <class P>
+    static RSQ_HD uint32_t record(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, const SamVarId &id, uint64_t adapter_only_number, const ReadMeta &m,
+                                  const WordColumn &seq, const WordColumn &qual, const WordColumn &ops, const Mate &e, const SamAlign &a, P dst) {
+        WordSinkT<P> t(dst);
+        head(S, names, has_f, f, id, adapter_only_number, m, seq, ops, e, a, t);
+        tail(S, m, id, qual, ops, a, t);
+        t.finish();
+        return t.n;
     }
 };
 

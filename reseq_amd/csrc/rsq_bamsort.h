@@ -4,12 +4,14 @@
 // Why a call can hand out part of the order before the run ends: block b of sequence i covers the start positions [(b - first_block[i]) * kBlockSize, + kBlockSize),
 // a forward mate lies at start + dL, a reverse mate at start + len - t + dL with t <= len (the template part of a read is not longer than its fragment), so every
 // record of a call over [block_lo, block_hi) and of every later call has a key >= cut(block_lo) = (block_seq[block_lo], (block_lo - first_block) * kBlockSize).
+// The same holds for a reference with variants (BamVarFormat, reference coordinates): every base of a fragment's allele stretch stands at or behind the start
+// position, and a position the allele deleted inside the stretch lies behind the base in front of it, so POS - 1 >= start for both mates.
 // After sorting, what lies below cut(block_hi) is FINAL and goes to the caller; the rest is HELD for the next call -- the longest fragment times the coverage.
 // k_bam_sort_keys counts records below the cut of the call before (and positions the sort's digits do not cover): such a call fails instead of writing a file
 // that is silently unsorted.
 //
-// A call: k_truth_write<BamFormat> (unchanged) writes into a staging buffer [held records | this call's records in pair order]; k_bam_sort_keys appends a
-// directory entry per record (key, staging offset, size, reference bases) from the side entries and sam_align -- no record is read again; held records keep
+// A call: k_truth_write<BamFormat> (or <BamVarFormat>) writes into a staging buffer [held records | this call's records in pair order]; k_bam_sort_keys appends a
+// directory entry per record (key, staging offset, size, reference bases) from the side entries and sam_align (with variants: from the entries alone) -- no record is read again; held records keep
 // theirs, in front, so that ties fall in the order of the unsorted stream.  The sort is an LSD radix sort of (key, index) pairs over the significant bits only
 // (bits(n_seqs) + bits(longest sequence)), 8 bits a pass: k_bam_sort_hist (per-workgroup digit counts, digit-major), the library's exclusive scan, k_bam_sort_scatter
 // (stable rank inside the workgroup from wave ballots and per-wave counters: no place is ever taken from the arrival order of an atomic).  k_bam_cut finds the final
@@ -79,6 +81,17 @@ RSQ_HD BamDirEntry bam_dir_entry(const Fragment &f, uint32_t seg, const BamPair 
     e.off = pair_off + (seg ? p.mate[0].w.bytes : 0u);
     e.size = m.w.bytes;
     e.span = a.mapped ? (span ? span : 1u) : 0u;
+    return e;
+}
+// ... of a reference with variants (BamVarFormat): POS and the reference bases are the entry's
+RSQ_HD BamDirEntry bam_dir_entry(const Fragment &f, uint32_t seg, const BamVarPair &p, uint64_t pair_off, uint32_t n_seqs) {
+    const bool mapped = f.len != 0u;
+    const SamVarMate &m = p.mate[seg].v;
+    BamDirEntry e;
+    e.key = mapped ? bam_sort_key(f.seq, m.pos) : bam_unmapped_key(n_seqs);
+    e.off = pair_off + (seg ? p.mate[0].v.w.bytes : 0u);
+    e.size = m.w.bytes;
+    e.span = mapped ? (m.ref_bases ? m.ref_bases : 1u) : 0u;
     return e;
 }
 // what k_bam_sort_keys counts: a mapped record below the cut of the call before, or at a position the digits do not cover
@@ -210,13 +223,14 @@ inline std::string bam_bai_bytes(const BamIndexState &x, const uint64_t *block_u
 
 #if RSQ_DEVICE_BUILD
 // One lane per raw row pair: both mates' directory entries, at dir[2 * pair + segment] (pair order, whatever the rows' order); counts what is out of order
-__global__ void __launch_bounds__(256) k_bam_sort_keys(const Fragment *frags, uint64_t n_pairs, const uint32_t *perm, const BamPair *side, const uint64_t *offsets, uint64_t stage_base,
+template <class Pair>
+__global__ void __launch_bounds__(256) k_bam_sort_keys(const Fragment *frags, uint64_t n_pairs, const uint32_t *perm, const Pair *side, const uint64_t *offsets, uint64_t stage_base,
                                                        BamDirEntry *dir, uint32_t n_seqs, uint64_t prev_cut, uint32_t pos_bits, uint32_t *out_of_order) {
     const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= n_pairs) return;
     const uint64_t pair = perm ? perm[row] : row;
     const Fragment f = frags[pair];
-    const BamPair p = side[row];
+    const Pair p = side[row];
     const uint64_t at = stage_base + offsets[pair];
     uint32_t bad = 0;
     for (uint32_t seg = 0; seg < 2u; ++seg) {

@@ -11,13 +11,16 @@
 // last op down, its bases are the reverse complement, its qualities reversed.  Adapter-only pairs are unmapped (flags 77 / 141).
 //
 // Per lane, host and device (tests/hostemu/truth_trial.h runs them on the CPU): sam_walk, sam_align, sam_cigar, RowRound, sam_line, sam_record_size, sam_record.
+// For a reference with variants (rsq_sim_truth_variants; the second half of this file, tests/hostemu/truth_var_trial.cpp): AlleleCursor, sam_var_walk, sam_var_columns,
+// sam_var_cigar, sam_var_align -- the record in reference coordinates, SamVarFormat (BamVarFormat in rsq_bam.h).
 //
 // A truth-record FORMAT is a type of static members (SamFormat below, BamFormat in rsq_bam.h): the side array's entry per mate (Mate; Pair holds a row's two,
 // one load), walk(entry) and bytes(entry), mate(...) -- the entry from a walk and an alignment --, head(..., sink) -- everything in front of QUAL --,
 // tail(..., sink) -- QUAL and the tags --, tail_at(entry, meta), the offset at which the tail begins, and record(..., dst), the whole record through one sink
 // (sam_record, bam_record: the straight-to-HBM fallback).  Everything that is not a record's bytes is written once over a format: the kernels k_truth_sizes<Format> (one lane per pair: both
 // mates' entries into the side array, the pair's bytes) and k_truth_write<Format, PERM> (one wave per 16 pairs, four lanes a pair, through the wave's LDS image,
-// WaveImage in rsq_format.h).  Not part of what hiprtc compiles for a profile (rsq_spec.h): nothing of the read kernel's text includes this file.
+// WaveImage in rsq_format.h).  A format with kVariants has the same members with the FragmentVar's part (SamVarId) among their arguments, and its alignment comes from the
+// entries (sam_var_align): the two kernels branch on it at compile time.  Not part of what hiprtc compiles for a profile (rsq_spec.h): nothing of the read kernel's text includes this file.
 #pragma once
 #include "rsq_format.h"
 
@@ -140,20 +143,12 @@ struct SamAlign {
     int32_t tlen;
     uint32_t mapped, reverse;
 };
-RSQ_HD SamAlign sam_align(bool has_f, const Fragment &f, uint32_t seg, const SamMate &w0, const SamMate &w1) {
+// ... from both mates' POS and last aligned position (1-based; a mate without reference bases: last = pos - 1)
+RSQ_HD SamAlign sam_align_at(bool has_f, const Fragment &f, uint32_t seg, const int32_t (&pos)[2], const int32_t (&last)[2]) {
     SamAlign a{};
     if (!has_f || !f.len) {                                             // adapter-only: unmapped
         a.flag = seg ? 141u : 77u;
         return a;
-    }
-    const uint32_t end = f.start + f.len;
-    int32_t pos[2], last[2];
-    for (uint32_t s = 0; s < 2u; ++s) {
-        const SamMate &w = s ? w1 : w0;
-        const bool rev = s != f.strand;                                 // fragment_src (rsq_reads.h): src.reverse = seg != f.strand
-        const uint32_t d_left = rev ? w.trail : w.lead, d_right = rev ? w.lead : w.trail;
-        pos[s] = (int32_t)((rev ? end - w.t : f.start) + 1u + d_left);
-        last[s] = pos[s] + (int32_t)((uint32_t)w.t - d_left - d_right) - 1;
     }
     const uint32_t o = seg ^ 1u;
     const bool rev = seg != f.strand;
@@ -167,16 +162,32 @@ RSQ_HD SamAlign sam_align(bool has_f, const Fragment &f, uint32_t seg, const Sam
     a.tlen = leftmost ? span : -span;
     return a;
 }
+RSQ_HD SamAlign sam_align(bool has_f, const Fragment &f, uint32_t seg, const SamMate &w0, const SamMate &w1) {
+    const uint32_t end = f.start + f.len;
+    int32_t pos[2], last[2];
+    for (uint32_t s = 0; s < 2u; ++s) {
+        const SamMate &w = s ? w1 : w0;
+        const bool rev = s != f.strand;                                 // fragment_src (rsq_reads.h): src.reverse = seg != f.strand
+        const uint32_t d_left = rev ? w.trail : w.lead, d_right = rev ? w.lead : w.trail;
+        pos[s] = (int32_t)((rev ? end - w.t : f.start) + 1u + d_left);
+        last[s] = pos[s] + (int32_t)((uint32_t)w.t - d_left - d_right) - 1;
+    }
+    return sam_align_at(has_f, f, seg, pos, last);
+}
 
-// QNAME: the id line of format_header (rsq_text.h) without '@', up to its first blank
+// QNAME: the id line of format_header (rsq_text.h) without '@', up to its first blank.  `end`: the id's end position; allele: the id carries "_allele<a>" (both
+// differ from the fragment's own only for a reference with variants, SamVarFormat below)
 template <class Sink>
-RSQ_HD void sam_qname(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, Sink &t) {
+RSQ_HD void sam_qname_at(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint32_t end, bool allele, uint64_t adapter_only_number, const ReadMeta &m, Sink &t) {
     t.str(names.base_identifier, names.base_len);
     if (has_f) {
-        const uint32_t end = f.start + f.len;
         t.num(f.block);
         t.ch('_');
         t.num(f.number);
+        if (allele) {
+            t.str("_allele", 7);
+            t.num((uint32_t)f.allele);
+        }
         t.ch(':');
         t.num(f.strand ? end : f.start + 1u);
         t.ch(':');
@@ -193,21 +204,26 @@ RSQ_HD void sam_qname(const DevSim &S, const NameTable &names, bool has_f, const
     t.num((uint32_t)S.tiles[m.tile_id]);
     t.str(":1337:1337", 10);
 }
-RSQ_HD uint32_t sam_qname_size(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m) {
+RSQ_HD uint32_t sam_qname_size_at(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint32_t end, bool allele, uint64_t adapter_only_number, const ReadMeta &m) {
     uint32_t n = names.base_len + 1u + digits_u32(S.tiles[m.tile_id]) + 10u;
     if (has_f) {
-        const uint32_t end = f.start + f.len;
         n += digits_u32(f.block) + 1u + digits_u32(f.number) + 1u + digits_u32(f.start + 1u) + 1u + (names.name_ptr[f.seq + 1] - names.name_ptr[f.seq]) + 1u + digits_u32(end);
+        if (allele) n += 7u + digits_u32(f.allele);
     } else n += 2u + digits_u64(adapter_only_number) + 12u;
     return n;
 }
+template <class Sink>
+RSQ_HD void sam_qname(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, Sink &t) {
+    sam_qname_at(S, names, has_f, f, f.start + f.len, false, adapter_only_number, m, t);
+}
+RSQ_HD uint32_t sam_qname_size(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m) {
+    return sam_qname_size_at(S, names, has_f, f, f.start + f.len, false, adapter_only_number, m);
+}
 RSQ_HD uint32_t sam_tlen_chars(int32_t v) { return v < 0 ? 1u + digits_u32((uint32_t)-(int64_t)v) : digits_u32((uint32_t)v); }
 
-// the record's three stretches: everything in front of SEQ (with its tab) ...
+// the record's three stretches: everything in front of SEQ (with its tab) -- QNAME, the fields up to the CIGAR, the CIGAR, the fields behind it -- ...
 template <class Sink>
-RSQ_HD void sam_head(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &ops, const SamMate &w,
-                     const SamAlign &a, Sink &t) {
-    sam_qname(S, names, has_f, f, adapter_only_number, m, t);
+RSQ_HD void sam_head_front(const NameTable &names, const Fragment &f, const SamAlign &a, Sink &t) {
     t.ch('\t');
     t.num(a.flag);
     t.ch('\t');
@@ -216,23 +232,38 @@ RSQ_HD void sam_head(const DevSim &S, const NameTable &names, bool has_f, const 
         t.ch('\t');
         t.num(a.pos);
         t.str("\t60\t", 4);
-        sam_cigar(ops, m, w, a.reverse != 0u, t);
-        t.str("\t=\t", 3);
-        t.num(a.pnext);
-        t.ch('\t');
-        if (a.tlen < 0) {
-            t.ch('-');
-            t.num((uint32_t)-(int64_t)a.tlen);
-        } else t.num((uint32_t)a.tlen);
-        t.ch('\t');
     } else t.str("*\t0\t0\t*\t*\t0\t0\t", 14);
 }
-RSQ_HD uint32_t sam_head_size(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, const SamMate &w, const SamAlign &a) {
-    uint32_t n = sam_qname_size(S, names, has_f, f, adapter_only_number, m) + 1u + digits_u32(a.flag) + 1u;
-    if (a.mapped)
-        n += (names.name_ptr[f.seq + 1] - names.name_ptr[f.seq]) + 1u + digits_u32(a.pos) + 4u + w.cigar_chars + 3u + digits_u32(a.pnext) + 1u + sam_tlen_chars(a.tlen) + 1u;
+template <class Sink>
+RSQ_HD void sam_head_back(const SamAlign &a, Sink &t) {
+    t.str("\t=\t", 3);
+    t.num(a.pnext);
+    t.ch('\t');
+    if (a.tlen < 0) {
+        t.ch('-');
+        t.num((uint32_t)-(int64_t)a.tlen);
+    } else t.num((uint32_t)a.tlen);
+    t.ch('\t');
+}
+template <class Sink>
+RSQ_HD void sam_head(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &ops, const SamMate &w,
+                     const SamAlign &a, Sink &t) {
+    sam_qname(S, names, has_f, f, adapter_only_number, m, t);
+    sam_head_front(names, f, a, t);
+    if (a.mapped) {
+        sam_cigar(ops, m, w, a.reverse != 0u, t);
+        sam_head_back(a, t);
+    }
+}
+// (without the QNAME's characters)
+RSQ_HD uint32_t sam_head_fields_size(const NameTable &names, const Fragment &f, uint32_t cigar_chars, const SamAlign &a) {
+    uint32_t n = 1u + digits_u32(a.flag) + 1u;
+    if (a.mapped) n += (names.name_ptr[f.seq + 1] - names.name_ptr[f.seq]) + 1u + digits_u32(a.pos) + 4u + cigar_chars + 3u + digits_u32(a.pnext) + 1u + sam_tlen_chars(a.tlen) + 1u;
     else n += 14u;
     return n;
+}
+RSQ_HD uint32_t sam_head_size(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, const SamMate &w, const SamAlign &a) {
+    return sam_qname_size(S, names, has_f, f, adapter_only_number, m) + sam_head_fields_size(names, f, w.cigar_chars, a);
 }
 // ... SEQ or QUAL (no tab, no line end): the row's words as they lie, or from the last one down -- a read length that is no multiple of four takes every output
 // word from two neighbours --, bytes reversed; bases as letters (reverse: the complement's), qualities moved from the profile's offset to Phred+33
@@ -324,6 +355,7 @@ RSQ_HD uint32_t sam_record(const DevSim &S, const NameTable &names, bool has_f, 
 
 // SAM text as a format (the header comment states what a format is); an entry is the walk itself, with the record's bytes
 struct SamFormat {
+    static constexpr bool kVariants = false;
     using Mate = SamMate;
     using Pair = SamPair;
     static RSQ_HD const SamMate &walk(const Mate &e) { return e; }
@@ -354,12 +386,302 @@ struct SamFormat {
     }
 };
 
+// ------------------------------------------------------------------------------------------------ a reference with variants (rsq_sim_truth_variants)
+// The same record in REFERENCE coordinates (DESIGN.md 4.8 states the rules).  A mate's template part is a stretch of its ALLELE's sequence (rsq_variants.h): the
+// forward mate's begins at the allele coordinate of (start, start variant), the reverse mate's ends where (end position, EndVariant) points, exactly as
+// allele_template places them.  Every allele base either stands at a reference position p (class R) or is base k >= 1 of the replacement at p (class X, inserted).
+// Walked in ascending allele order -- the ops in read order, or (reverse) from the last op down -- the columns are: M on R -> M, M on X -> I, D on R -> D, D on X ->
+// nothing, I -> I, and in front of an allele base one D per reference position the allele deleted between it and the base before it (deleted positions that touch
+// only the outside of the stretch are no part of the alignment).  Equal neighbours merge, D runs at either end are dropped, POS is the first remaining column that
+// consumes the reference; a mate without one (wholly inside inserted bases of the variant at p, or without template bases) takes the position its next such column
+// would have: POS = p + 2.  The id's "_allele<a>" stays in the QNAME, its end position is the id's (FragmentVar::end), and one tag follows XE:
+// XI:i:<FragmentVar::start_var_pos>, the bases of the replacement at the start position that lie in front of the fragment.
+//
+// AlleleCursor is placed once per mate (one allele_point, hinted by the one bisection that finds the stretch) and then steps base by base, entry by entry.  A mate
+// whose stretch no entry with a coordinate effect reaches -- most of them -- is `plain`: today's walk and CIGAR, its position the stretch's first base's.  With
+// substitutions only (allele copies, no FragmentVar) every mate is plain and the stretch is the fragment's own.
+struct AlleleBase {
+    uint32_t p;                // the base's reference position (class X: of its replacement)
+    uint32_t gap;              // reference positions the allele deleted between the base before and this one: [p - gap, p)
+    bool x;                    // class X
+};
+struct AlleleCursor {
+    AlleleView a;
+    uint32_t j;                // the map's next entry
+    uint32_t ref;              // the reference position of the next base
+    uint32_t k, len;           // k < len: the next base is base k of the replacement at ref
+    // at allele coordinate h, `entries` of the map beginning at or before it (what allele_point found there)
+    RSQ_HD AlleleCursor(const AlleleView &a_, int64_t h, uint32_t entries) : a(a_), j(entries), k(0u), len(0u) {
+        if (j) {
+            const int64_t at = h - a.begin_of(j - 1u);
+            const uint32_t n = a.var(j - 1u).len;
+            if (at < (int64_t)n) {
+                ref = a.e[j - 1u].pos;
+                k = (uint32_t)at;
+                len = n;
+                return;
+            }
+        }
+        ref = (uint32_t)(h - a.e[j].shift);
+    }
+    RSQ_HD bool inserted() const { return k < len && k != 0u; }         // the next base is of class X
+    RSQ_HD bool clear(uint32_t n) const { return !(k < len) && a.e[j].pos - ref >= n; }      // the next n bases are no entry's (the sentinel stands at the sequence's length)
+    RSQ_HD void skip(uint32_t n) { ref += n; }                          // ... n such bases
+    RSQ_HD AlleleBase next() {
+        AlleleBase b{ref, 0u, false};
+        if (k < len) {
+            b.x = k != 0u;
+            if (++k == len) {
+                ++ref;
+                k = len = 0u;
+            }
+            return b;
+        }
+        while (j < a.n && a.e[j].pos == ref) {
+            const uint32_t n = a.var(j).len;
+            ++j;
+            if (n) {                                                    // the base standing at ref, with n - 1 inserted ones behind it
+                b.p = ref;
+                if (n > 1u) {
+                    k = 1u;
+                    len = n;
+                } else ++ref;
+                return b;
+            }
+            ++b.gap;                                                    // deleted
+            ++ref;
+        }
+        b.p = ref++;
+        return b;
+    }
+};
+
+// the side entry of a mate: the walk, and where the record stands
+struct SamVarMate {
+    SamMate w;                 // q, t, cigar_chars, bytes as ever; pad: 0 plain (lead, trail as ever: sam_cigar writes the CIGAR), 1: the columns are walked with the cursor
+    uint32_t pos;              // POS - 1
+    uint32_t ref_bases;        // reference bases of the cleaned CIGAR
+    uint32_t entry;            // the cursor's start: entries of the map at or before ...
+    uint32_t at;               // ... the allele coordinate of the stretch's first base
+};
+static_assert(sizeof(SamVarMate) == 32, "two mates are one 64-byte load");
+struct SamVarPair {
+    SamVarMate mate[2];
+};
+// what the record takes from the FragmentVar beside the stretch
+struct SamVarId {
+    uint32_t end;              // the id's end position
+    uint32_t allele;           // the id names the allele
+    uint32_t xi;               // the XI tag
+};
+RSQ_HD SamVarId sam_var_id(const DevSim &S, const Fragment &f, bool has_fv, const FragmentVar &fv) {
+    return SamVarId{has_fv ? fv.end : f.start + f.len, 1u < S.num_alleles ? 1u : 0u, has_fv ? fv.start_var_pos : 0u};
+}
+
+// The columns of a template part, merged into elements: col() takes them in ascending allele order, end() closes; element() of the sink gets every run but D
+// runs at either end.  Beside the elements: where the first reference-consuming column stands and how many there are, dropped ones included.
+template <class Sink>
+struct SamVarRuns {
+    Sink &t;
+    bool reverse;
+    uint32_t cur = 3u, run = 0u, runs = 0u;
+    uint32_t first_ref = 0u, n_ref = 0u, left = 0u, right = 0u;         // left, right: reference positions of the D runs dropped at the low and the high end
+    bool any = false;
+    RSQ_HD void put() {
+        t.element(cur == 0u ? 'M' : cur == 1u ? 'D' : 'I', run);
+        any = true;
+    }
+    RSQ_HD void col(uint32_t op, uint32_t count, uint32_t p) {         // op: 0 M, 1 D, 2 I; p: the reference position of an M or D column (of the first of `count`)
+        if (op != 2u) {
+            if (!n_ref) first_ref = p;
+            n_ref += count;
+        }
+        if (op != cur) {
+            if (run) {
+                if (cur == 1u && runs == 1u) left = run;
+                else put();
+            }
+            cur = op;
+            run = 0u;
+            ++runs;
+        }
+        run += count;
+    }
+    RSQ_HD void end() {
+        if (!run) return;
+        if (cur != 1u) put();
+        else if (runs == 1u && !reverse) left = run;                    // D alone is dropped at the end the read begins at, as sam_walk's lead
+        else right = run;
+    }
+};
+template <class V>
+RSQ_HD void sam_var_columns(const WordColumn &ops, const ReadMeta &m, AlleleCursor &c, bool reverse, V &v) {
+    const uint32_t n = m.n_iter_m;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t it = reverse ? n - 1u - i : i;
+        // 16 plain iterations at once, as sam_cigar takes them -- where no entry of the map stands among their 16 bases
+        if ((reverse ? (it & 15u) == 15u : !(it & 15u) && it + 16u <= n) && (m.plain || !ops.at(it >> 4)) && c.clear(16u)) {
+            v.col(0u, 16u, c.ref);
+            c.skip(16u);
+            i += 15u;
+            continue;
+        }
+        const uint32_t op = m.plain ? 0u : sam_op_at(ops, it);
+        if (op == 2u) {
+            v.col(2u, 1u, 0u);
+            continue;
+        }
+        const AlleleBase b = c.next();
+        if (b.gap) v.col(1u, b.gap, b.p - b.gap);
+        if (!b.x) v.col(op, 1u, b.p);
+        else if (op == 0u) v.col(2u, 1u, 0u);
+    }
+    v.end();
+}
+// The CIGAR of a mate with an entry in reach (e.w.pad), or sam_cigar: the clip and the merged columns.  Returns what the columns came to.
+struct SamVarSpan {
+    uint32_t pos, ref_bases;
+};
+template <class Sink>
+RSQ_HD SamVarSpan sam_var_cigar(const DevSim &S, const Fragment &f, const WordColumn &ops, const ReadMeta &m, const SamVarMate &e, bool reverse, Sink &t) {
+    if (!e.w.pad) {
+        sam_cigar(ops, m, e.w, reverse, t);
+        return SamVarSpan{e.pos, e.ref_bases};
+    }
+    const uint32_t clip = (uint32_t)m.read_len - e.w.q;
+    AlleleCursor c(allele_view(S, f.seq, f.allele), (int64_t)e.at, e.entry);
+    const uint32_t behind = c.ref + (c.inserted() ? 1u : 0u);           // where a mate without a reference-consuming column stands
+    SamVarRuns<Sink> v{t, reverse};
+    if (reverse && clip) {
+        t.element('S', clip);
+        v.any = true;
+    }
+    sam_var_columns(ops, m, c, reverse, v);
+    if (!reverse && clip) {
+        t.element('S', clip);
+        v.any = true;
+    }
+    if (!v.any) t.ch('*');
+    return SamVarSpan{v.n_ref ? v.first_ref + v.left : behind, v.n_ref - v.left - v.right};
+}
+struct SamCigarCount {                                                  // a CIGAR's characters and elements
+    uint32_t chars = 0, n = 0;
+    RSQ_HD void element(char, uint32_t count) {
+        chars += digits_u32(count) + 1u;
+        ++n;
+    }
+    RSQ_HD void ch(char) { ++chars; }
+};
+
+// A mate's walk: sam_walk, the stretch, and -- only with an entry in reach -- the columns.  n_cigar: the CIGAR's elements where the columns were walked.
+RSQ_HD SamVarMate sam_var_walk(const DevSim &S, bool has_f, const Fragment &f, bool has_fv, const FragmentVar &fv, uint32_t seg, const WordColumn &ops, const ReadMeta &m,
+                               uint32_t &n_cigar) {
+    SamVarMate e{};
+    e.w = sam_walk(ops, m);
+    n_cigar = 0;
+    if (!has_f || !f.len) return e;
+    const bool rev = seg != f.strand;
+    const uint32_t t = e.w.t, d_left = rev ? e.w.trail : e.w.lead;
+    e.ref_bases = t - e.w.lead - e.w.trail;
+    if (!has_fv) {                                                      // allele copies: the fragment's own coordinates
+        e.pos = (rev ? f.start + f.len - t : f.start) + d_left;
+        return e;
+    }
+    // the stretch's first base, as allele_template finds it
+    const AlleleView a = allele_view(S, f.seq, f.allele);
+    const uint32_t var_pos = rev ? fv.end_var_pos : fv.start_var_pos, at = var_pos ? a.r.v[rev ? fv.end_var : fv.start_var].pos : rev ? fv.end : f.start;
+    const uint32_t near = a.entries_before(at);                         // the mate's one bisection
+    int64_t h = (int64_t)at + a.e[near].shift + var_pos - (rev ? t : 0u);
+    if (h < 0) h = 0;
+    const AllelePoint p = allele_point(a, h, near);
+    e.entry = p.j;
+    e.at = (uint32_t)h;
+    e.pos = p.ref + d_left;
+    bool reach = p.inside && (p.k || a.var(p.j - 1u).len != 1u);
+    for (uint32_t j = p.j; !reach && j < a.n && a.e[j].pos - p.ref < t; ++j) reach = a.var(j).len != 1u;      // (a substitution moves no coordinate)
+    if (reach) {
+        e.w.pad = 1u;
+        SamCigarCount count;
+        const SamVarSpan span = sam_var_cigar(S, f, ops, m, e, rev, count);
+        e.w.cigar_chars = (uint16_t)count.chars;
+        e.pos = span.pos;
+        e.ref_bases = span.ref_bases;
+        n_cigar = count.n;
+    }
+    return e;
+}
+RSQ_HD SamAlign sam_var_align(bool has_f, const Fragment &f, uint32_t seg, const SamVarMate &e0, const SamVarMate &e1) {
+    const int32_t pos[2] = {(int32_t)e0.pos + 1, (int32_t)e1.pos + 1}, last[2] = {pos[0] + (int32_t)e0.ref_bases - 1, pos[1] + (int32_t)e1.ref_bases - 1};
+    return sam_align_at(has_f, f, seg, pos, last);
+}
+
+template <class Sink>
+RSQ_HD void sam_var_head(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, const SamVarId &id, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &ops,
+                         const SamVarMate &e, const SamAlign &a, Sink &t) {
+    sam_qname_at(S, names, has_f, f, id.end, id.allele != 0u, adapter_only_number, m, t);
+    sam_head_front(names, f, a, t);
+    if (a.mapped) {
+        sam_var_cigar(S, f, ops, m, e, a.reverse != 0u, t);
+        sam_head_back(a, t);
+    }
+}
+template <class Sink>
+RSQ_HD void sam_var_tags(const ReadMeta &m, const WordColumn &ops, const SamVarId &id, Sink &t) {
+    t.str("\tXC:Z:", 6);
+    cigar_replay(ops, m, t);
+    t.str("\tXE:i:", 6);
+    t.num((uint32_t)m.num_errors);
+    t.str("\tXI:i:", 6);
+    t.num(id.xi);
+    t.ch('\n');
+}
+RSQ_HD uint32_t sam_var_tags_size(const ReadMeta &m, const SamVarId &id) { return sam_tags_size(m) + 6u + digits_u32(id.xi); }
+
+// SAM text of a reference with variants as a format.  What differs from SamFormat's members: the FragmentVar's part (SamVarId) where the QNAME or the tags are
+// written, and the alignment comes from the entries (sam_var_align).
+struct SamVarFormat {
+    static constexpr bool kVariants = true;
+    using Mate = SamVarMate;
+    using Pair = SamVarPair;
+    static RSQ_HD const SamVarMate &var(const Mate &e) { return e; }
+    static RSQ_HD uint32_t bytes(const Mate &e) { return e.w.bytes; }
+    static RSQ_HD Mate mate(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, const SamVarId &id, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &,
+                            const SamVarMate &w, uint32_t, const SamAlign &a) {
+        Mate e = w;
+        e.w.bytes = sam_qname_size_at(S, names, has_f, f, id.end, id.allele != 0u, adapter_only_number, m) + sam_head_fields_size(names, f, w.w.cigar_chars, a) + 2u * m.read_len + 1u +
+                    sam_var_tags_size(m, id);
+        return e;
+    }
+    template <class Sink>
+    static RSQ_HD void head(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, const SamVarId &id, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &seq,
+                            const WordColumn &ops, const Mate &e, const SamAlign &a, Sink &t) {
+        sam_var_head(S, names, has_f, f, id, adapter_only_number, m, ops, e, a, t);
+        sam_line(seq, m.read_len, false, a.reverse != 0u, S.phred_offset, t);
+        t.ch('\t');
+    }
+    template <class Sink>
+    static RSQ_HD void tail(const DevSim &S, const ReadMeta &m, const SamVarId &id, const WordColumn &qual, const WordColumn &ops, const SamAlign &a, Sink &t) {
+        sam_line(qual, m.read_len, true, a.reverse != 0u, S.phred_offset, t);
+        sam_var_tags(m, ops, id, t);
+    }
+    static RSQ_HD uint32_t tail_at(const Mate &e, const ReadMeta &m, const SamVarId &id) { return e.w.bytes - sam_var_tags_size(m, id) - m.read_len; }
+    template <class P>
+    static RSQ_HD uint32_t record(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, const SamVarId &id, uint64_t adapter_only_number, const ReadMeta &m,
+                                  const WordColumn &seq, const WordColumn &qual, const WordColumn &ops, const Mate &e, const SamAlign &a, P dst) {
+        WordSinkT<P> t(dst);
+        head(S, names, has_f, f, id, adapter_only_number, m, seq, ops, e, a, t);
+        tail(S, m, id, qual, ops, a, t);
+        t.finish();
+        return t.n;
+    }
+};
+
 #if RSQ_DEVICE_BUILD
 // One lane per raw row pair (row i of both segments: the two mates of pair perm[i], or of pair i): both mates' entries into side[row], the pair's bytes into
-// sizes[pair]
+// sizes[pair].  fvars: read by the formats of a reference with variants only (nullptr: allele copies)
 template <class Format>
 __global__ void __launch_bounds__(256) k_truth_sizes(DevSim S, NameTable names, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_only_first, RawLayout raw, const uint32_t *perm,
-                                                     typename Format::Pair *side, uint32_t *sizes) {
+                                                     typename Format::Pair *side, uint32_t *sizes, const FragmentVar *fvars) {
     const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= n_pairs) return;
     const uint64_t pair = perm ? perm[row] : row;
@@ -368,11 +690,22 @@ __global__ void __launch_bounds__(256) k_truth_sizes(DevSim S, NameTable names, 
     const bool has_f = frags != nullptr;
     const ReadMeta m0 = raw.meta[row], m1 = raw.meta[n_pairs + row];
     const WordColumn ops0 = raw.ops_of(row), ops1 = raw.ops_of(n_pairs + row);
-    const SamMate w0 = sam_walk(ops0, m0), w1 = sam_walk(ops1, m1);
     const uint64_t ao_number = adapter_only_first + pair + 1u;
     typename Format::Pair p;
-    p.mate[0] = Format::mate(S, names, has_f, f, ao_number, m0, ops0, w0, sam_align(has_f, f, 0u, w0, w1));
-    p.mate[1] = Format::mate(S, names, has_f, f, ao_number, m1, ops1, w1, sam_align(has_f, f, 1u, w0, w1));
+    if constexpr (Format::kVariants) {
+        const bool has_fv = has_f && fvars != nullptr;
+        FragmentVar fv{};
+        if (has_fv) fv = fvars[pair];
+        const SamVarId id = sam_var_id(S, f, has_fv, fv);
+        uint32_t n0, n1;
+        const SamVarMate w0 = sam_var_walk(S, has_f, f, has_fv, fv, 0u, ops0, m0, n0), w1 = sam_var_walk(S, has_f, f, has_fv, fv, 1u, ops1, m1, n1);
+        p.mate[0] = Format::mate(S, names, has_f, f, id, ao_number, m0, ops0, w0, n0, sam_var_align(has_f, f, 0u, w0, w1));
+        p.mate[1] = Format::mate(S, names, has_f, f, id, ao_number, m1, ops1, w1, n1, sam_var_align(has_f, f, 1u, w0, w1));
+    } else {
+        const SamMate w0 = sam_walk(ops0, m0), w1 = sam_walk(ops1, m1);
+        p.mate[0] = Format::mate(S, names, has_f, f, ao_number, m0, ops0, w0, sam_align(has_f, f, 0u, w0, w1));
+        p.mate[1] = Format::mate(S, names, has_f, f, ao_number, m1, ops1, w1, sam_align(has_f, f, 1u, w0, w1));
+    }
     side[row] = p;
     sizes[pair] = Format::bytes(p.mate[0]) + Format::bytes(p.mate[1]);
 }
@@ -389,7 +722,8 @@ RSQ_HD uint32_t sam_lds_bytes(uint64_t pair_bytes, bool slots) {        // the i
 template <class Format, bool PERM>
 __global__ void __launch_bounds__(64) k_truth_write(DevSim S, NameTable names, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_only_first, RawLayout raw,
                                                    const typename Format::Pair *side, const uint64_t *offsets, char *dst, uint64_t cap, const uint64_t *fastq_end0,
-                                                   const uint64_t *fastq_end1, uint64_t fastq_cap0, uint64_t fastq_cap1, const uint32_t *perm, uint32_t lds_bytes) {
+                                                   const uint64_t *fastq_end1, uint64_t fastq_cap0, uint64_t fastq_cap1, const uint32_t *perm, uint32_t lds_bytes,
+                                                   const FragmentVar *fvars) {
     extern __shared__ __attribute__((aligned(16))) char s_truth[];
     using Image = WaveImage<PERM, kSamPairs>;
     const uint32_t lane = threadIdx.x, part = lane / kSamPairs, seg = part >> 1, half = part & 1u;
@@ -411,18 +745,37 @@ __global__ void __launch_bounds__(64) k_truth_write(DevSim S, NameTable names, c
     const WordColumn seq = raw.seq_of(r), qual = raw.qual_of(r), ops = raw.ops_of(r);
     const uint64_t ao_number = adapter_only_first + pair + 1u;
     const typename Format::Mate e = seg ? p.mate[1] : p.mate[0];
-    const SamAlign a = sam_align(has_f, f, seg, Format::walk(p.mate[0]), Format::walk(p.mate[1]));
     const uint32_t rec_at = seg ? Format::bytes(p.mate[0]) : 0u;       // of the record within its pair's bytes
-    if (!im.through_lds) {
-        if (im.active && half == 0u) Format::record(S, names, has_f, f, ao_number, m, seq, qual, ops, e, a, dst + offsets[pair] + rec_at);
-        return;
-    }
-    im.clear(s_truth, lds_bytes);
-    if (im.active) {
-        ImageSink t(im.item_text(s_truth) + rec_at + (half ? Format::tail_at(e, m) : 0u));
-        if (half == 0u) Format::head(S, names, has_f, f, ao_number, m, seq, ops, e, a, t);
-        else Format::tail(S, m, qual, ops, a, t);
-        t.finish();
+    if constexpr (Format::kVariants) {
+        const bool has_fv = has_f && fvars != nullptr && im.active;
+        FragmentVar fv{};
+        if (has_fv) fv = fvars[pair];
+        const SamVarId id = sam_var_id(S, f, has_fv, fv);
+        const SamAlign a = sam_var_align(has_f, f, seg, Format::var(p.mate[0]), Format::var(p.mate[1]));
+        if (!im.through_lds) {
+            if (im.active && half == 0u) Format::record(S, names, has_f, f, id, ao_number, m, seq, qual, ops, e, a, dst + offsets[pair] + rec_at);
+            return;
+        }
+        im.clear(s_truth, lds_bytes);
+        if (im.active) {
+            ImageSink t(im.item_text(s_truth) + rec_at + (half ? Format::tail_at(e, m, id) : 0u));
+            if (half == 0u) Format::head(S, names, has_f, f, id, ao_number, m, seq, ops, e, a, t);
+            else Format::tail(S, m, id, qual, ops, a, t);
+            t.finish();
+        }
+    } else {
+        const SamAlign a = sam_align(has_f, f, seg, Format::walk(p.mate[0]), Format::walk(p.mate[1]));
+        if (!im.through_lds) {
+            if (im.active && half == 0u) Format::record(S, names, has_f, f, ao_number, m, seq, qual, ops, e, a, dst + offsets[pair] + rec_at);
+            return;
+        }
+        im.clear(s_truth, lds_bytes);
+        if (im.active) {
+            ImageSink t(im.item_text(s_truth) + rec_at + (half ? Format::tail_at(e, m) : 0u));
+            if (half == 0u) Format::head(S, names, has_f, f, ao_number, m, seq, ops, e, a, t);
+            else Format::tail(S, m, qual, ops, a, t);
+            t.finish();
+        }
     }
     im.store_out(s_truth);
 }

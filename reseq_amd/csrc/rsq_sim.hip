@@ -258,6 +258,7 @@ struct rsq_sim : PrepassSim {
     DevBuf sam_totals, sam_longest;          // rsq_sim_pairs_sam: [sub-ranges + 1] bytes of SAM text in front of a sub-range; the call's longest pair of records
     uint64_t sam_pair_bytes = 1100;          // that of the last call and a few bytes (sam_stage sizes the writer's LDS image with it)
     uint64_t bam_pair_bytes = 700;           // the same for a call that writes BAM records
+    bool truth_variants = false;             // rsq_sim_truth_variants: truth alignments of a reference with variants, in reference coordinates (SamVarFormat, BamVarFormat)
     // rsq_sim_bam_sorted_*: a run of calls whose BAM records leave in coordinate order (rsq_bamsort.h)
     struct BamSorted {
         bool active = false;
@@ -741,10 +742,11 @@ static char *sorted_stage_room(rsq_sim &s, uint64_t n_pairs, uint32_t part, hipS
     cap = b.stage[b.cur].bytes() - 32u - b.held_bytes;
     return b.stage[b.cur].as<char>() + b.held_bytes;
 }
-static void sorted_directory(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, const ReadsDone &rd, const BamPair *side, const uint64_t *offsets, hipStream_t st) {
+template <class Pair>
+static void sorted_directory(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, const ReadsDone &rd, const Pair *side, const uint64_t *offsets, hipStream_t st) {
     rsq_sim::BamSorted &b = s.bam_sorted;
     s.timers["bam_sort_keys"].start(st);
-    hipLaunchKernelGGL(k_bam_sort_keys, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, frags, n_pairs, rd.row_order, side, offsets, b.held_bytes,
+    hipLaunchKernelGGL(k_bam_sort_keys<Pair>, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, frags, n_pairs, rd.row_order, side, offsets, b.held_bytes,
                        b.dir[b.cur].as<BamDirEntry>() + b.n_held + 2u * b.call_pairs, s.dev.n_seqs, b.prev_cut, b.plan.pos_bits, b.out_of_order.as<uint32_t>());
     s.timers["bam_sort_keys"].stop(st);
     HIP_CHECK(hipGetLastError());
@@ -752,9 +754,9 @@ static void sorted_directory(rsq_sim &s, const Fragment *frags, uint64_t n_pairs
 }
 template <class Format>
 static void truth_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_first, const ReadsDone &rd, char *r1, size_t r1_cap, char *r2, size_t r2_cap, const SamOut &sam,
-                        uint32_t part, hipStream_t st) {
+                        uint32_t part, hipStream_t st, const FragmentVar *fvars) {
     using Pair = typename Format::Pair;
-    constexpr bool bam = std::is_same<Format, BamFormat>::value;
+    constexpr bool bam = std::is_same<Format, BamFormat>::value || std::is_same<Format, BamVarFormat>::value;
     const char *sizes_timer = bam ? "bam_sizes" : "sam_sizes", *write_timer = bam ? "bam_write" : "sam_write";
     rsq_sim::Workspace &w = *s.cur;
     DevBuf &side = bam ? w.bam_side : w.sam_side;
@@ -767,22 +769,24 @@ static void truth_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uin
     const uint64_t cap1 = r1 ? r1_cap : 0, cap2 = r2 ? r2_cap : 0;
     s.timers[sizes_timer].start(st);
     hipLaunchKernelGGL(k_truth_sizes<Format>, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw, rd.row_order, side.as<Pair>(),
-                       w.sam_sizes.as<uint32_t>());
+                       w.sam_sizes.as<uint32_t>(), fvars);
     s.timers[sizes_timer].stop(st);
     exclusive_scan(s, w.sam_sizes.as<uint32_t>(), n_pairs, w.off_sam.as<uint64_t>(), st, totals + part, totals + part + 1, s.sam_longest.as<uint32_t>());
     const uint32_t lds = sam_lds_bytes(bam ? s.bam_pair_bytes : s.sam_pair_bytes, rd.row_order != nullptr);
     if (sam.sorted) dst = sorted_stage_room(s, n_pairs, part, st, cap);
     s.timers[write_timer].start(st);
     launch_text_waves(k_truth_write<Format, true>, k_truth_write<Format, false>, rd.row_order, dim3(cdiv(n_pairs, kSamPairs)), lds, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw,
-                      side.as<Pair>(), w.off_sam.as<uint64_t>(), dst, cap, w.off_r1.as<uint64_t>() + n_pairs, w.off_r2.as<uint64_t>() + n_pairs, cap1, cap2, rd.row_order, lds);
+                      side.as<Pair>(), w.off_sam.as<uint64_t>(), dst, cap, w.off_r1.as<uint64_t>() + n_pairs, w.off_r2.as<uint64_t>() + n_pairs, cap1, cap2, rd.row_order, lds, fvars);
     s.timers[write_timer].stop(st);
     HIP_CHECK(hipGetLastError());
     if constexpr (bam)
         if (sam.sorted) sorted_directory(s, frags, n_pairs, rd, side.as<Pair>(), w.off_sam.as<uint64_t>(), st);
 }
 static void sam_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_first, const ReadsDone &rd, char *r1, size_t r1_cap, char *r2, size_t r2_cap, const SamOut &sam,
-                      uint32_t part, hipStream_t st) {
-    (sam.bam ? truth_stage<BamFormat> : truth_stage<SamFormat>)(s, frags, n_pairs, adapter_first, rd, r1, r1_cap, r2, r2_cap, sam, part, st);
+                      uint32_t part, hipStream_t st, const FragmentVar *fvars = nullptr) {
+    // a reference with variants (accepted only with rsq_sim_truth_variants): the formats in reference coordinates; every other simulator launches what it always did
+    if (s.has_variants) (sam.bam ? truth_stage<BamVarFormat> : truth_stage<SamVarFormat>)(s, frags, n_pairs, adapter_first, rd, r1, r1_cap, r2, r2_cap, sam, part, st, fvars);
+    else (sam.bam ? truth_stage<BamFormat> : truth_stage<SamFormat>)(s, frags, n_pairs, adapter_first, rd, r1, r1_cap, r2, r2_cap, sam, part, st, nullptr);
 }
 static void begin_sam_totals(rsq_sim &s, uint32_t parts, hipStream_t st) {
     s.sam_totals.reserve((size_t)(parts + 1) * 8 + 16);
@@ -1101,7 +1105,7 @@ static int sim_pairs(rsq_sim &s, uint32_t block_lo, uint32_t block_hi, char *r1,
                 HIP_CHECK(hipStreamWaitEvent(s_text, s.ev_fill, 0));
             }
             text_stage(s, frags, n, 0, rd, r1, r1_cap, r2, r2_cap, k, s_text, fvars);
-            if (sam) sam_stage(s, frags, n, 0, rd, r1, r1_cap, r2, r2_cap, *sam, k, s_text);
+            if (sam) sam_stage(s, frags, n, 0, rd, r1, r1_cap, r2, r2_cap, *sam, k, s_text, fvars);
         } else {                                                     // no pairs in this part: its text ends where it begins
             HIP_CHECK(hipMemcpyAsync(s.totals.as<uint64_t>() + 2 * (k + 1), s.totals.as<uint64_t>() + 2 * k, 16, hipMemcpyDeviceToDevice, s_text));
             if (sam) HIP_CHECK(hipMemcpyAsync(s.sam_totals.as<uint64_t>() + k + 1, s.sam_totals.as<uint64_t>() + k, 8, hipMemcpyDeviceToDevice, s_text));
@@ -1999,11 +2003,11 @@ int rsq_sim_pairs(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev
     REQUIRE(s && r1_len && r2_len && n_pairs, "null argument");
     return guard([&] { return sim_pairs(*s, block_lo, block_hi, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, n_pairs, frags_dev, frags_cap, (hipStream_t)stream); });
 }
-// Truth alignments, as SAM text or (bam) as BAM records.  Coordinates through an allele's insertions and deletions are not worked out: a reference with variants is
-// refused.  What BAM cannot hold is refused as well, before anything is launched: l_read_name is a byte, so no QNAME may exceed 254 characters (the base
+// Truth alignments, as SAM text or (bam) as BAM records.  A reference with variants is refused unless the caller has chosen the coordinate system of the record
+// (rsq_sim_truth_variants: reference coordinates, rsq_sam.h SamVarFormat).  What BAM cannot hold is refused as well, before anything is launched: l_read_name is a byte, so no QNAME may exceed 254 characters (the base
 // identifier, the longest reference name, every number at its widest), and the bins cover 2^29 bases.
 static bool truth_refusal(const rsq_sim &s, bool bam) {
-    if (s.has_variants) {
+    if (s.has_variants && !s.truth_variants) {
         g_last_error = std::string("truth alignments (") + (bam ? "BAM" : "SAM") + ") are not available for a reference with variants (rsq_ref_read_variants)";
         return true;
     }
@@ -2017,13 +2021,20 @@ static bool truth_refusal(const rsq_sim &s, bool bam) {
         return true;
     }
     // "{base}{block}_{number}:{pos}:{name}:{pos}:{tile}:1337:1337" with 32-bit block and number and a 16-bit tile; "{base}0_{number}:0:Adapter:0:{tile}:1337:1337" with a 64-bit number
-    const size_t mapped = s.names.base_len + 10 + 1 + 10 + 1 + 2 * (size_t)digits_u32(longest_seq) + 2 + longest_name + 1 + 5 + 10;
+    // (a reference with variants, rsq_sim_truth_variants: "_allele{a}" behind the number)
+    const size_t allele = s.has_variants && 1 < s.num_alleles ? 7 + digits_u32(s.num_alleles - 1) : 0;
+    const size_t mapped = s.names.base_len + 10 + 1 + 10 + allele + 1 + 2 * (size_t)digits_u32(longest_seq) + 2 + longest_name + 1 + 5 + 10;
     const size_t adapter_only = s.names.base_len + 2 + 20 + 12 + 1 + 5 + 10;
     if (std::max(mapped, adapter_only) > kBamMaxQname) {
         g_last_error = "truth alignments (BAM): a read name could take " + std::to_string(std::max(mapped, adapter_only)) + " characters, BAM holds 254 (shorten the reference names or the base identifier)";
         return true;
     }
     return false;
+}
+int rsq_sim_truth_variants(rsq_sim *s, int on) {
+    REQUIRE(s, "null argument");
+    s->truth_variants = on != 0;
+    return RSQ_OK;
 }
 static int pairs_truth(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len, char *out_dev,
                        size_t out_cap, size_t *out_len, uint64_t *n_pairs, rsq_fragment *frags_dev, size_t frags_cap, void *stream, bool bam) {
