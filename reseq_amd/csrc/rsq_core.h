@@ -298,11 +298,12 @@ RSQ_HD QuadFactors quad_factors(uint32_t c, const R0 &r0, const R1 &r1, const R2
 constexpr float kScreenSafety = 1.5f;
 constexpr float kScreenMinSum = 9.313225746154785e-10f;      // 2^-30
 
-// Q quads per row (compile-time: the loops unroll, the loads of a batch of quads are issued before their products are formed).
+// Q quads per row (compile-time: the loops unroll, the loads of a batch of G quads are issued before their products are formed: Q / G round trips to the rows'
+// memory, 16 more registers in flight per further quad of a batch; the additions and their order do not depend on G).
 // Returns true and the outcome COLUMN if the draw is decided.
-template <int Q, class... Rs>
-RSQ_HD bool draw_screened(uint32_t word, uint32_t &col, const Rs &...rs) {
-    constexpr int G = Q % RSQ_SCREEN_BATCH == 0 ? RSQ_SCREEN_BATCH : (Q % 2 == 0 ? 2 : 1);      // quads per batch
+template <int Q, int G, class... Rs>
+RSQ_HD bool draw_screened_batched(uint32_t word, uint32_t &col, const Rs &...rs) {
+    static_assert(G >= 1 && Q % G == 0, "whole batches");
     constexpr bool kKeep = Q <= 2;                           // short rows: the factors stay in registers, pass 2 loads nothing
     // pass 1 runs from the bottom quad up with ONE running sum, kept as a pair (the columns 0, 2 and 1, 3 of the quads so far): bot[c] = the sum of the quads below
     // c, S = bot[Q].  Per quad two packed FMAs take the last factor and the addition together (the bounds above: 2Q roundings in the pair, one across it).  [One sum
@@ -358,6 +359,11 @@ RSQ_HD bool draw_screened(uint32_t word, uint32_t &col, const Rs &...rs) {
     constexpr float kBand = kScreenSafety * (float)(4 * Q + 20) * 5.9604644775390625e-08f;
     const float delta = fma1(kBand, hi, (kBand * 9.5367431640625e-07f) * S);      // kBand * (hi + 2^-20 S): two roundings, as the sum and the product had
     return S >= kScreenMinSum && below != 0u && r - lo > delta && hi - r >= delta;      // S >= 2^-30 also rejects NaN
+}
+
+template <int Q, class... Rs>
+RSQ_HD bool draw_screened(uint32_t word, uint32_t &col, const Rs &...rs) {
+    return draw_screened_batched<Q, Q % RSQ_SCREEN_BATCH == 0 ? RSQ_SCREEN_BATCH : (Q % 2 == 0 ? 2 : 1)>(word, col, rs...);
 }
 
 // AdjustIndeces (:368-380): v < from ? 0 : (v - from >= rows ? rows - 1 : v - from), as a signed difference held between 0 and rows - 1 (values, first values

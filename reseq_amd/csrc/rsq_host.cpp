@@ -46,6 +46,7 @@ const OptionEntry kOptionTable[] = {
     {"fasta_stretch", &Options::fasta_stretch}, {"overlap", &Options::overlap}, {"specialize", &Options::specialize}, {"job_write_direct", &Options::job_write_direct},             {"job_chunk_bytes", &Options::job_chunk_bytes}, {"host_gzip", &Options::host_gzip}, {"fill_waves", &Options::fill_waves}, {"fasta_no_stage", &Options::fasta_no_stage},
     {"hiprtc_by_name", &Options::hiprtc_by_name}, {"gzip_route", &Options::gzip_route},       {"gzip_stretch", &Options::gzip_stretch},
     {"sieve_lds", &Options::sieve_lds},         {"sieve_lds_bytes", &Options::sieve_lds_bytes}, {"sieve_tracks_mb", &Options::sieve_tracks_mb},
+    {"wide_rows", &Options::wide_rows},
 };
 }  // namespace
 bool set_option(const char *name, int64_t value) {

@@ -50,6 +50,7 @@ struct Options {
     int64_t sieve_lds = 1;             // 1: the sieve's gap walk reads its coverage group's tables from LDS copies (k_sieve_gaps_lds) where they fit; 0: always from memory
     int64_t sieve_lds_bytes = 0;       // > 0: the LDS the staged gap tables may take (default 64 KB; tests: below the profile's need, so that the walk falls back to memory)
     int64_t sieve_tracks_mb = 4096;    // the surrounding-bias tracks of the pre-pass (16 bytes per position) stay for the sieve's candidate kernel when they take no more MB than this; 0: never
+    int64_t wide_rows = 0;             // 1: the read kernel's cursor forms 64-bit addresses (RawLayout::wide) as for raw arrays of 4 GB and more, whatever the call's size (tests)
     int64_t overlap = 0;               // n > 1: rsq_sim_pairs cuts its block range into n sub-ranges whose sieve / reads / text stages are pipelined on three streams
 };
 Options &options();                                               // the process-wide values

@@ -45,8 +45,64 @@ struct ReadOut {                        // destination of one lane's read; bases
             qual.at(n_put >> 2) = qual_word;
         }
     }
+    RSQ_HD void finish(uint32_t, uint32_t) { finish(); }      // WaveReadOut is told what this one counts itself
 };
 RSQ_HD ReadOut make_read_out(const WordColumn &seq, const WordColumn &qual, const WordColumn &ops) { return ReadOut{seq, qual, ops, 0u, 0u, 0u, 0u, 0u}; }
+
+// The same destination for the wave kernels, without a 64-bit address per lane and array.  The three arrays are the kernel's argument (wave-uniform: scalar
+// registers) and share one pitch; the lane keeps its row, and a store forms ONE 32-bit byte offset from word and row (global_store_dword v_off, v_data,
+// s[base:base+1], as PoolRow32 loads).  A call's arrays can span 4 GB or more (38 words x pitch x 4 B): the host says so per call (RawLayout::wide) and the
+// store then forms the 64-bit address as WordColumn does -- a wave-uniform branch at the store, which a lane reaches once in four steps; the state
+// carried through the steps is the same either way.  [The alternative, the chunk's first row in the scalar base, shortens only the row's share of the
+// offset: the word's share, w * pitch * 4, passes 2^32 all the same, and the rows of a chunk of records are not neighbours.]
+// Words are stored as ReadOut stores them: a seq / qual word when its fourth base arrives, an ops word when the first iteration of the next one
+// arrives; the rest in finish().  The positions come 0, 1, 2, ... and the iterations with an op 0, 1, 2, ... up to the tail, so "which word" is the
+// counter's high bits and needs no register of its own.
+RSQ_HD constexpr uint32_t read_out_offset(uint32_t w, uint32_t pitch, uint32_t row) { return (w * pitch + row) * 4u; }      // bytes; exact while words * pitch * 4 <= 2^32
+RSQ_HD constexpr bool read_out_is_wide(uint64_t words, uint64_t pitch) { return words * pitch * 4u > 0x100000000ull; }      // words: of the longest array; pitch below 2^32 (raw_layout refuses more)
+struct WaveReadOut {
+    uint32_t *seq, *qual, *ops;         // wave-uniform
+    uint32_t pitch;                     // wave-uniform
+    bool wide;                          // wave-uniform
+    uint32_t row;                       // the lane's row
+    uint32_t cur_word, seq_word, qual_word;
+    RSQ_HD uint32_t *at(uint32_t *base, uint32_t w) const {      // word w of the lane's row of array `base`
+        if (wide) {
+            uint32_t r = row;
+#if defined(__HIP_DEVICE_COMPILE__)
+            asm volatile("" : "+v"(r));      // or the compiler carries base + row, a 64-bit address per array, through the steps for this branch
+#endif
+            return base + ((uint64_t)w * pitch + r);
+        }
+        return reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(base) + read_out_offset(w, pitch, row));
+    }
+    RSQ_HD void store(uint32_t *base, uint32_t w, uint32_t v) const { *at(base, w) = v; }
+    RSQ_HD void put(uint32_t pos, uint32_t base, uint32_t qual_char) {
+        const uint32_t sh = (pos & 3u) * 8u;
+        seq_word |= base << sh;
+        qual_word |= qual_char << sh;
+        if ((pos & 3u) == 3u) {
+            store(seq, pos >> 2, seq_word);
+            store(qual, pos >> 2, qual_word);
+            seq_word = qual_word = 0;
+        }
+    }
+    RSQ_HD void op(uint32_t it, uint32_t code) {
+        if (!(it & 15u) && it) {
+            store(ops, (it >> 4) - 1u, cur_word);
+            cur_word = 0;
+        }
+        cur_word |= code << ((it & 15u) * 2u);
+    }
+    // n_put: bases put (the read's length so far), n_ops: iterations that had an op
+    RSQ_HD void finish(uint32_t n_put, uint32_t n_ops) {
+        store(ops, n_ops ? (n_ops - 1u) >> 4 : 0u, cur_word);
+        if (n_put & 3u) {
+            store(seq, n_put >> 2, seq_word);
+            store(qual, n_put >> 2, qual_word);
+        }
+    }
+};
 
 struct RawLayout {                      // word-major arrays of the read kernel, read index = segment * n_pairs + pair
     uint32_t *seq, *qual;               // [read_words][pitch]: 4 bases / 4 quality characters per word
@@ -55,12 +111,14 @@ struct RawLayout {                      // word-major arrays of the read kernel,
     uint64_t pitch;                     // reads per word row (>= number of reads)
     uint64_t *templates;                // --methylation: [reads][template_words] converted templates, else nullptr
     uint32_t template_words;
+    uint32_t wide;                      // read_out_is_wide of the arrays: a byte offset into them needs more than 32 bits (WaveReadOut)
     const uint32_t *order;              // seqToIllumina, after a read kernel that ran binned by tile: row r holds record order[r]; nullptr: record r
     RSQ_HD uint64_t item_of(uint64_t row) const { return order ? order[row] : row; }
     RSQ_HD WordColumn seq_of(uint64_t r) const { return WordColumn{seq + r, pitch}; }
     RSQ_HD WordColumn qual_of(uint64_t r) const { return WordColumn{qual + r, pitch}; }
     RSQ_HD WordColumn ops_of(uint64_t r) const { return WordColumn{ops + r, pitch}; }
     RSQ_HD ReadOut out_of(uint64_t r) const { return make_read_out(seq_of(r), qual_of(r), ops_of(r)); }
+    RSQ_HD WaveReadOut wave_out_of(uint64_t r) const { return WaveReadOut{seq, qual, ops, (uint32_t)pitch, wide != 0u, (uint32_t)r, 0u, 0u, 0u}; }
 };
 
 struct FragmentSrc {                    // template of one mate cut from the 2-bit reference (Reference.cpp:483-496)
@@ -136,6 +194,61 @@ struct FragmentSrc {                    // template of one mate cut from the 2-b
         return sum;
     }
 };
+
+// What the STEPS of a wave kernel need of a FragmentSrc (init() takes the whole one: its totals want gc_prefix and both forms of the template).  The arrays --
+// the 2-bit reference or the converted templates, the two error tracks -- are wave-uniform and stay in scalar registers; the lane keeps ELEMENT indices of
+// its first template word and its first error entry and forms the address at the load, once in 32 steps (template) and once in four (errors).  An index is
+// 32 bits and a few high bits: a human-sized error track has more than 2^31 entries (above 4 GB in bytes), a larger reference more than 2^32; the high bits
+// share one register with the two flags (WaveSrcBits), so the state is four registers and what the source last read.
+namespace WaveSrcBits {
+constexpr uint32_t kBackward = 1u, kRevStrand = 2u;      // the template is read downwards and complemented; the errors are the reverse strand's
+constexpr uint32_t kWordHighShift = 8u, kWordHighBits = 8u, kSysHighShift = 16u, kSysHighBits = 16u;
+RSQ_HD constexpr uint32_t pack(bool backward, bool rev_strand, uint64_t word0, uint64_t sys0) {
+    return (backward ? kBackward : 0u) | (rev_strand ? kRevStrand : 0u) | ((uint32_t)(word0 >> 32) << kWordHighShift) | ((uint32_t)(sys0 >> 32) << kSysHighShift);
+}
+RSQ_HD constexpr uint64_t word_index(uint32_t bits, uint32_t word0, uint32_t index) { return (((uint64_t)((bits >> kWordHighShift) & ((1u << kWordHighBits) - 1u)) << 32) | word0) + index; }
+RSQ_HD constexpr uint64_t sys_index(uint32_t bits, uint32_t sys0, uint32_t k) { return (((uint64_t)(bits >> kSysHighShift) << 32) | sys0) + k; }
+}  // namespace WaveSrcBits
+struct WaveFragmentSrc {
+    const uint64_t *words;              // wave-uniform: the 2-bit reference (with the alleles' copies behind it), or the converted templates
+    const uint16_t *sys_fwd, *sys_rev;  // wave-uniform
+    uint32_t word0;                     // the word of `words` that holds template position 0 of the lane's sequence (or template): low 32 bits
+    uint32_t first;                     // as FragmentSrc::first; 0 in a converted template
+    uint32_t sys0;                      // the entry of the strand's track at the first template base: low 32 bits
+    uint32_t bits;                      // WaveSrcBits
+    mutable uint32_t held_word = 0xFFFFFFFFu, held_sys = 0xFFFFFFFFu;
+    mutable uint64_t word = 0, sys4 = 0;
+    RSQ_HD const uint64_t *word_at(uint32_t index) const { return words + WaveSrcBits::word_index(bits, word0, index); }      // word `index` of the lane's sequence (or template)
+    RSQ_HD const uint16_t *sys_at(uint32_t k) const { return ((bits & WaveSrcBits::kRevStrand) ? sys_rev : sys_fwd) + WaveSrcBits::sys_index(bits, sys0, k); }
+    RSQ_HD uint32_t base(uint32_t k) const {
+        const bool backward = bits & WaveSrcBits::kBackward;
+        const uint32_t pos = backward ? first - 1u - k : first + k, index = pos >> 5;
+        if (index != held_word) {
+            held_word = index;
+            word = *word_at(index);
+        }
+        const uint32_t b = (uint32_t)(word >> ((pos & 31u) * 2u)) & 3u;
+        return backward ? 3u - b : b;
+    }
+    RSQ_HD uint32_t sys_base(uint32_t k) const {
+        if ((k >> 2) != held_sys) {
+            held_sys = k >> 2;
+            const uint16_t *p = sys_at(k & ~3u);
+#if defined(__HIP_DEVICE_COMPILE__)
+            sys4 = *reinterpret_cast<const uint64_t __attribute__((aligned(2))) *>(p);
+#else
+            memcpy(&sys4, p, 8);
+#endif
+        }
+        return (uint32_t)(sys4 >> ((k & 3u) * 16u)) & 0xFFFFu;
+    }
+    RSQ_HD uint32_t sys_deleted(uint32_t k) const { return sys_base(k); }
+};
+// of a FragmentSrc whose template is `converted_word0` words into `templates` (src.converted set) or the reference's own (templates == nullptr)
+RSQ_HD WaveFragmentSrc wave_fragment_src(const DevSim &S, const FragmentSrc &src, const uint64_t *templates, uint64_t converted_word0) {
+    const uint64_t word0 = templates ? converted_word0 : (uint64_t)(src.words - S.ref_words) + src.word_off, sys0 = (uint64_t)(src.sys_ - (src.reverse ? S.sys_rev : S.sys_fwd));
+    return WaveFragmentSrc{templates ? templates : S.ref_words, S.sys_fwd, S.sys_rev, (uint32_t)word0, templates ? 0u : src.first, (uint32_t)sys0, WaveSrcBits::pack(!templates && src.reverse, src.reverse, word0, sys0)};
+}
 
 // ------------------------------------------------------------------------------------- bisulfite conversion (a16)
 // Simulator::CTConversion (Simulator.cpp:1925-2247): a C of a template becomes a T with probability 1 - methylation where the template lies in an
@@ -386,7 +499,9 @@ RSQ_HD int32_t geo_clamp(int32_t d, int32_t last) {
 // QQ = quads per row of the quality family (LdsPlan::quads_q).  `t` is the step the wave is in: the quality rows over the read
 // positions t, ... t-kRingLag are in the wave's ring (lds_ring_load / lds_ring_store).  Rows are found from (table, value) by the families' common
 // geometry; a table's descriptor is read only on the double-precision route and for the rare fallbacks of FillReadPart.
-template <uint32_t MASK>
+// QB = quads per batch of the quality draw (draw_screened_batched): its QQ quads are QQ / QB dependent round trips to LDS in every step.  RSQ_SCREEN_BATCH unless
+// the kernel asks for more (the kernel of the plain pairs: kQualityBatchPairs); the draws of short rows take RSQ_SCREEN_BATCH through draw_screened.
+template <uint32_t MASK, int QB = RSQ_SCREEN_BATCH>
 struct ScreenTables {
     using Sum = uint32_t;              // 0: prob_sum is 0, else 1 (all the callers ask; a double here costs the loop moves and 64-bit compares)
     static constexpr int QQ = (int)MASK;
@@ -431,7 +546,7 @@ struct ScreenTables {
         const LdsRow32 m2{ring_ + (near ? idx[2] % kRingSlots : kRingSlots) * RSQ_PLAN(S, ring_stride) + local * slot};
         const LdsRow32 m3{img + RSQ_PLAN(S, q3_off) + local * RSQ_PLAN(S, q3_stride) + (r3 < nr ? r3 : 0u) * slot};
         uint32_t col = 0;
-        const bool decided = draw_screened<QQ>(u, col, m0, m1, m2, m3) && (near || idx[2] == demand) && r3 < nr;      // a rate or a position whose row is not staged: double precision
+        const bool decided = draw_screened_batched<QQ, QQ % QB == 0 ? QB : (QQ % 2 == 0 ? 2 : 1)>(u, col, m0, m1, m2, m3) && (near || idx[2] == demand) && r3 < nr;      // a rate or a position whose row is not staged: double precision
         RSQ_SCREEN_COUNT(0, decided);
         return settle<4>(decided, RSQ_PLAN(S, q.values), local * slot + col, local, idx, u, ps);
     }
@@ -862,9 +977,11 @@ RSQ_HD RecordSrc record_src_at(const uint8_t *seqs, const uint8_t *dom, const ui
 }
 // Workgroup sizes of the read kernels: 1024 threads -- four waves per SIMD at 128 VGPRs.  The step is a chain of dependent draws that leaves VALU and LDS idle a
 // fifth of the time at three waves per SIMD; a fourth wave fills more of it than the spills cost that 128 registers bring (the profile's own kernel for read pairs:
-// 11 spilled VGPRs, 80 B of scratch; with variants 67 and 208 B).  Measured against 768 threads, 157-168 VGPRs and no spill (profiles/r04_zz_block_*): read pairs
+// then 11 spilled VGPRs, 80 B of scratch; with variants 67 and 208 B).  Measured then against 768 threads, 157-168 VGPRs and no spill (profiles/r04_zz_block_*): read pairs
 // 47.2 -> 42.5 ms per 10 M pairs, seqToIllumina records 22.9 -> 22.1 ms per 8 M, configs[4] at 1/10 scale 107.5 -> 112.8 M pairs/s -- with the screen's loads
-// issued a quad at a time (RSQ_SCREEN_BATCH 1; two at a time the walking kernels lose 3-7 % at 1024 threads).  RSQ_FILL_BLOCK_WALK: the kernels whose source walks
+// issued a quad at a time in every kernel (RSQ_SCREEN_BATCH 1; two at a time the walking kernels lose 3-7 % at 1024 threads, and they still take one).  Since the
+// kernel of the plain pairs carries WaveReadOut and WaveFragmentSrc it has the registers for two quads of the quality draw at a time: 11 spilled VGPRs and 88 B with
+// them, 17 and 104 B before (DESIGN_LOG.md section 23).  RSQ_FILL_BLOCK_WALK: the kernels whose source walks
 // per-lane state (variants, records), should a build want them smaller.
 // The same for records parsed on the device (rsq_fasta.h Packed): a half-word per base -- base code in bits 0-1, dominant error in bits 2-4, error percent in
 // bits 8-15 -- so the lane's eight bases of all three come with ONE 16-byte load (RecordSrc: three 8-byte loads, each touching a cache line of the lane's own).
@@ -932,6 +1049,7 @@ RSQ_HD PackedRecordSrc packed_record_src(const uint16_t *codes, uint32_t at, uin
 #ifndef RSQ_FILL_BLOCK_WALK
 #define RSQ_FILL_BLOCK_WALK 1024
 #endif
+constexpr int kQualityBatchPairs = RSQ_SCREEN_BATCH > 2 ? RSQ_SCREEN_BATCH : 2;      // quads per batch of the quality draw in the kernel of the plain pairs (ScreenTables QB): at least two
 constexpr uint32_t kFillBlock = RSQ_FILL_BLOCK, kFillBlockWalk = RSQ_FILL_BLOCK_WALK;
 constexpr uint32_t kFillWavesMax = (kFillBlock > kFillBlockWalk ? kFillBlock : kFillBlockWalk) / 64u;      // the LDS image has a ring for every wave of the larger one
 RSQ_HD constexpr uint32_t fill_block(bool walk) { return walk ? kFillBlockWalk : kFillBlock; }
@@ -981,22 +1099,23 @@ __device__ RSQ_LDS float *fill_stage_image(const DevSim &S, float *lds_image, ui
 }
 // 64 reads of one wave through the state machine: one uniform step loop.  Screened (MASK != 0): at the beginning of a step the wave
 // copies the quality rows over the step's read position into its ring.  `tile` (index among the profile's tiles) is the lane's own.
-template <uint32_t MASK, class Src>
+// `whole`: the template as init() wants it (the totals of the read's start); `src`: as the steps read it (the same object, or its WaveFragmentSrc).
+template <uint32_t MASK, int QB = RSQ_SCREEN_BATCH, class Whole, class Src, class Out>
 __device__ void fill_wave_reads(const DevSim &S, RSQ_LDS float *img, uint32_t qbase, uint32_t seg, bool active, const Stream &st, uint32_t tile, uint32_t fragment_length,
-                                const Src &src, ReadOut &out, ReadMeta &meta) {
+                                const Whole &whole, const Src &src, Out &out, ReadMeta &meta) {
     ReadMachine m;
     if constexpr (MASK == 0) {
         const GlobalTables tab{S};
         if (active) {
-            m.init(S, tab, st, seg, tile, fragment_length, src);
+            m.init(S, tab, st, seg, tile, fragment_length, whole);
             while (m.step(S, tab, st, src, out)) {}
         }
     } else {
         const uint32_t lane = threadIdx.x & 63u, n_items = lds_ring_items(S);
         RSQ_LDS float *ring = img + RSQ_PLAN(S, ring_off) + (threadIdx.x >> 6) * kRingRows * RSQ_PLAN(S, ring_stride);
-        ScreenTables<MASK> tab{S, img, qbase, ring, 0u};
+        ScreenTables<MASK, QB> tab{S, img, qbase, ring, 0u};
         m.idle();
-        if (active) m.init(S, tab, st, seg, tile, fragment_length, src);
+        if (active) m.init(S, tab, st, seg, tile, fragment_length, whole);
         const RingItem mine = lds_ring_item(S, qbase, lane < n_items ? lane : 0u);      // the lane's first item (with one tile per image: its only one)
         // the lane's item of the NEXT step is loaded while this step runs (the row comes from L2: its latency would stand at the head of every step)
         Quad ahead = lane < n_items ? lds_ring_load(S, mine, 0u) : zero_quad();
@@ -1042,7 +1161,7 @@ __device__ void fill_wave_reads(const DevSim &S, RSQ_LDS float *img, uint32_t qb
     }
     if (active) {
         m.finalize(meta);
-        out.finish();
+        out.finish(m.par.read_pos, m.par.iteration - m.hard_clip);      // every tail iteration (the iterations without an op) emits one of the hard_clip bases
     }
 }
 
@@ -1121,7 +1240,6 @@ __device__ void fill_pair_chunk(const DevSim &S, const NameTable &names, RSQ_LDS
                                 const Fragment *frags, uint64_t n_pairs, uint64_t adapter_only_first, const RawLayout &raw, uint32_t *sizes, const FragmentVar *fvars,
                                 const uint32_t *perm) {
     const uint64_t at = active ? row : 0u, r_out = (uint64_t)seg * n_pairs + at;
-    ReadOut out = raw.out_of(r_out);
     Fragment f{};
     if (active && frags) f = frags[at];
     // the read's stream and template (CreateReads :634-721 / SimulateAdapterOnlyPairs :2359-2382)
@@ -1137,11 +1255,19 @@ __device__ void fill_pair_chunk(const DevSim &S, const NameTable &names, RSQ_LDS
     if constexpr (VAR) {                                            // launched for fragments only
         VariantSrc src = variant_src(S, f, fvars ? &fv : nullptr, seg);
         if (raw.templates) src.converted = raw.templates + ((uint64_t)seg * n_pairs + pair0) * raw.template_words;
-        fill_wave_reads<MASK>(S, img, qbase, seg, active, st, tile, f.len, src, out, meta);
+        ReadOut out = raw.out_of(r_out);
+        fill_wave_reads<MASK>(S, img, qbase, seg, active, st, tile, f.len, src, src, out, meta);
     } else {
+        // The kernel of the plain pairs carries the slim forms of cursor and template through its steps, and with the registers they leave it draws the quality
+        // two quads at a time.  The kernels whose source walks per-lane state (variants above, records) have no registers to gain from them: compiled for P0
+        // they trade the vector registers for scalar ones that spill in turn, and two quads at a time spill more than one (DESIGN_LOG.md section 23).
         FragmentSrc src = from_fragment && active ? fragment_src(S, f, seg) : FragmentSrc{S.ref_words, 0, 0, 0, false, S.sys_fwd, nullptr, nullptr};      // len 0 = empty template
-        if (from_fragment && raw.templates) src.converted = raw.templates + ((uint64_t)seg * n_pairs + pair0) * raw.template_words;
-        fill_wave_reads<MASK>(S, img, qbase, seg, active, st, tile, f.len, src, out, meta);
+        const uint64_t *templates = from_fragment ? raw.templates : nullptr;                          // wave-uniform
+        const uint64_t template_at = ((uint64_t)seg * n_pairs + pair0) * raw.template_words;
+        if (templates) src.converted = templates + template_at;
+        const WaveFragmentSrc walk = wave_fragment_src(S, src, templates, template_at);
+        WaveReadOut out = raw.wave_out_of(r_out);
+        fill_wave_reads<MASK, kQualityBatchPairs>(S, img, qbase, seg, active, st, tile, f.len, src, walk, out, meta);
     }
     if (active) {
         raw.meta[r_out] = meta;
@@ -1207,11 +1333,11 @@ __device__ void fill_record_chunk(const DevSim &S, const RecordJob &job, RSQ_LDS
     const uint32_t tile = BINNED ? bin_tile : (active ? draw_tile(S, st.c0, st.c1, st.c2, pair_c3(kDomErrModel, 0, 2)) : 0u);
     if constexpr (PACKED) {
         const PackedRecordSrc src = packed_record_src(job.codes, job.rec_at[i], job.rec_len[i], job.array_bytes);
-        fill_wave_reads<MASK>(S, img, qbase, seg, active, st, tile, job.frag_len[i], src, out, meta);
+        fill_wave_reads<MASK>(S, img, qbase, seg, active, st, tile, job.frag_len[i], src, src, out, meta);
     } else {
         const RecordSrc src = job.rec_at ? record_src_at(job.seqs, job.dom, job.rate, job.rec_at[i], job.rec_len[i], job.array_bytes)
                                          : record_src(job.seqs, job.dom, job.rate, job.read_len, i, job.n_records);
-        fill_wave_reads<MASK>(S, img, qbase, seg, active, st, tile, job.frag_len[i], src, out, meta);
+        fill_wave_reads<MASK>(S, img, qbase, seg, active, st, tile, job.frag_len[i], src, src, out, meta);
     }
     if (active) raw.meta[row] = meta;
 }

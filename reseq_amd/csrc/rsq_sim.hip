@@ -469,7 +469,10 @@ static RawLayout raw_layout(rsq_sim &s, uint64_t n_reads) {
     s.cur->raw_qual.reserve((uint64_t)(s.read_stride / 4u) * pitch * 4 + 16);
     s.cur->raw_ops.reserve((uint64_t)s.ops_stride * pitch * 4 + 16);
     s.cur->raw_meta.reserve(n_reads * sizeof(ReadMeta) + 16);
-    return RawLayout{s.cur->raw_seq.as<uint32_t>(), s.cur->raw_qual.as<uint32_t>(), s.cur->raw_ops.as<uint32_t>(), s.cur->raw_meta.as<ReadMeta>(), pitch, nullptr, 0, nullptr};
+    // the read kernels' stores take 32-bit byte offsets while the longest of the arrays stays within 4 GB (WaveReadOut)
+    if (pitch > 0xFFFFFFFFull) throw Error("more than 2^32 reads in one call: use smaller block ranges");      // the cursor's row and pitch are 32-bit (no device holds such arrays)
+    const uint32_t wide = s.opt.wide_rows || read_out_is_wide(std::max<uint64_t>(s.read_stride / 4u, s.ops_stride), pitch) ? 1u : 0u;
+    return RawLayout{s.cur->raw_seq.as<uint32_t>(), s.cur->raw_qual.as<uint32_t>(), s.cur->raw_ops.as<uint32_t>(), s.cur->raw_meta.as<ReadMeta>(), pitch, nullptr, 0, wide, nullptr};
 }
 
 // Reads binned by tile (the LDS plan holds one tile per image): keys, histogram, the bins' places and units, the scatter.  n_keys = n_tiles (pairs:
