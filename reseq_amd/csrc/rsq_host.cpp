@@ -38,7 +38,7 @@ struct OptionEntry {
 };
 const OptionEntry kOptionTable[] = {
     {"fill_mode", &Options::fill_mode},         {"image_tiles", &Options::image_tiles},     {"rate_rows", &Options::rate_rows},
-    {"no_indel_skip", &Options::no_indel_skip}, {"force_exact", &Options::force_exact},     {"min_quality_quads", &Options::min_quality_quads},
+    {"no_indel_skip", &Options::no_indel_skip}, {"force_exact", &Options::force_exact},     {"base_call_word", &Options::base_call_word},     {"min_quality_quads", &Options::min_quality_quads},
     {"trace_plan", &Options::trace_plan},       {"trace_prepare", &Options::trace_prepare},
     {"bias_window", &Options::bias_window},     {"window_chunks", &Options::window_chunks}, {"serial_fasta", &Options::serial_fasta},   {"trace_load", &Options::trace_load},
     {"chain_chunk", &Options::chain_chunk},     {"chain_warmup", &Options::chain_warmup},

@@ -115,6 +115,76 @@ static inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b -
 constexpr uint32_t kLdsBudgetBytes = 160u * 1024u;
 constexpr uint32_t kLdsRateRowsFirst = 64;    // rows of the error-rate margins staged in LDS before anything optional (97 % of all positions have rate 0)
 
+// Base calls decided by the random word alone (ScreenTables::base_call_word, rsq_reads.h).  The bound is the one of "Draws decided by the random word alone" in
+// pack_tables below -- column z is certain for u between B_hi / (1 + B_hi) and 1 / (1 + B_lo) --, with z = the column whose outcome value is the table's template
+// base (prob_sum == 0 then means the same: FillReadPart takes the template base), but a base-call draw has four margins that all differ from lane to lane.  So the
+// sum over the columns on one side of z of the products of the margins' ratios row[c] / row[z] is bounded by a PRODUCT of one scalar per margin: the SUM of the
+// ratios of the lane's quality row (margin 0) times, for each other margin, the LARGEST ratio over the side's columns.  Every scalar is kept per VALUE of the
+// margin, not per row: the table's own row of a value (AdjustIndeces: its edge rows outside its range) is looked up here, so ragged tables get their own bound
+// and a lane only clamps at the top of a list, whose last entry is the largest scalar of all values from there on.  Read positions share an entry in buckets of
+// 2^kWordPosShift.  A row with row[z] = 0 < row[c] makes its entry infinite (no bound for lanes that land there); an all-zero row on a side contributes 0.
+// Rounding: an entry is stored as the smallest float not below (1 + 2^-21) times its value, and a non-zero one not below 2^-30, so that the lane's product of
+// four such floats -- three roundings of 2^-24 each, no underflow -- is still at least the product of the four values.
+struct WordScreenGeo {
+    uint32_t at[4], cap[4], stride;      // LdsPlan::bw_at, bw_cap (entries), and the entries of one table
+};
+inline WordScreenGeo word_screen_geo(const FamilyGeo &g) {
+    WordScreenGeo w{};
+    const uint32_t lim[4] = {kWordCapQuality, kWordCapBuckets, kWordCapErrors, kWordCapRate};
+    uint32_t at = 0;
+    for (uint32_t n = 0; n < 4; ++n) {
+        const uint32_t top = (g.from[n] + g.last[n]) >> (1 == n ? kWordPosShift : 0u);
+        w.at[n] = at;
+        w.cap[n] = std::min(top, lim[n]);
+        at += w.cap[n] + 1u;
+    }
+    w.stride = at;
+    return w;
+}
+// out[2 * w.stride], pairs (below, above); false: the table has no bound (every entry infinite).  *sides gets bit 0 when an entry of the lower side is not zero, bit 1 for the upper side.
+inline bool base_call_word_bounds(const DevTable &d, const double *pool, const uint8_t *par0, uint32_t base, const FamilyGeo &g, const WordScreenGeo &w, float *out, uint32_t *sides) {
+    const float inf = __builtin_inff();
+    std::fill(out, out + 2u * w.stride, inf);
+    if (!d.k || d.k > 8u || !d.f32_ok || !d.rows[0] || !d.rows[1] || !d.rows[2] || !d.rows[3]) return false;
+    uint32_t z = d.k;
+    for (uint32_t c = d.k; c--;)
+        if (par0[d.par0_off + c] == base) z = c;
+    if (z == d.k) return false;
+    const uint32_t kp = row_stride(d.k);
+    auto stored = [&](double x) {
+        if (!(x > 0.0)) return 0.f;
+        if (x > 0x1p100) return inf;
+        x *= 1.0 + 0x1p-21;
+        float f = (float)x;
+        if ((double)f < x) f = nextafterf(f, inf);
+        return f < 0x1p-30f ? 0x1p-30f : f;
+    };
+    for (uint32_t n = 0; n < 4; ++n)
+        for (uint32_t e = 0; e <= w.cap[n]; ++e) {
+            const uint32_t sh = 1 == n ? kWordPosShift : 0u, lo_v = e << sh, hi_v = e < w.cap[n] ? ((e + 1u) << sh) - 1u : std::max(lo_v, g.from[n] + g.last[n]);
+            double side[2] = {0.0, 0.0};                                // below z, above z
+            for (uint32_t v = lo_v; v <= hi_v; ++v) {
+                const int64_t own = (int64_t)v - (int64_t)d.from[n];
+                const double *row = pool + d.off[n] + (size_t)std::min<int64_t>(std::max<int64_t>(own, 0), (int64_t)d.rows[n] - 1) * kp;
+                double got[2] = {0.0, 0.0};
+                for (uint32_t c = 0; c < d.k; ++c) {
+                    if (c == z) continue;
+                    double &x = got[c > z];
+                    if (row[z] > 0.0) x = 0 == n ? x + row[c] / row[z] : std::max(x, row[c] / row[z]);
+                    else if (row[c] > 0.0) x = (double)inf;
+                }
+                side[0] = std::max(side[0], got[0]);
+                side[1] = std::max(side[1], got[1]);
+            }
+            float *o = out + 2u * (w.at[n] + e);
+            o[0] = stored(side[0]);
+            o[1] = stored(side[1]);
+        }
+    for (uint32_t n = 0; n < 4; ++n)                                    // an infinite entry counts: only its side's check keeps such a lane from being sure
+        for (uint32_t e = 0; e <= w.cap[n]; ++e) *sides |= (out[2u * (w.at[n] + e)] > 0.f ? 1u : 0u) | (out[2u * (w.at[n] + e) + 1u] > 0.f ? 2u : 0u);
+    return true;
+}
+
 inline void pack_tables(SimState &s, Uploader &up) {
     const Profile &p = s.prof;
     std::vector<double> pool;
@@ -322,6 +392,27 @@ inline void pack_tables(SimState &s, Uploader &up) {
         if (!opt.no_indel_skip)
             for (DevTable &d : indels) certain_no_indel(d);
     }
+    // ... and the base call almost always returns the template base (base_call_word_bounds above): per table the lists of scalars a lane multiplies
+    plan.bw_off = kNoLds;
+    const bool word_screen = screenable && opt.base_call_word != 0;
+    const WordScreenGeo wg = word_screen_geo(plan.b);
+    if (word_screen) {
+        std::vector<float> pairs(base_call.size() * 2u * wg.stride);
+        uint32_t sides = 0;
+        for (size_t i = 0; i < base_call.size(); ++i)
+            base_call_word_bounds(base_call[i], pool.data(), par0.data(), (uint32_t)(i / 5u % 4u), plan.b, wg, pairs.data() + i * 2u * wg.stride, &sides);
+        if (!sides) sides = 1u;                        // a table without a bound is infinite on both sides: whichever side is checked keeps its lanes from being sure
+        // pairs when some table has columns on both sides of its template base's, else the one side's numbers (half the room in the image, 32-bit loads)
+        const uint32_t width = 3u == sides ? 2u : 1u;
+        plan.bw_sides = sides;
+        plan.bw_stride = (wg.stride * width + 3u) & ~3u;
+        plan.bw_src = (uint32_t)pool32.size();
+        pool32.resize(pool32.size() + base_call.size() * plan.bw_stride, 0.f);
+        for (size_t i = 0; i < base_call.size(); ++i)
+            for (uint32_t e = 0; e < wg.stride; ++e)
+                for (uint32_t h = 0; h < width; ++h) pool32[plan.bw_src + i * plan.bw_stride + e * width + h] = pairs[(i * wg.stride + e) * 2u + (2u == width ? h : sides - 1u)];
+        for (uint32_t n = 0; n < 4; ++n) plan.bw_at[n] = wg.at[n], plan.bw_cap[n] = wg.cap[n];
+    }
     // the two families of the systematic-error chains: rows of whole quads, read from HBM
     s.dev.chain_quads = 0;
     s.dev.force_exact = opt.force_exact ? 1u : 0u;
@@ -410,6 +501,11 @@ inline void pack_tables(SimState &s, Uploader &up) {
         const uint32_t ring_stride = 4 * Ti * plan.slot_q;
         need += (uint64_t)kFillWavesMax * kRingRows * ring_stride;                              // the waves' rings
         if (need + need_rate(1, 1) > budget) return false;
+        // the word screen's scalars come before everything else that is optional: they take their room from the error-rate rows below, never from the parts above,
+        // and a plan without room for them has no word screen
+        const uint64_t need_bw = (uint64_t)20 * Ti * plan.bw_stride;
+        const bool stage_bw = word_screen && need + need_bw + need_rate(1, 1) <= budget;
+        if (stage_bw) need += need_bw;
         // what is left goes to: error-rate rows of the quality tables up to kLdsRateRowsFirst (a lane whose rate has no staged row
         // repeats its draw in double precision), the base-call margin over the number of errors, the indel margin over the indel
         // position, then more error-rate rows of both families
@@ -448,7 +544,8 @@ inline void pack_tables(SimState &s, Uploader &up) {
         plan.q3_stride = odd_stride((uint64_t)plan.rate_rows_q * plan.slot_q);
         plan.b3_stride = odd_stride((uint64_t)plan.rate_rows_b * plan.slot_b);
         plan.b3_off = plan.q3_off + 4 * Ti * plan.q3_stride;
-        plan.total_words = plan.b3_off + 20 * Ti * plan.b3_stride;
+        plan.bw_off = stage_bw ? plan.b3_off + 20 * Ti * plan.b3_stride : kNoLds;
+        plan.total_words = plan.b3_off + 20 * Ti * plan.b3_stride + (stage_bw ? (uint32_t)need_bw : 0u);
         plan.mask = plan.quads_q;
         return true;
     };
@@ -464,10 +561,13 @@ inline void pack_tables(SimState &s, Uploader &up) {
     if ((plan.desc_words | plan.q3_off | plan.b3_off | plan.ring_off | plan.ring_stride | plan.slot_q | plan.slot_b | plan.slot_i | plan.q.off32 | plan.b.off32 | plan.i.off32 |
          (plan.mask ? plan.q.lds | plan.b.lds | (plan.b.lds2 != kNoLds ? plan.b.lds2 : 0u) | (plan.i.lds != kNoLds ? plan.i.lds : 0u) : 0u)) & 3u)
         throw Error("internal: LDS rows must start on 16-byte boundaries");      // a misaligned ds_read_b128 is 2.4x slower
-    if (opt.trace_plan)
+    if (opt.trace_plan) {
         fprintf(stderr, "[rsq] LDS image: mask %u, %u of %u tiles per image, %u words (%u KiB), desc %u, quality slot %u, rate rows %u / %u, q3 %u b3 %u, ring %u x %u, b2 %d i0 %d\n", plan.mask,
                 plan.img_tiles, T, plan.total_words, plan.total_words / 256, plan.desc_words, plan.slot_q, plan.rate_rows_q, plan.rate_rows_b, plan.q3_off, plan.b3_off, plan.ring_off,
                 plan.ring_stride, (int)(plan.b.lds2 != kNoLds), (int)(plan.i.lds != kNoLds));
+        fprintf(stderr, "[rsq] word screen of the base call: %s, %u words per table (caps %u %u %u %u), %s\n", plan.bw_off != kNoLds ? "staged" : "none", plan.bw_stride, plan.bw_cap[0],
+                plan.bw_cap[1], plan.bw_cap[2], plan.bw_cap[3], 3u == plan.bw_sides ? "both ends" : (2u == plan.bw_sides ? "lower end only" : "upper end only"));
+    }
     s.dev.lds = plan;
     s.dev.quality = up.put(quality);
     s.dev.seq_quality = up.put(seq_quality);

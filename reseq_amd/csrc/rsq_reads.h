@@ -496,6 +496,34 @@ RSQ_HD int32_t geo_clamp(int32_t d, int32_t last) {
 #endif
 }
 
+// the trial program of tests/hostemu counts the base calls the random word alone decided
+#if defined(RSQ_WORD_SCREEN_STATS) && !defined(__HIP_DEVICE_COMPILE__)
+#define RSQ_WORD_SCREEN_COUNT(sure) RSQ_WORD_SCREEN_STATS(sure)
+#else
+#define RSQ_WORD_SCREEN_COUNT(sure) ((void)0)
+#endif
+
+// A base call decided by the random word alone.  a, p, e, r: the lane's four pairs of scalars (rsq_pack.h base_call_word_bounds: x = columns below the template
+// base's column z, y = columns above it), each at least (1 + 2^-21) times the largest ratio it stands for, so that b = the single-precision product of the four x
+// (three roundings of 2^-24) is at least the sum of the lower columns' products over p_z, and likewise g for the columns above.  With u = word * 2^-32 column z is
+// certain when u (1 + b) <= 1 - 1e-9 and (1 - u) (1 + g) <= 1 - 1e-9 g (pack_tables, "Draws decided by the random word alone").  In single precision:
+//  * uf = u (1 + d), |d| <= 2^-24; t = fma(uf, b, uf) >= uf (1 + b) (1 - 2^-24), so t < 1 - 2^-20 gives u (1 + b) < (1 - 2^-20) (1 + 2^-24)^2 < 1 - 2^-21;
+//  * 1 - uf is off by at most 2^-23 from 1 - u, absolutely, so with g < 512 and s = fma(1 - uf, g, 1 - uf) < 1 - 2^-13:
+//    (1 - u) (1 + g) < s (1 + 2^-23) + 513 * 2^-23 < 1 - 2^-14 + 2^-23 <= 1 - 1e-9 g.  (A lane with g of 512 and more could be sure for one word in 513.)
+// `sides` (LdsPlan::bw_sides): bit 0 = some table has a column below z, bit 1 = above; a side no table has is not checked (P0: the template base is column 0).
+// An infinite scalar ("this row has no bound") makes t or s infinite or NaN: every compare is written so that NaN is "not sure".
+RSQ_HD bool word_screen_sure(const Float2 &a, const Float2 &p, const Float2 &e, const Float2 &r, uint32_t word, uint32_t sides) {
+    const Float2 f = ((a * p) * e) * r;
+    const float uf = (float)word * 2.3283064365386963e-10f;
+    bool sure = true;
+    if (sides & 1u) sure = fma1(uf, f.x, uf) < 0.99999904632568359375f;   // 1 - 2^-20
+    if (sides & 2u) {
+        const float om = 1.f - uf;
+        sure = sure && f.y < 512.f && fma1(om, f.y, om) < 0.9998779296875f;      // 1 - 2^-13
+    }
+    return sure;
+}
+
 // QQ = quads per row of the quality family (LdsPlan::quads_q).  `t` is the step the wave is in: the quality rows over the read
 // positions t, ... t-kRingLag are in the wave's ring (lds_ring_load / lds_ring_store).  Rows are found from (table, value) by the families' common
 // geometry; a table's descriptor is read only on the double-precision route and for the rare fallbacks of FillReadPart.
@@ -550,8 +578,37 @@ struct ScreenTables {
         RSQ_SCREEN_COUNT(0, decided);
         return settle<4>(decided, RSQ_PLAN(S, q.values), local * slot + col, local, idx, u, ps);
     }
+    // The lane's scalars of the word screen (LdsPlan::bw_off): lists by VALUE -- AdjustIndeces is folded into them when they are packed --, so a lane clamps at
+    // the top only; no row address is formed.
+    RSQ_HD bool base_call_word(uint32_t local, const uint32_t (&idx)[4], uint32_t u) const {
+        if (RSQ_PLAN(S, bw_off) == kNoLds || RSQ_SIM(S, force_exact)) return false;
+        const RSQ_LDS float *mine = img + RSQ_PLAN(S, bw_off) + local * RSQ_PLAN(S, bw_stride);
+        const uint32_t sides = RSQ_PLAN(S, bw_sides);
+        auto entry = [&](uint32_t n, uint32_t value) {
+            const uint32_t e = RSQ_PLAN(S, bw_at[n]) + (value < RSQ_PLAN(S, bw_cap[n]) ? value : RSQ_PLAN(S, bw_cap[n]));
+            Float2 f;
+            if (3u == sides) f = *reinterpret_cast<const RSQ_LDS Float2 *>(mine + 2u * e);
+            else {
+                const float x = mine[e];
+                f.x = 2u == sides ? 0.f : x;
+                f.y = 2u == sides ? x : 0.f;
+            }
+            return f;
+        };
+        return word_screen_sure(entry(0, idx[0]), entry(1, idx[1] >> kWordPosShift), entry(2, idx[2]), entry(3, idx[3]), u, sides);
+    }
     RSQ_HD uint32_t draw_base_call(uint32_t i, const uint32_t (&idx)[4], uint32_t u, uint32_t &ps) const {
-        const uint32_t local = i - qbase * 5u, slot = RSQ_PLAN(S, slot_b), nr = RSQ_PLAN(S, rate_rows_b), r3 = RSQ_GEO_ROW(S, b, 3, idx[3]);
+        const uint32_t local = i - qbase * 5u;
+        // nearly every draw: the random word alone says "the template base" (the table's base: tables come five to a base, four bases to a tile).  Such a lane
+        // reads four scalars and no row; the others draw among themselves, and a wave without one skips the branch (s_cbranch_execz)
+        const bool sure = base_call_word(local, idx, u);
+        RSQ_WORD_SCREEN_COUNT(sure);
+        if (sure) {
+            RSQ_SCREEN_COUNT(1, true);
+            ps = 1u;
+            return ((local * 52429u) >> 18) & 3u;              // local / 5 % 4 (local is far below 2^16: the image's tables fit LDS)
+        }
+        const uint32_t slot = RSQ_PLAN(S, slot_b), nr = RSQ_PLAN(S, rate_rows_b), r3 = RSQ_GEO_ROW(S, b, 3, idx[3]);
         const uint32_t g = 4u * (RSQ_PLAN(S, b.off32) + i * (RSQ_PLAN(S, b.table_rows) * slot));               // the table's rows in device memory: bytes from the pool's address (below 4 GB: pack_tables)
         const LdsRow32 m0{img + RSQ_PLAN(S, b.lds) + local * RSQ_PLAN(S, b.lds_stride) + RSQ_GEO_ROW(S, b, 0, idx[0]) * slot};
         const PoolRow32 m1{S.pool32, g + 4u * (RSQ_PLAN(S, b.before[1]) + RSQ_GEO_ROW(S, b, 1, idx[1])) * slot};
@@ -641,6 +698,11 @@ RSQ_HD void lds_stage_rows(const DevSim &S, RSQ_LDS float *img, uint32_t qbase, 
                           nthreads);
     lds_stage_family_rows(S, img, RSQ_PLAN(S, b.off32), RSQ_PLAN(S, b.table_rows), qbase * 5u, 20u * T, RSQ_PLAN(S, b.before[3]), RSQ_PLAN(S, rate_rows_b), sb, RSQ_PLAN(S, b3_off), RSQ_PLAN(S, b3_stride), tid,
                           nthreads);
+    // the word screen's scalars of the image's base-call tables: one contiguous piece of the pool
+    if (RSQ_PLAN(S, bw_off) != kNoLds) {
+        const float *src = S.pool32 + RSQ_PLAN(S, bw_src) + (size_t)qbase * 5u * RSQ_PLAN(S, bw_stride);
+        for (uint32_t i = tid; i < 20u * T * RSQ_PLAN(S, bw_stride); i += nthreads) img[RSQ_PLAN(S, bw_off) + i] = src[i];
+    }
 }
 // The ring: the quality rows (margin 2) over read position p of the segment's tables, copied by the wave itself at the beginning of
 // step p into slot p % kRingSlots of its ring: one load of 16 bytes per lane instead of one per lane and quad of the row.  Item i is

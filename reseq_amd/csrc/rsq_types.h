@@ -141,7 +141,19 @@ struct LdsPlan {
     uint32_t ring_off, ring_stride;      // per wave: kRingRows x [4 img_tiles quality slots]: the quality rows over the read positions of the wave's current steps, and one slot staged on demand
     uint32_t total_words;        // size of the image
     FamilyGeo q, b, i;           // the three families' common geometry
+    // Base calls decided by the random word alone (rsq_pack.h base_call_word_bounds, ScreenTables::base_call_word): per base-call table of the image bw_stride words
+    // at bw_off: a list of scalars per quality VALUE 0 .. bw_cap[0], then from entry bw_at[n] on a list per bucket of 2^kWordPosShift read positions, per number
+    // of errors and per error rate, each list's last entry standing for everything beyond it.  An entry is a pair (columns below the template base's, columns above
+    // it) when the profile has tables with columns on both sides (bw_sides == 3), else the one number of the side there is.  bw_off == kNoLds: the image has none
+    // (option base_call_word 0, or no room beside the required parts).
+    uint32_t bw_off, bw_stride;
+    uint32_t bw_src;             // DevSim::pool32: the same for all base-call tables of the profile, [table][bw_stride]
+    uint32_t bw_at[4], bw_cap[4];        // bw_at[0] is 0; bw_cap[1] counts buckets
+    uint32_t bw_sides;           // bit 0: some table has outcome columns below its template base's (the upper end of the word's range is checked), bit 1: above (the lower end)
 };
+// buckets of 2^kWordPosShift read positions, and the largest quality value / bucket / number of errors / error rate with scalars of their own (chosen from the
+// measurement in DESIGN_LOG.md section 24)
+constexpr uint32_t kWordPosShift = 4, kWordCapQuality = 95, kWordCapBuckets = 63, kWordCapErrors = 3, kWordCapRate = 63;
 
 // Fragment produced by the coverage sieve: one simulated read pair (Simulator.cpp:2249-2357 -> CreateReads).
 struct Fragment {
