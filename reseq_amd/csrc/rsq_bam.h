@@ -105,28 +105,7 @@ RSQ_HD void bam_fixed(const Fragment &f, const ReadMeta &m, const SamMate &w, co
     bam_fixed_span(f, m, (uint32_t)w.t - w.lead - w.trail, a, l_read_name, n_cigar, block_size, t);
 }
 
-// four base codes, one per byte (0..3 ACGT, 4 N) -> their 4-bit codes, one per byte; complement: of the complementary bases
-RSQ_HD uint32_t bam_nibbles(uint32_t codes, bool complement) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_perm(0x0F0F0F0Fu, complement ? 0x01020408u : 0x08040201u, codes);      // selector 0-3: the table's bytes, 4-7: N
-#else
-    uint32_t out = 0;
-    for (uint32_t k = 0; k < 4u; ++k) {
-        const uint32_t b = (codes >> (8u * k)) & 0xFFu;
-        out |= (b < 4u ? (complement ? 8u >> b : 1u << b) : 15u) << (8u * k);
-    }
-    return out;
-#endif
-}
-// eight 4-bit codes, one per byte of (n1 : n0) -> four bytes, the earlier code of a pair in the high nibble
-RSQ_HD uint32_t bam_pack(uint32_t n0, uint32_t n1) {
-    const uint32_t x0 = (n0 << 4) | (n0 >> 8), x1 = (n1 << 4) | (n1 >> 8);      // bytes 0 and 2 hold the pairs (0, 1) and (2, 3)
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_perm(x1, x0, 0x06040200u);
-#else
-    return (x0 & 0xFFu) | ((x0 >> 8) & 0xFF00u) | ((x1 & 0xFFu) << 16) | ((x1 << 8) & 0xFF000000u);
-#endif
-}
+// (bam_nibbles: four base codes -> their 4-bit codes; bam_pack: eight 4-bit codes -> four bytes; both rsq_portable.h)
 // SEQ: the row's words in output order (sam_line's walk), two of them an output word.  What lies behind the row's last code becomes nibble 0.
 template <class Sink>
 RSQ_HD void bam_seq(const WordColumn &row, uint32_t read_len, bool reverse, Sink &t) {

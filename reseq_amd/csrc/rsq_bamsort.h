@@ -323,7 +323,7 @@ __global__ void k_bam_cut(const uint64_t *keys, uint64_t n, uint64_t cut, uint64
 }
 
 // The kernel that moves the bytes.  Sixteen lanes a record (100 - 400 bytes, any alignment at both ends): a lane stores aligned 16-byte words of the destination,
-// each fed from the two neighbouring aligned 16-byte words of the source through the byte funnel (sam_funnel: v_alignbyte_b32); the ragged bytes in front of
+// each fed from the two neighbouring aligned 16-byte words of the source through the byte funnel (align_bytes: v_alignbyte_b32); the ragged bytes in front of
 // the first and behind the last aligned word are written one a lane.  Every byte of the destination is written by exactly one lane.  The source's second word
 // may lie behind the record: the staging buffers end with 32 spare bytes.
 __device__ __forceinline__ void bam_copy_record(char *dst, const char *src, uint32_t size, uint32_t lane) {
@@ -343,10 +343,10 @@ __device__ __forceinline__ void bam_copy_record(char *dst, const char *src, uint
                        e2 = q == 0u ? lo.z : q == 1u ? lo.w : q == 2u ? hi.x : hi.y, e3 = q == 0u ? lo.w : q == 1u ? hi.x : q == 2u ? hi.y : hi.z,
                        e4 = q == 0u ? hi.x : q == 1u ? hi.y : q == 2u ? hi.z : hi.w;
         uint4 o;
-        o.x = sam_funnel(e1, e0, r);
-        o.y = sam_funnel(e2, e1, r);
-        o.z = sam_funnel(e3, e2, r);
-        o.w = sam_funnel(e4, e3, r);
+        o.x = align_bytes(e1, e0, r);
+        o.y = align_bytes(e2, e1, r);
+        o.z = align_bytes(e3, e2, r);
+        o.w = align_bytes(e4, e3, r);
         *reinterpret_cast<uint4 *>(a) = o;
     }
 }

@@ -11,9 +11,6 @@
 // CPU against the oracle without a GPU.  The shipped library only ever calls them from kernels.
 #pragma once
 #include "rsq_types.h"
-#if !defined(__HIPCC_RTC__)
-#include <math.h>
-#endif
 
 namespace rsq {
 
@@ -57,20 +54,7 @@ RSQ_HD uint32_t pair_c3(uint32_t dom, uint32_t strand, uint32_t segsel, uint32_t
 // ------------------------------------------------------------------------- integer helpers (utilities.hpp)
 RSQ_HD bool is_gc(uint32_t b) { return b == 1 || b == 2; }
 RSQ_HD uint32_t divide_u32(uint32_t nom, uint32_t den) { return (nom + den / 2u) / den; }          // :450-452
-// x / d for x < 2^24, 1 <= d and a quotient below 2^17 (the percentages: at most 65535 + d / 2 over d).  The device has no integer division: the compiler's
-// sequence for a 32-bit one is about 28 instructions.  Here: both operands are exact in single precision, the product with the reciprocal (1 ulp) is off by less than
-// 2^17 * 2^-22 of the true quotient, so its integer part is the quotient or one beside it, and the remainder says which.
-RSQ_HD uint32_t div_small(uint32_t x, uint32_t d) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    uint32_t q = (uint32_t)((float)x * __builtin_amdgcn_rcpf((float)d));
-    const int32_t r = (int32_t)(x - q * d);
-    if (r < 0) --q;
-    else if ((uint32_t)r >= d) ++q;
-    return q;
-#else
-    return x / d;
-#endif
-}
+// (div_small, rsq_portable.h: x / d for x < 2^24 and a quotient below 2^17)
 RSQ_HD uint32_t percent_u16(uint32_t nom, uint32_t den) {                                            // :552-554, T = uint16_t
     uint32_t n100 = (nom * 100u) & 0xFFFFu;
     return (div_small(n100 + den / 2u, den) & 0xFFFFu) & 0xFFu;
@@ -93,12 +77,6 @@ RSQ_HD uint32_t discrete_draw(const double *cp, uint32_t n, double u) {
 // sum exceeds u*prob_sum.  Nothing is kept between the passes, so K is unbounded and the lane needs no per-outcome
 // registers.  Rows have an even stride (zero pad column), so both passes read two columns per 16-byte load; the pad
 // column adds +0.0 to prob_sum in pass 1 (exact) and is skipped in pass 2.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define RSQ_LDS __attribute__((address_space(3)))
-#else
-#define RSQ_LDS
-#endif
-
 struct alignas(16) Pair {
     double x, y;
 };
@@ -107,13 +85,6 @@ struct GlobalRow {                     // a margin row in HBM (read through L1/L
     const double *p;
     RSQ_HD Pair pair(uint32_t j) const { return *reinterpret_cast<const Pair *>(p + 2u * j); }
 };
-#if defined(__HIP_DEVICE_COMPILE__)
-// the wave's ballot of a predicate is the compare's own result (s_and with exec); __any() takes an int, so the predicate went to a register, was compared again,
-// and the mask took a trip through vcc: three vector instructions per use, four uses in a step
-#define RSQ_ANY(x) (__builtin_amdgcn_ballot_w64(x) != 0ull)
-#else
-#define RSQ_ANY(x) (x)
-#endif
 
 // Both passes work on CHUNKS of U column pairs: all row loads of a chunk are issued before the first product is formed
 // (the loops are latency-bound otherwise).  Rows are zero-padded to whole chunks (row_stride), so no chunk needs a
@@ -221,25 +192,8 @@ RSQ_HD uint32_t draw_rows_k(uint32_t K, double u, double &prob_sum, const Rs &..
 // Preconditions, checked when the tables are packed (DevTable::f32_ok) and here: values are 0 or in [2^-60, 2^29] (no overflow;
 // an intermediate product that underflows -- (r0*r1) itself below 2^-126, i.e. two factors near 2^-60 and below -- is lost entirely: at most 2^-68 absolutely after the
 // largest factors 2^29 * 2^29, far below delta >= 2^-30 * 2^-20 * 2^-19; this assumes gradual or flushed underflow alike, no other denormal mode) and S32 >= 2^-30.
-// The FMAs are explicit (fma2 / fma1): the screen never leaves contraction to the compiler, and the double-precision recipe above is built with -ffp-contract=off.
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef float Float2 __attribute__((ext_vector_type(2)));      // v_pk_mul_f32 / v_pk_add_f32
-#else
-struct Float2 {
-    float x, y;
-};
-inline Float2 operator*(const Float2 &a, const Float2 &b) { return Float2{a.x * b.x, a.y * b.y}; }
-inline Float2 operator+(const Float2 &a, const Float2 &b) { return Float2{a.x + b.x, a.y + b.y}; }
-#endif
-// a * b + c with one rounding: v_pk_fma_f32 / v_fma_f32 on the device, the correctly rounded fmaf on the host (the emulation decides as the device does)
-RSQ_HD Float2 fma2(const Float2 &a, const Float2 &b, const Float2 &c) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_elementwise_fma(a, b, c);
-#else
-    return Float2{__builtin_fmaf(a.x, b.x, c.x), __builtin_fmaf(a.y, b.y, c.y)};
-#endif
-}
-RSQ_HD float fma1(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+// The FMAs are explicit (fma2 / fma1 on Float2 and float, rsq_portable.h): the screen never leaves contraction to the compiler, and the double-precision recipe
+// above is built with -ffp-contract=off.
 struct alignas(16) Quad {              // columns 4c .. 4c+3 of a row: lo = (4c, 4c+1), hi = (4c+2, 4c+3)
     Float2 lo, hi;
 };
@@ -287,11 +241,6 @@ RSQ_HD QuadFactors quad_factors(uint32_t c, const R0 &r0, const R1 &r1, const R2
     const Quad a = r0.quad(c), b = r1.quad(c), d = r2.quad(c), e = r3.quad(c);
     return QuadFactors{mul_quad(mul_quad(a, b), d), e};
 }
-#if defined(__HIP_DEVICE_COMPILE__)
-#define RSQ_SCHED_BARRIER() __builtin_amdgcn_sched_barrier(0)
-#else
-#define RSQ_SCHED_BARRIER() ((void)0)
-#endif
 #ifndef RSQ_SCREEN_BATCH
 #define RSQ_SCREEN_BATCH 1
 #endif
@@ -369,12 +318,7 @@ RSQ_HD bool draw_screened(uint32_t word, uint32_t &col, const Rs &...rs) {
 // AdjustIndeces (:368-380): v < from ? 0 : (v - from >= rows ? rows - 1 : v - from), as a signed difference held between 0 and rows - 1 (values, first values
 // and row counts are far below 2^31; a table that is drawn from has rows): one subtraction and a median of three on the device instead of two compares and two selects
 RSQ_HD uint32_t clamp_row(const DevTable &t, int n, uint32_t v) {
-    const int32_t d = (int32_t)v - (int32_t)t.from[n], last = (int32_t)t.rows[n] - 1;
-#if defined(__clang__)
-    return (uint32_t)__builtin_elementwise_min(__builtin_elementwise_max(d, 0), last);
-#else
-    return (uint32_t)(d < 0 ? 0 : (d > last ? last : d));
-#endif
+    return (uint32_t)clamp_from_zero((int32_t)v - (int32_t)t.from[n], (int32_t)t.rows[n] - 1);
 }
 
 // generic draw with every margin in HBM; returns the outcome VALUE
@@ -437,11 +381,7 @@ RSQ_HD uint32_t ref_gc_count(const uint64_t *__restrict__ words, uint64_t word_o
         uint32_t hi = w == ((b - 1) >> 5) ? ((b - 1) & 31u) + 1u : 32u;
         if (lo) g &= ~0ull << (2u * lo);
         if (hi < 32u) g &= (1ull << (2u * hi)) - 1ull;
-#if defined(__HIP_DEVICE_COMPILE__)
-        gc += (uint32_t)__popcll(g);
-#else
-        gc += (uint32_t)__builtin_popcountll(g);
-#endif
+        gc += popcount64(g);
     }
     return gc;
 }
@@ -449,12 +389,7 @@ RSQ_HD uint32_t ref_gc_count(const uint64_t *__restrict__ words, uint64_t word_o
 // the same count from the per-word running totals built by pack_reference (gc_prefix[w] = G/C in words [0, w) of the sequence):
 // four independent loads instead of a loop over up to 32 words
 RSQ_HD uint32_t gc_low(uint64_t x, uint32_t n_bases) {            // G/C among the lowest n_bases (< 32) bases of a word
-    const uint64_t g = (x ^ (x >> 1)) & 0x5555555555555555ull & ((1ull << (2u * n_bases)) - 1ull);
-#if defined(__HIP_DEVICE_COMPILE__)
-    return (uint32_t)__popcll(g);
-#else
-    return (uint32_t)__builtin_popcountll(g);
-#endif
+    return popcount64((x ^ (x >> 1)) & 0x5555555555555555ull & ((1ull << (2u * n_bases)) - 1ull));
 }
 RSQ_HD uint32_t ref_gc_count_prefix(const uint64_t *__restrict__ words, const uint32_t *__restrict__ gc_prefix, uint64_t word_off, uint32_t a, uint32_t b) {
     const uint32_t wa = a >> 5, wb = b >> 5;
@@ -474,12 +409,7 @@ RSQ_HD uint64_t ref_bits60(const uint64_t *__restrict__ words, uint64_t word_off
 }
 // ten bases packed first-base-lowest -> the reference's code with the first base most significant
 RSQ_HD uint32_t reverse_ten_bases(uint32_t g) {
-    uint32_t r = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-    r = __brev(g) >> 12;
-#else
-    for (uint32_t i = 0; i < 20u; ++i) r |= ((g >> i) & 1u) << (19u - i);
-#endif
+    const uint32_t r = bit_reverse32(g) >> 12;
     return ((r & 0x55555u) << 1) | ((r >> 1) & 0x55555u);         // the two bits of every base back in order
 }
 // `wrap_words`: with variants `words` is an allele's copy of the reference; the bases a window takes from beyond a sequence end

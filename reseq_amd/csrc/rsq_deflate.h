@@ -40,14 +40,6 @@
 
 #include "rsq_types.h"
 
-#ifndef RSQ_LDS
-#if defined(__HIP_DEVICE_COMPILE__)
-#define RSQ_LDS __attribute__((address_space(3)))
-#else
-#define RSQ_LDS
-#endif
-#endif
-
 namespace rsq {
 namespace gz {
 
@@ -83,22 +75,8 @@ RSQ_HD uint32_t hash4(uint32_t v) { return (v * 2654435761u) >> (32u - kHashBits
 // window by chance, and the chance candidate -- the latest -- hides the read that truly overlaps; six bytes recur by chance once in 4096 positions.  (Measured on P0's
 // text: 2.74 x smaller with four bytes, 2.91 x with six, 2.89 x with eight; the shortest match found this way is six bytes, which is about where a match begins to pay.)
 RSQ_HD uint32_t hash6(uint32_t v, uint32_t more) { return hash4(v ^ ((more & 0xFFFFu) * 0x9E3779B1u)); }
-RSQ_HD uint32_t load4(const uint8_t *p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return *reinterpret_cast<const uint32_t __attribute__((aligned(1))) *>(p);
-#else
-    uint32_t v;
-    memcpy(&v, p, 4);
-    return v;
-#endif
-}
-RSQ_HD uint32_t low_zero_bytes(uint32_t x) {           // number of low bytes of x that are zero (x != 0)
-#if defined(__HIP_DEVICE_COMPILE__)
-    return (uint32_t)__builtin_ctz(x) >> 3;
-#else
-    return (uint32_t)__builtin_ctz(x) >> 3;
-#endif
-}
+RSQ_HD uint32_t load4(const uint8_t *p) { return load_as<uint32_t, 1>(p); }
+RSQ_HD uint32_t low_zero_bytes(uint32_t x) { return (uint32_t)__builtin_ctz(x) >> 3; }      // number of low bytes of x that are zero (x != 0)
 // Where the walk reads the piece: plain memory (the host), or the ring of its last kRing bytes in LDS (the device; byte p at p mod kRing, the ring's first
 // bytes repeated behind its end so that a word may begin on its last three bytes)
 struct PlainText {
@@ -133,15 +111,9 @@ struct RingText {
     const RSQ_LDS uint8_t *ring;
     RSQ_HD uint32_t byte(uint32_t p) const { return ring[ring_index(p)]; }
     RSQ_HD uint32_t word(uint32_t p) const {
-#if defined(__HIP_DEVICE_COMPILE__)
         // two aligned words and a byte shift: an unaligned word would be read byte by byte
         const RSQ_LDS uint32_t *w = reinterpret_cast<const RSQ_LDS uint32_t *>(ring) + (ring_index(p) >> 2);
-        return __builtin_amdgcn_alignbyte(w[1], w[0], p & 3u);
-#else
-        uint32_t v;
-        memcpy(&v, ring + ring_index(p), 4);
-        return v;
-#endif
+        return align_bytes(w[1], w[0], p & 3u);
     }
 };
 // the match of `len` bytes (so far) at p, `dist` back, to its end: at most `most` bytes in all
@@ -277,9 +249,7 @@ RSQ_HD void found_at(const uint32_t *found, uint32_t i, uint32_t &len, uint32_t 
 template <uint32_t STEP, class Sink>
 RSQ_HD void walk_segment(const SegmentT<STEP> &g, uint32_t n, Sink &sink) {
     uint32_t skip = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
+    RSQ_UNROLL
     for (uint32_t i = 0; i < kSeg; ++i) {
         const uint32_t c = (g.text[i >> 2] >> ((i & 3u) * 8u)) & 0xFFu;
         const bool searched = (g.kind >> i) & 1u;

@@ -39,37 +39,13 @@ constexpr uint64_t kOnes = 0x0101010101010101ull, kHighs = 0x8080808080808080ull
 // bytes [off, off + 8) of a record of `size` bytes, zeros beyond it
 // (P: pointer to the text's bytes -- const uint8_t * or, on the device, the same in LDS)
 template <class P>
-struct WordOf;
-template <>
-struct WordOf<const uint8_t *> {
-    typedef const uint64_t __attribute__((aligned(1))) *type;
-};
-#if defined(__HIP_DEVICE_COMPILE__)
-template <>
-struct WordOf<const RSQ_LDS uint8_t *> {
-    typedef const RSQ_LDS uint64_t __attribute__((aligned(1))) *type;
-};
-#endif
-template <class P>
 RSQ_HD uint64_t word_at(P rec, uint64_t off, uint64_t size) {
+    if (off + 8u <= size) return load_as<uint64_t, 1>(rec + off);
     uint64_t w = 0;
-    if (off + 8u <= size) {
-#if defined(__HIP_DEVICE_COMPILE__)
-        w = *reinterpret_cast<typename WordOf<P>::type>(rec + off);          // unaligned 8-byte loads are what the hardware does (amdhsa)
-#else
-        for (uint32_t j = 0; j < 8u; ++j) w |= (uint64_t)rec[off + j] << (8u * j);
-#endif
-    } else
-        for (uint32_t j = 0; off + j < size; ++j) w |= (uint64_t)rec[off + j] << (8u * j);
+    for (uint32_t j = 0; off + j < size; ++j) w |= (uint64_t)rec[off + j] << (8u * j);
     return w;
 }
-RSQ_HD void store_word(uint8_t *dst, uint64_t w) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    *reinterpret_cast<uint64_t __attribute__((aligned(1))) *>(dst) = w;
-#else
-    for (uint32_t j = 0; j < 8u; ++j) dst[j] = (uint8_t)(w >> (8u * j));
-#endif
-}
+RSQ_HD void store_word(uint8_t *dst, uint64_t w) { store_as<uint64_t, 1>(dst, w); }
 // the first position >= from of byte c in the record, or size
 template <class P>
 RSQ_HD uint64_t find_byte(P rec, uint64_t from, uint64_t size, uint8_t c) {

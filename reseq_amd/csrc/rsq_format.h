@@ -7,8 +7,6 @@
 //   k_format_write                                              FASTQ text: one wave per 16 records                 (Simulator.cpp:596-632, a5)
 //   k_record_text_sizes, k_record_text_waves                    seqToIllumina records: their FASTQ text             (Simulator.cpp:2497-2504)
 #pragma once
-#include <string.h>
-
 #include "rsq_reads.h"
 
 namespace rsq {
@@ -20,42 +18,9 @@ namespace rsq {
 // WaveImage (or, on the host, a byte buffer whose first byte lies on a word boundary), which the wave ZEROES first: a lane then ORs aligned words into it.  The
 // bytes of a word that belong to a neighbouring part are zero in the lane's own word, so a word shared by two parts needs no special case, in either order,
 // and the first and last partial word of a part are dealt with where the part begins (the sink starts with the phase of its address) and in finish().  They
-// stay host/device functions: tests/hostemu/text_trial.cpp runs them on the CPU against format_record.
-RSQ_HD void image_or(RSQ_LDS uint32_t *w, uint32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __hip_atomic_fetch_or(w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);      // result unused: ds_or_b32 without return
-#else
-    uint32_t x;
-    memcpy(&x, w, 4);
-    x |= v;
-    memcpy(w, &x, 4);
-#endif
-}
-// the four bytes of (hi : lo) from byte `at` on, at <= 4: one byte permute whose selector depends on `at` alone (a part's phase: computed once)
-RSQ_HD uint32_t image_bytes_at(uint32_t hi, uint32_t lo, uint32_t at) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_perm(hi, lo, 0x03020100u + at * 0x01010101u);
-#else
-    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8u * at));
-#endif
-}
-RSQ_HD uint32_t image_word(const uint32_t *p) {               // a word of text that is kept as characters
-#if defined(__HIP_DEVICE_COMPILE__)
-    return *p;
-#else
-    uint32_t x;
-    memcpy(&x, p, 4);
-    return x;
-#endif
-}
-// true for any lane of the wave that is here (the host: the caller's own): skips work that no lane needs without a divergent branch
-RSQ_HD bool image_any(bool p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __any(p) != 0;
-#else
-    return p;
-#endif
-}
+// stay host/device functions: tests/hostemu/text_trial.cpp runs them on the CPU against format_record.  What they rest on is in rsq_portable.h: image_or (the OR
+// into the image), bytes_at (four bytes of a pair of words from a part's phase on) and wave_any (skips work that no lane of the wave needs without a divergent branch).
+RSQ_HD uint32_t image_word(const uint32_t *p) { return load_as<uint32_t, 4>(p); }      // a word of text that is kept as characters
 RSQ_HD constexpr uint32_t chars4(char a, char b = 0, char c = 0, char d = 0) {
     return (uint32_t)(uint8_t)a | ((uint32_t)(uint8_t)b << 8) | ((uint32_t)(uint8_t)c << 16) | ((uint32_t)(uint8_t)d << 24);
 }
@@ -134,12 +99,12 @@ struct ImageSink {
         uint32_t i = 0;
         for (; i + 4u <= len; i += 4u, ++next) {               // the stream: len bytes from byte a of (low, from[next], ...)
             const uint32_t high = a + len > i + 4u ? image_word(from + next) : 0u;
-            push4(image_bytes_at(high, low, a));
+            push4(bytes_at(high, low, a));
             low = high;
         }
         uint32_t rest = len - i;
         const uint32_t high = a + len > i + 4u ? image_word(from + next) : 0u;
-        uint32_t word = image_bytes_at(high, low, a) & ((1u << (8u * rest)) - 1u);
+        uint32_t word = bytes_at(high, low, a) & ((1u << (8u * rest)) - 1u);
         if (tail) {
             word |= tail << (8u * rest);
             ++rest;
@@ -149,10 +114,10 @@ struct ImageSink {
     // decimal digits without a loop: four at a time by multiply and shift, their number from compares, the leading zeros shifted out; `tail`: tail_len <= 4
     // characters behind the number (the fixed text that follows it) in the same pushes
     RSQ_HD void num(uint32_t v, uint32_t tail = 0, uint32_t tail_len = 0) {
-        if (!image_any(v >= 10000u)) {                         // the common number
+        if (!wave_any(v >= 10000u)) {                         // the common number
             const uint32_t digits = count_digits4(v), total = digits + tail_len, at = 4u - digits;
-            push(image_bytes_at(tail, four_digits(v), at), total < 4u ? total : 4u);
-            if (image_any(total > 4u)) push(tail >> (8u * at), total > 4u ? total - 4u : 0u);
+            push(bytes_at(tail, four_digits(v), at), total < 4u ? total : 4u);
+            if (wave_any(total > 4u)) push(tail >> (8u * at), total > 4u ? total - 4u : 0u);
             return;
         }
         const uint32_t upper = v / 10000u, hi = upper / 10000u, mid = upper - 10000u * hi;
@@ -160,10 +125,10 @@ struct ImageSink {
         const uint32_t x[4] = {four_digits(hi), four_digits(mid), four_digits(v - 10000u * upper), tail};      // twelve characters and the tail: skip 12 - digits
         const uint32_t skip = 12u - digits, sw = skip >> 2, at = skip & 3u, total = digits + tail_len;
         const uint32_t x0 = sw == 0u ? x[0] : sw == 1u ? x[1] : x[2], x1 = sw == 0u ? x[1] : sw == 1u ? x[2] : x[3], x2 = sw == 0u ? x[2] : sw == 1u ? x[3] : 0u, x3 = sw == 0u ? x[3] : 0u;
-        push(image_bytes_at(x1, x0, at), total < 4u ? total : 4u);
-        push(image_bytes_at(x2, x1, at), total < 4u ? 0u : total < 8u ? total - 4u : 4u);
-        if (image_any(total > 8u)) push(image_bytes_at(x3, x2, at), total < 8u ? 0u : total < 12u ? total - 8u : 4u);
-        if (image_any(total > 12u)) push(x3 >> (8u * at), total < 12u ? 0u : total - 12u);
+        push(bytes_at(x1, x0, at), total < 4u ? total : 4u);
+        push(bytes_at(x2, x1, at), total < 4u ? 0u : total < 8u ? total - 4u : 4u);
+        if (wave_any(total > 8u)) push(bytes_at(x3, x2, at), total < 8u ? 0u : total < 12u ? total - 8u : 4u);
+        if (wave_any(total > 12u)) push(x3 >> (8u * at), total < 12u ? 0u : total - 12u);
     }
     RSQ_HD void nine_digits(uint32_t v) {                      // v < 10^9 with its leading zeros
         const uint32_t upper = v / 10000u, hi = upper / 10000u;
@@ -231,7 +196,7 @@ RSQ_HD void image_line_part(const WordColumn &row, uint32_t read_len, bool is_qu
 #pragma unroll
             for (uint32_t k = 0; k < kAhead; ++k) {
                 const uint32_t text = is_qual ? w[k] : base_letters(w[k]);
-                image_or(out + i + k, image_bytes_at(text, before, at));
+                image_or(out + i + k, bytes_at(text, before, at));
                 before = text;
             }
         } else {
@@ -241,7 +206,7 @@ RSQ_HD void image_line_part(const WordColumn &row, uint32_t read_len, bool is_qu
             for (uint32_t k = 0; k < kAhead; ++k) {
                 if (i + k < full) {
                     const uint32_t text = is_qual ? w[k] : base_letters(w[k]);
-                    image_or(out + i + k, image_bytes_at(text, before, at));
+                    image_or(out + i + k, bytes_at(text, before, at));
                     before = text;
                 }
             }
@@ -256,9 +221,9 @@ RSQ_HD void image_line_part(const WordColumn &row, uint32_t read_len, bool is_qu
         x |= (is_qual ? last : base_letters(last)) & ((1u << (8u * rest)) - 1u);
     }
     const uint32_t x0 = (uint32_t)x, x1 = (uint32_t)(x >> 32);
-    if (used > 0u) image_or(out + full, image_bytes_at(x0, before, at));
-    if (used > 4u) image_or(out + full + 1u, image_bytes_at(x1, x0, at));
-    if (used > 8u) image_or(out + full + 2u, image_bytes_at(0u, x1, at));
+    if (used > 0u) image_or(out + full, bytes_at(x0, before, at));
+    if (used > 4u) image_or(out + full + 1u, bytes_at(x1, x0, at));
+    if (used > 8u) image_or(out + full + 2u, bytes_at(0u, x1, at));
 }
 
 #ifndef RSQ_FORMAT_RECORDS

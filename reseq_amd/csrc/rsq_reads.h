@@ -69,9 +69,7 @@ struct WaveReadOut {
     RSQ_HD uint32_t *at(uint32_t *base, uint32_t w) const {      // word w of the lane's row of array `base`
         if (wide) {
             uint32_t r = row;
-#if defined(__HIP_DEVICE_COMPILE__)
-            asm volatile("" : "+v"(r));      // or the compiler carries base + row, a 64-bit address per array, through the steps for this branch
-#endif
+            RSQ_KEEP_IN_VGPR(r);             // or the compiler carries base + row, a 64-bit address per array, through the steps for this branch
             return base + ((uint64_t)w * pitch + r);
         }
         return reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(base) + read_out_offset(w, pitch, row));
@@ -151,11 +149,7 @@ struct FragmentSrc {                    // template of one mate cut from the 2-b
     RSQ_HD uint32_t sys_base(uint32_t k) const {
         if ((k >> 2) != held_sys) {
             held_sys = k >> 2;
-#if defined(__HIP_DEVICE_COMPILE__)
-            sys4 = *reinterpret_cast<const uint64_t __attribute__((aligned(2))) *>(sys_ + (k & ~3u));
-#else
-            memcpy(&sys4, sys_ + (k & ~3u), 8);
-#endif
+            sys4 = load_as<uint64_t, 2>(sys_ + (k & ~3u));
         }
         return (uint32_t)(sys4 >> ((k & 3u) * 16u)) & 0xFFFFu;
     }
@@ -175,12 +169,7 @@ struct FragmentSrc {                    // template of one mate cut from the 2-b
         };
         uint32_t sum = 0;
         for (uint32_t k = 0; k < n; k += 8u) {
-            Eight e;
-#if defined(__HIP_DEVICE_COMPILE__)
-            e = *reinterpret_cast<const Eight *>(sys_ + k);
-#else
-            memcpy(&e, sys_ + k, 16);
-#endif
+            Eight e = load_as<Eight, 2>(sys_ + k);
             const uint32_t left = n - k;                               // entries of this group that count
             if (left < 8u) {
                 if (left <= 4u) {
@@ -233,12 +222,7 @@ struct WaveFragmentSrc {
     RSQ_HD uint32_t sys_base(uint32_t k) const {
         if ((k >> 2) != held_sys) {
             held_sys = k >> 2;
-            const uint16_t *p = sys_at(k & ~3u);
-#if defined(__HIP_DEVICE_COMPILE__)
-            sys4 = *reinterpret_cast<const uint64_t __attribute__((aligned(2))) *>(p);
-#else
-            memcpy(&sys4, p, 8);
-#endif
+            sys4 = load_as<uint64_t, 2>(sys_at(k & ~3u));
         }
         return (uint32_t)(sys4 >> ((k & 3u) * 16u)) & 0xFFFFu;
     }
@@ -312,11 +296,7 @@ RSQ_HD void ct_convert_run(uint64_t *tmpl, uint32_t t, uint32_t n, double rate, 
         uint64_t cs = tmpl[w] & ~(tmpl[w] >> 1) & 0x5555555555555555ull;
         cs &= (hi == 32u ? ~0ull : (1ull << (2u * hi)) - 1ull) & ~((1ull << (2u * lo)) - 1ull);
         while (cs) {
-#if defined(__HIP_DEVICE_COMPILE__)
-            const uint32_t bit = (uint32_t)__ffsll((long long)cs) - 1u;
-#else
-            const uint32_t bit = (uint32_t)__builtin_ctzll(cs);
-#endif
+            const uint32_t bit = lowest_set_bit64(cs);
             cs &= cs - 1ull;
             if (d.uniform((w << 5) + (bit >> 1)) < rate) tmpl[w] |= (uint64_t)3u << bit;                             // C (1) -> T (3)
         }
@@ -454,13 +434,8 @@ RSQ_HD uint32_t lds_desc_count(uint32_t n_tiles) { return 25u * n_tiles + 12u; }
 RSQ_HD uint32_t image_qbase(const DevSim &S, uint32_t seg, uint32_t first_tile) { return (seg * RSQ_SIM(S, n_tiles) + first_tile) * 4u; }
 constexpr uint32_t kDescWords = sizeof(DevTable) / 4u;
 
-#if defined(__HIP_DEVICE_COMPILE__)
-#define RSQ_NOINLINE __device__ __noinline__
-#else
-#define RSQ_NOINLINE inline
-#endif
 // the host emulation counts what the screen decided (tests/hostemu): [family][0 = draws, 1 = left to double precision]
-#if defined(RSQ_SCREEN_STATS) && !defined(__HIP_DEVICE_COMPILE__)
+#if defined(RSQ_SCREEN_STATS) && !RSQ_ON_DEVICE
 #define RSQ_SCREEN_COUNT(family, decided) (++RSQ_SCREEN_STATS[family][0], RSQ_SCREEN_STATS[family][1] += !(decided))
 #else
 #define RSQ_SCREEN_COUNT(family, decided) ((void)0)
@@ -469,12 +444,7 @@ constexpr uint32_t kDescWords = sizeof(DevTable) / 4u;
 // A draw the screen left open, as a call: the double-precision recipe (draw_slim) is rare and large, and inlined at every draw site it costs the read
 // kernel's loop registers and a tenth of its time.  The callee reads the descriptor from the image again; the result carries prob_sum == 0 in bit 31.
 template <int NM>
-#if defined(__HIP_DEVICE_COMPILE__)
-__device__ __noinline__
-#else
-inline
-#endif
-    uint32_t exact_draw_call(const double *pool, const RSQ_LDS float *img, uint32_t par0_words, uint32_t desc, uint32_t i0, uint32_t i1, uint32_t i2, uint32_t i3, uint32_t word) {
+RSQ_NOINLINE uint32_t exact_draw_call(const double *pool, const RSQ_LDS float *img, uint32_t par0_words, uint32_t desc, uint32_t i0, uint32_t i1, uint32_t i2, uint32_t i3, uint32_t word) {
     const DevTable t = reinterpret_cast<const RSQ_LDS DevTable *>(img)[desc];
     uint32_t idx[NM];
     idx[0] = i0;
@@ -487,17 +457,10 @@ inline
 }
 
 // row of margin n for value v: AdjustIndeces over the family's common range
-#define RSQ_GEO_ROW(S, fam, n, v) ((uint32_t)geo_clamp((int32_t)(v) - (int32_t)RSQ_PLAN(S, fam.from[n]), (int32_t)RSQ_PLAN(S, fam.last[n])))
-RSQ_HD int32_t geo_clamp(int32_t d, int32_t last) {
-#if defined(__clang__)
-    return __builtin_elementwise_min(__builtin_elementwise_max(d, 0), last);
-#else
-    return d < 0 ? 0 : (d > last ? last : d);
-#endif
-}
+#define RSQ_GEO_ROW(S, fam, n, v) ((uint32_t)clamp_from_zero((int32_t)(v) - (int32_t)RSQ_PLAN(S, fam.from[n]), (int32_t)RSQ_PLAN(S, fam.last[n])))
 
 // the trial program of tests/hostemu counts the base calls the random word alone decided
-#if defined(RSQ_WORD_SCREEN_STATS) && !defined(__HIP_DEVICE_COMPILE__)
+#if defined(RSQ_WORD_SCREEN_STATS) && !RSQ_ON_DEVICE
 #define RSQ_WORD_SCREEN_COUNT(sure) RSQ_WORD_SCREEN_STATS(sure)
 #else
 #define RSQ_WORD_SCREEN_COUNT(sure) ((void)0)
@@ -981,16 +944,9 @@ struct RecordSrc {
     mutable uint32_t group;
     mutable uint64_t w_seq, w_dom, w_rate;
     RSQ_HD static uint64_t load8(const uint8_t *p, uint32_t off, uint32_t safe) {
+        if (off + 8u <= safe) return load_as<uint64_t, 1>(p + off);
         uint64_t w = 0;
-        if (off + 8u <= safe) {
-#if defined(__HIP_DEVICE_COMPILE__)
-            w = *reinterpret_cast<const uint64_t __attribute__((aligned(1))) *>(p + off);      // unaligned 8-byte loads are what the hardware does (amdhsa)
-#else
-            memcpy(&w, p + off, 8);
-#endif
-        } else {
-            for (uint32_t j = 0; j < 8u && off + j < safe; ++j) w |= (uint64_t)p[off + j] << (8u * j);
-        }
+        for (uint32_t j = 0; j < 8u && off + j < safe; ++j) w |= (uint64_t)p[off + j] << (8u * j);
         return w;
     }
     RSQ_HD void hold(uint32_t k) const {
@@ -1059,13 +1015,8 @@ struct PackedRecordSrc {
         group = g;
         const uint16_t *p = codes + 8u * g;
         if (8u * g + 8u <= safe) {
-#if defined(__HIP_DEVICE_COMPILE__)
-            lo = *reinterpret_cast<const uint64_t __attribute__((aligned(2))) *>(p);
-            hi = *reinterpret_cast<const uint64_t __attribute__((aligned(2))) *>(p + 4);
-#else
-            memcpy(&lo, p, 8);
-            memcpy(&hi, p + 4, 8);
-#endif
+            lo = load_as<uint64_t, 2>(p);
+            hi = load_as<uint64_t, 2>(p + 4);
         } else {
             lo = hi = 0;
             for (uint32_t j = 0; j < 8u && 8u * g + j < safe; ++j) (j < 4u ? lo : hi) |= (uint64_t)p[j] << (16u * (j & 3u));
@@ -1092,11 +1043,7 @@ struct PackedRecordSrc {
                 const uint32_t mine = left > 4u * part ? (left - 4u * part < 4u ? left - 4u * part : 4u) : 0u;
                 if (!mine) continue;
                 const uint64_t keep = mine >= 4u ? ~0ull : (1ull << (16u * mine)) - 1ull, w = (part ? hi : lo) & keep;
-#if defined(__HIP_DEVICE_COMPILE__)
-                gc += (uint32_t)__popcll((w ^ (w >> 1)) & kHalfOnes);
-#else
-                gc += (uint32_t)__builtin_popcountll((w ^ (w >> 1)) & kHalfOnes);
-#endif
+                gc += popcount64((w ^ (w >> 1)) & kHalfOnes);
                 rate_sum += (uint32_t)((((w >> 8) & 0x00FF00FF00FF00FFull) * kHalfOnes) >> 48);
             }
         }
@@ -1210,12 +1157,12 @@ __device__ void fill_wave_reads(const DevSim &S, RSQ_LDS float *img, uint32_t qb
         // moves between them around the "lane not running" join of EVERY step: 20.36 G -> 19.57 G vector instructions per launch of 10 M pairs, 216 -> 223 M pairs/s
         // (What did NOT move those copies, each measured on the device -- DESIGN_LOG.md section 11: tied asm operands on the state, both kinds of step behind a
         // wave-uniform branch inside ONE loop (11 % more instructions), the loop tested at its bottom, the phase changes behind a call.)
-        for (; !RSQ_ANY(!m.in_template()); ++t) {
+        for (; !wave_any(!m.in_template()); ++t) {
             begin_step(t);
             m.template iterate<true>(S, tab, st, src, out);
             __builtin_amdgcn_wave_barrier();
         }
-        for (; RSQ_ANY(m.phase != ReadMachine::kDone); ++t) {      // a read is complete (or a lane has none) exactly when its machine is in kDone: a plain compare for the ballot
+        for (; wave_any(m.phase != ReadMachine::kDone); ++t) {      // a read is complete (or a lane has none) exactly when its machine is in kDone: a plain compare for the ballot
             begin_step(t);
             m.step(S, tab, st, src, out);                    // a lane whose read is complete (or that has none: phase kDone from the start) returns at once
             __builtin_amdgcn_wave_barrier();

@@ -267,32 +267,7 @@ RSQ_HD uint32_t sam_head_size(const DevSim &S, const NameTable &names, bool has_
 }
 // ... SEQ or QUAL (no tab, no line end): the row's words as they lie, or from the last one down -- a read length that is no multiple of four takes every output
 // word from two neighbours --, bytes reversed; bases as letters (reverse: the complement's), qualities moved from the profile's offset to Phred+33
-RSQ_HD uint32_t sam_byte_reverse(uint32_t w) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_perm(0u, w, 0x00010203u);
-#else
-    return (w >> 24) | ((w >> 8) & 0xFF00u) | ((w << 8) & 0xFF0000u) | (w << 24);
-#endif
-}
-RSQ_HD uint32_t sam_complement_letters(uint32_t codes) {                // bytes 0..3 -> "TGCA" (3 - code), 4 -> 'N'
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_perm(0x4E4E4E4Eu, 0x41434754u, codes);
-#else
-    uint32_t out = 0;
-    for (uint32_t k = 0; k < 4u; ++k) {
-        const uint32_t b = (codes >> (8u * k)) & 0xFFu;
-        out |= (uint32_t)("TGCAN"[b < 4u ? b : 4u]) << (8u * k);
-    }
-    return out;
-#endif
-}
-RSQ_HD uint32_t sam_funnel(uint32_t hi, uint32_t lo, uint32_t bytes) {   // (hi:lo) >> 8 * bytes, bytes < 4
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_alignbyte(hi, lo, bytes);
-#else
-    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8u * bytes));
-#endif
-}
+// (sam_byte_reverse, sam_complement_letters and align_bytes: rsq_portable.h)
 // A round of up to kRowAhead of a row's words, loaded together and handed out oriented for output: at(k) is output word i + k -- row word i + k, or (reverse) the
 // row from its last word down, funnelled over two neighbours when read_len & 3, byte-reversed.  Words behind the row's last are 0.
 constexpr uint32_t kRowAhead = 10u;                                      // loads in flight (even: bam_seq pairs the words of a round)
@@ -306,7 +281,7 @@ struct RowRound {
 #pragma unroll
         for (uint32_t k = 0; k <= kRowAhead; ++k, at += step) w[k] = i + k < words && (k < kRowAhead || (reverse && odd)) ? row.p[at] : 0u;
     }
-    RSQ_HD uint32_t at(uint32_t k) const { return reverse ? sam_byte_reverse(odd ? sam_funnel(w[k], w[k + 1u], odd) : w[k]) : w[k]; }
+    RSQ_HD uint32_t at(uint32_t k) const { return reverse ? sam_byte_reverse(odd ? align_bytes(w[k], w[k + 1u], odd) : w[k]) : w[k]; }
 };
 template <class Sink>
 RSQ_HD void sam_line(const WordColumn &row, uint32_t read_len, bool is_qual, bool reverse, uint32_t phred_offset, Sink &t) {

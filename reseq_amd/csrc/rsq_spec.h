@@ -36,8 +36,8 @@ namespace rsq {
 struct SpecHeader {
     const char *name, *text;
 };
-constexpr SpecHeader kSpecHeaders[] = {{"rsq_types.h", kSrc_rsq_types_h}, {"rsq_core.h", kSrc_rsq_core_h}, {"rsq_variants.h", kSrc_rsq_variants_h},
-                                       {"rsq_text.h", kSrc_rsq_text_h},   {"rsq_reads.h", kSrc_rsq_reads_h}};
+constexpr SpecHeader kSpecHeaders[] = {{"rsq_portable.h", kSrc_rsq_portable_h}, {"rsq_types.h", kSrc_rsq_types_h}, {"rsq_core.h", kSrc_rsq_core_h}, {"rsq_variants.h", kSrc_rsq_variants_h},
+                                       {"rsq_text.h", kSrc_rsq_text_h},         {"rsq_reads.h", kSrc_rsq_reads_h}};
 constexpr int kSpecHeaderCount = sizeof(kSpecHeaders) / sizeof(kSpecHeaders[0]);
 
 struct Hiprtc {                                   // the few entry points, bound at run time: the library must load where libhiprtc is absent

@@ -139,12 +139,10 @@ template <class P>
 struct WordPtr {
     using type = uint32_t *;
 };
-#if defined(__HIP_DEVICE_COMPILE__)
 template <>
-struct WordPtr<RSQ_LDS char *> {
+struct WordPtr<RSQ_LDS char *> {         // (the host: RSQ_LDS is empty and this is the general case again)
     using type = RSQ_LDS uint32_t *;
 };
-#endif
 template <class P>
 struct WordSinkT : TextOps<WordSinkT<P>> {
     P p;                 // next destination byte not yet stored
@@ -242,19 +240,7 @@ RSQ_HD void format_header(const DevSim &S, const NameTable &names, const Fragmen
     format_header(S, names, f != nullptr, f ? *f : Fragment{}, adapter_only_number, m, ops, t, fv != nullptr, fv ? *fv : FragmentVar{});
 }
 // ... and one of its two data lines: the bases ("SEQ\n+\n", is_qual false) or the qualities ("QUAL\n").  The read kernel
-// leaves both as bytes in 16-byte aligned rows; four base codes become four letters with one byte permute.
-RSQ_HD uint32_t base_letters(uint32_t codes) {                       // bytes 0..3 -> "ACGT", 4 -> 'N'
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_perm(0x4E4E4E4Eu, 0x54474341u, codes);   // selector 0-3: bytes of "ACGT", 4-7: 'N'
-#else
-    uint32_t out = 0;
-    for (uint32_t k = 0; k < 4u; ++k) {
-        const uint32_t b = (codes >> (8u * k)) & 0xFFu;
-        out |= (uint32_t)("ACGTN"[b < 4u ? b : 4u]) << (8u * k);
-    }
-    return out;
-#endif
-}
+// leaves both as bytes in 16-byte aligned rows; four base codes become four letters with one byte permute (base_letters, rsq_portable.h).
 // words [first_word, first_word + n_words) of the line, then (with_end) the line end
 template <class Sink>
 RSQ_HD void format_line_part(const WordColumn &row, uint32_t read_len, bool is_qual, uint32_t first_word, uint32_t n_words, bool with_end, Sink &t) {

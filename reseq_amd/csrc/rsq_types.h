@@ -5,28 +5,9 @@
 // (schmeing/ReSeq): tables are LogArrayResult<N> (ProbabilityEstimates.h:351-557), "sys errors" are
 // SimBlock::sys_errors_ (Simulator.h:115), thresholds are non_zero_thresholds_ (Simulator.h:298).
 #pragma once
-// compiled by hipcc (the library) or at run time by hiprtc (a read kernel for one profile, rsq_spec.h; its built-in header has the fixed-width types and the
-// device's math), or by a host compiler (the test-only host emulation)
-#if defined(__HIPCC_RTC__)
-using __hip_internal::int32_t;
-using __hip_internal::int64_t;
-using __hip_internal::uint16_t;
-using __hip_internal::uint32_t;
-using __hip_internal::uint64_t;
-using __hip_internal::uint8_t;
-typedef unsigned long uintptr_t;
-#define RSQ_DEVICE_BUILD 1
-#define RSQ_HD __host__ __device__ __forceinline__
-#elif defined(__HIPCC__)
-#include <stdint.h>
-#include <hip/hip_runtime.h>
-#define RSQ_DEVICE_BUILD 1
-#define RSQ_HD __host__ __device__ __forceinline__
-#else
-#include <stdint.h>
-#define RSQ_DEVICE_BUILD 0
-#define RSQ_HD inline
-#endif
+// compiled by hipcc (the library), at run time by hiprtc (a read kernel for one profile, rsq_spec.h) or by a host compiler (the test-only host emulation): what
+// differs between them -- RSQ_HD, the fixed-width types, every device builtin with its host form -- is rsq_portable.h
+#include "rsq_portable.h"
 
 namespace rsq {
 

@@ -254,12 +254,7 @@ RSQ_HD AlleleCell allele_cell(const AlleleView &a, const VarStart &st, uint32_t 
 // variant), the reverse mate's is the reverse complement of the stretch that ends where (end position, EndVariant) points -- inside inserted
 // bases after `end_var_pos` of them, else in front of everything that replaces the end position.  32 bases per word, gathered piecewise.
 RSQ_HD uint64_t reverse_complement_bits(uint64_t x, uint32_t n) {        // of the lowest n <= 32 bases
-#if defined(__HIP_DEVICE_COMPILE__)
-    uint64_t r = __brevll(~x);
-#else
-    uint64_t r = 0, c = ~x;
-    for (uint32_t i = 0; i < 64u; ++i) r |= ((c >> i) & 1ull) << (63u - i);
-#endif
+    uint64_t r = bit_reverse64(~x);
     r = ((r & 0x5555555555555555ull) << 1) | ((r >> 1) & 0x5555555555555555ull);      // the two bits of every base back in order
     return n < 32u ? r >> (64u - 2u * n) : r;
 }
