@@ -391,6 +391,39 @@ int rsq_sim_bam_sorted_index(rsq_sim *s, const uint64_t *block_u, const uint64_t
  * BAM's QNAME limit counts "_allele<a>". */
 int rsq_sim_truth_variants(rsq_sim *s, int on);
 
+/* NM:i and MD:Z on every MAPPED truth record, computed on the device in the same call.  Valid after rsq_sim_create; on == 0 (the default): the truth calls write
+ * the bytes and launch the kernels they always did.  on != 0 shapes rsq_sim_pairs_sam, rsq_sim_pairs_bam, rsq_sim_pairs_bam_sorted and rsq_sim_bam_sorted_flush;
+ * the adapter-only calls accept it and write what they write without it (their records are unmapped).  Changing it inside a sorted run (between
+ * rsq_sim_bam_sorted_begin and a successful rsq_sim_bam_sorted_flush) fails with RSQ_ESTATE.  The RSQ_ENOSPC contract is unchanged: the reported size includes the
+ * tags.  Kernel-time names stay sam_sizes / sam_write / bam_sizes / bam_write.
+ *   The rule.  The tags are a pure function of the finished record and the reference as loaded (after rsq_ref_replace_n; with variants: the reference itself,
+ * never an allele).  With ref = the bases of RNAME, seq = SEQ as written (a reverse mate's is already reverse-complemented), cigar = the CIGAR's elements,
+ * pos = POS:
+ *     r, q, run, nm, md = pos - 1, 0, 0, 0, ""
+ *     for n, op in cigar:
+ *         if op == "M":
+ *             for _ in range(n):
+ *                 if seq[q] == ref[r]: run += 1
+ *                 else: md += str(run) + ref[r]; run = 0; nm += 1
+ *                 q += 1; r += 1
+ *         elif op == "I": q += n; nm += n
+ *         elif op == "S": q += n
+ *         elif op == "D": md += str(run) + "^" + ref[r:r + n]; run = 0; r += n; nm += n
+ *     md += str(run)
+ * This is what `samtools calmd` writes: a 0 between adjacent mismatches and between a deletion and a mismatch that follows it, the string always ends in a
+ * number, insertions and clips do not appear in MD.  Consequences:
+ *   - a read base N is a mismatch; MD prints the reference base;
+ *   - the D runs the CIGAR drops at either end are not in MD, and POS has already moved past them;
+ *   - bases converted by a methylation file count as mismatches;
+ *   - with rsq_sim_truth_variants the comparison is against the reference, not the allele: a substituted allele base that the read reproduces is a mismatch,
+ *     one that a sequencing error turns back into the reference base is a match; the I and D columns that come from the allele map count in NM, and for D MD
+ *     prints the deleted reference bases; substitution-only variant sets (allele copies) compare against the reference as well;
+ *   - a mapped mate without an M column (a CIGAR of nI and the clip, a bare clip, or "*") gets MD:Z:0 and NM = its inserted bases;
+ *   - unmapped records (flags 77 / 141: fragments of length 0 and every record of the adapter-only calls) get neither tag.
+ * Placement.  SAM: "\tNM:i:<n>\tMD:Z:<md>" after XE:i (after XI:i with variants), before the line end.  BAM: "NM" 'I' u32, then "MD" 'Z' <md> NUL, after XE / XI;
+ * block_size covers them. */
+int rsq_sim_truth_md(rsq_sim *s, int on);
+
 /* Simulator::ApplyErrorsAndQualityToFastaInput with the FASTA header already parsed (reseq/Simulator.cpp:2403-2512):
  * n records of `read_len` template bases each.  Inputs (device): seqs[n][read_len] base codes 0..3, seg[n] template
  * segment 0/1, frag_len[n], dom[n][read_len] dominant-error base codes 0..4, rate[n][read_len] error percent.

@@ -109,6 +109,7 @@ SYMBOLS = {
     "rsq_sim_pairs_bam": (C.c_int, [_vp, _u32, _u32, _vp, _sz, _psz, _vp, _sz, _psz, _vp, _sz, _psz, C.POINTER(_u64), _vp, _sz, _vp]),
     "rsq_sim_adapter_only_pairs_bam": (C.c_int, [_vp, _u64, _u64, _vp, _sz, _psz, _vp, _sz, _psz, _vp, _sz, _psz, _vp]),
     "rsq_sim_truth_variants": (C.c_int, [_vp, C.c_int]),
+    "rsq_sim_truth_md": (C.c_int, [_vp, C.c_int]),
     "rsq_sim_bam_sorted_begin": (C.c_int, [_vp, _u64]),
     "rsq_sim_pairs_bam_sorted": (C.c_int, [_vp, _u32, _u32, _vp, _sz, _psz, _vp, _sz, _psz, _vp, _sz, _psz, C.POINTER(_u64), C.POINTER(_u64), _vp, _sz, _vp]),
     "rsq_sim_bam_sorted_flush": (C.c_int, [_vp, _vp, _sz, _psz, C.POINTER(_u64), C.POINTER(_u64), _vp]),
@@ -603,6 +604,10 @@ class Simulator:
         finally:
             for d in (r1, r2, out):
                 d.free()
+
+    def truth_md(self, on=True):
+        """rsq_sim_truth_md: the truth calls append NM:i and MD:Z to every mapped record (computed on the device against the reference as loaded)"""
+        _check(lib().rsq_sim_truth_md(self.h, 1 if on else 0))
 
     def truth_variants(self, on=True):
         """rsq_sim_truth_variants: the truth calls accept a reference with variants and write their records in reference coordinates (with the XI:i tag)"""

@@ -66,7 +66,7 @@ const std::map<std::string, std::string> kShort = {{"-j", "threads"}, {"-h", "he
                                                    {"-v", "vcfIn"},   {"-p", "probabilitiesIn"}, {"-P", "probabilitiesOut"}, {"-1", "firstReadsOut"},
                                                    {"-2", "secondReadsOut"}, {"-c", "coverage"}, {"-R", "refSim"}, {"-V", "vcfSim"}, {"-i", "input"}, {"-o", "output"}};
 const std::set<std::string> kFlags = {"help", "version", "noBias", "noTiles", "statsOnly", "tiles", "stopAfterEstimation", "noInDelErrors", "noSubstitutionErrors", "maxLenDeletion", "maxReadLength",
-                                      "dumpArchiveLayout", "traceStages", "hostGzip", "truthBamSort", "truthVariants"};
+                                      "dumpArchiveLayout", "traceStages", "hostGzip", "truthBamSort", "truthVariants", "truthMD"};
 
 bool parse(int argc, char **argv, int first, Args &a) {
     for (int i = first; i < argc; ++i) {
@@ -699,6 +699,10 @@ int illumina_pe(const Args &a) {
         ERR("--truthVariants chooses the coordinates of --truthSam / --truthBam: give one of them as well");
         return 1;
     }
+    if (a.has("truthMD") && !any_truth) {
+        ERR("--truthMD adds the tags NM:i and MD:Z to the records of --truthSam / --truthBam: give one of them as well");
+        return 1;
+    }
     const char *truth_option = any_truth ? truths.front().option : "";
     rsq_profile *prof = nullptr;
     rsq_ref *ref = nullptr;
@@ -771,6 +775,7 @@ int illumina_pe(const Args &a) {
     if (ok && a.has("device")) ok = parse_u64(a, "device", device);
     ok = ok && check(rsq_sim_create(prof, ref, (int)device, &sim), "Could not set up the simulator");
     if (ok && a.has("truthVariants")) ok = check(rsq_sim_truth_variants(sim, 1), "--truthVariants");
+    if (ok && a.has("truthMD")) ok = check(rsq_sim_truth_md(sim, 1), "--truthMD");
     trace.at("simulator created");
     if (ok && !sys_write.empty()) {
         INFO("Writing systematic error profile to " << sys_write);
@@ -1199,6 +1204,7 @@ const char *kUsage =
     "                 \t--truthBam truth.bam: the same records as BAM (BGZF blocks made on the device; unsorted, no index; may be given beside --truthSam; with -V only with --truthVariants; not with --hostGzip, one worker)\n"
     "                 \t--truthBamSort: with --truthBam, the records sorted by coordinate on the device (@HD SO:coordinate) and the index truth.bam.bai beside the file\n"
     "                 \t--truthVariants: with -V, --truthSam / --truthBam [--truthBamSort] write their records in reference coordinates (inserted bases as I, deleted ones as D, tag XI:i)\n"
+    "                 \t--truthMD: --truthSam / --truthBam [--truthBamSort] [--truthVariants] append NM:i and MD:Z to every mapped record (computed on the device against the reference as loaded, as samtools calmd would)\n"
     "                 \t--truthSam truth.sam[.gz]: where every read really came from, as SAM records (header, two records per pair in the files' order; with -V only with --truthVariants; one worker)\n"
     "  seqToIllumina\t\tapplies illumina quality and error model to input sequences (alias: replaceQuals)\n"
     "                 \t-i in.fa[.gz|.bz2] (stdin) -o out.fq[.gz|.bz2] (stdout) -s profile; --readThreads N, --traceStages;\n"

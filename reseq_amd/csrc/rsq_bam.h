@@ -174,9 +174,10 @@ RSQ_HD BamMate bam_mate(const DevSim &S, const NameTable &names, bool has_f, con
 
 // BAM records as a format (rsq_sam.h states what a format is)
 struct BamFormat {
-    static constexpr bool kVariants = false;
+    static constexpr bool kVariants = false, kMd = false, kBam = true;
     using Mate = BamMate;
     using Pair = BamPair;
+    static RSQ_HD void grow(Mate &e, uint32_t n) { e.w.bytes += n; }    // more tags behind the record's own (rsq_md.h): block_size covers them
     static RSQ_HD const SamMate &walk(const Mate &e) { return e.w; }
     static RSQ_HD uint32_t bytes(const Mate &e) { return e.w.bytes; }
     static RSQ_HD Mate mate(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &ops, const SamMate &w,
@@ -192,6 +193,10 @@ struct BamFormat {
     static RSQ_HD void tail(const DevSim &S, const ReadMeta &m, const WordColumn &qual, const WordColumn &ops, const SamAlign &a, Sink &t) {
         bam_qual(qual, m.read_len, a.reverse != 0u, S.phred_offset, t);
         bam_tags(m, ops, t);
+    }
+    template <class Sink>
+    static RSQ_HD void tail_open(const DevSim &S, const ReadMeta &m, const WordColumn &qual, const WordColumn &ops, const SamAlign &a, Sink &t) {      // (a BAM record has no terminator)
+        tail(S, m, qual, ops, a, t);
     }
     static RSQ_HD uint32_t tail_at(const Mate &e, const ReadMeta &m) { return e.w.bytes - bam_tags_size(m) - m.read_len; }
     template <class P>
@@ -216,9 +221,10 @@ struct BamVarPair {
 };
 constexpr uint32_t kBamVarTag = 7u;                                     // "XI" 'I' u32
 struct BamVarFormat {
-    static constexpr bool kVariants = true;
+    static constexpr bool kVariants = true, kMd = false, kBam = true;
     using Mate = BamVarMate;
     using Pair = BamVarPair;
+    static RSQ_HD void grow(Mate &e, uint32_t n) { e.v.w.bytes += n; }
     static RSQ_HD const SamVarMate &var(const Mate &e) { return e.v; }
     static RSQ_HD uint32_t bytes(const Mate &e) { return e.v.w.bytes; }
     static RSQ_HD Mate mate(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, const SamVarId &id, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &ops,
@@ -248,6 +254,10 @@ struct BamVarFormat {
         bam_tags(m, ops, t);
         t.bytes(chars4('X', 'I', 'I'), 3u);
         t.bytes(id.xi, 4u);
+    }
+    template <class Sink>
+    static RSQ_HD void tail_open(const DevSim &S, const ReadMeta &m, const SamVarId &id, const WordColumn &qual, const WordColumn &ops, const SamAlign &a, Sink &t) {
+        tail(S, m, id, qual, ops, a, t);
     }
     static RSQ_HD uint32_t tail_at(const Mate &e, const ReadMeta &m, const SamVarId &) { return e.v.w.bytes - bam_tags_size(m) - kBamVarTag - m.read_len; }
     template <class P>

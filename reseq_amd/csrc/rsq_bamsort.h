@@ -26,7 +26,7 @@
 #include <string>
 #include <vector>
 
-#include "rsq_bam.h"
+#include "rsq_md.h"
 
 namespace rsq {
 
@@ -93,6 +93,13 @@ RSQ_HD BamDirEntry bam_dir_entry(const Fragment &f, uint32_t seg, const BamVarPa
     e.size = m.w.bytes;
     e.span = mapped ? (m.ref_bases ? m.ref_bases : 1u) : 0u;
     return e;
+}
+// ... of the formats with NM and MD (rsq_md.h): the entry's own part says it all, the record's bytes with the tags included
+RSQ_HD BamDirEntry bam_dir_entry(const Fragment &f, uint32_t seg, const MdPair<BamMate> &p, uint64_t pair_off, uint32_t n_seqs) {
+    return bam_dir_entry(f, seg, BamPair{{p.mate[0].b, p.mate[1].b}}, pair_off, n_seqs);
+}
+RSQ_HD BamDirEntry bam_dir_entry(const Fragment &f, uint32_t seg, const MdPair<BamVarMate> &p, uint64_t pair_off, uint32_t n_seqs) {
+    return bam_dir_entry(f, seg, BamVarPair{{p.mate[0].b, p.mate[1].b}}, pair_off, n_seqs);
 }
 // what k_bam_sort_keys counts: a mapped record below the cut of the call before, or at a position the digits do not cover
 RSQ_HD bool bam_key_out_of_order(uint64_t key, uint64_t prev_cut, uint32_t n_seqs, uint32_t pos_bits) {

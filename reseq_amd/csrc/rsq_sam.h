@@ -20,7 +20,9 @@
 // (sam_record, bam_record: the straight-to-HBM fallback).  Everything that is not a record's bytes is written once over a format: the kernels k_truth_sizes<Format> (one lane per pair: both
 // mates' entries into the side array, the pair's bytes) and k_truth_write<Format, PERM> (one wave per 16 pairs, four lanes a pair, through the wave's LDS image,
 // WaveImage in rsq_format.h).  A format with kVariants has the same members with the FragmentVar's part (SamVarId) among their arguments, and its alignment comes from the
-// entries (sam_var_align): the two kernels branch on it at compile time.  Not part of what hiprtc compiles for a profile (rsq_spec.h): nothing of the read kernel's text includes this file.
+// entries (sam_var_align): the two kernels branch on it at compile time.  A format with kMd (rsq_md.h: MdFormat over each of the four, rsq_sim_truth_md) appends NM:i and MD:Z to a
+// mapped record: its mate() and tail() also take the SEQ row, the fragment and the entry -- the second compile-time branch --, and it is built from the members grow (more
+// bytes behind a record's own) and tail_open (the tail up to where more tags go) that every format has.  Not part of what hiprtc compiles for a profile (rsq_spec.h): nothing of the read kernel's text includes this file.
 #pragma once
 #include "rsq_format.h"
 
@@ -298,13 +300,17 @@ RSQ_HD void sam_line(const WordColumn &row, uint32_t read_len, bool is_qual, boo
         }
     }
 }
-// ... and the two tags with the line end
+// ... and the two tags (sam_tags_open: without the line end, for a format that writes more tags behind them) with the line end
 template <class Sink>
-RSQ_HD void sam_tags(const ReadMeta &m, const WordColumn &ops, Sink &t) {
+RSQ_HD void sam_tags_open(const ReadMeta &m, const WordColumn &ops, Sink &t) {
     t.str("\tXC:Z:", 6);
     cigar_replay(ops, m, t);
     t.str("\tXE:i:", 6);
     t.num((uint32_t)m.num_errors);
+}
+template <class Sink>
+RSQ_HD void sam_tags(const ReadMeta &m, const WordColumn &ops, Sink &t) {
+    sam_tags_open(m, ops, t);
     t.ch('\n');
 }
 RSQ_HD uint32_t sam_tags_size(const ReadMeta &m) { return 6u + m.cigar_chars + 6u + digits_u32(m.num_errors) + 1u; }
@@ -330,9 +336,10 @@ RSQ_HD uint32_t sam_record(const DevSim &S, const NameTable &names, bool has_f, 
 
 // SAM text as a format (the header comment states what a format is); an entry is the walk itself, with the record's bytes
 struct SamFormat {
-    static constexpr bool kVariants = false;
+    static constexpr bool kVariants = false, kMd = false, kBam = false;
     using Mate = SamMate;
     using Pair = SamPair;
+    static RSQ_HD void grow(Mate &e, uint32_t n) { e.bytes += n; }      // more tags behind the record's own (rsq_md.h)
     static RSQ_HD const SamMate &walk(const Mate &e) { return e; }
     static RSQ_HD uint32_t bytes(const Mate &e) { return e.bytes; }
     static RSQ_HD Mate mate(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &, const SamMate &w,
@@ -352,6 +359,11 @@ struct SamFormat {
     static RSQ_HD void tail(const DevSim &S, const ReadMeta &m, const WordColumn &qual, const WordColumn &ops, const SamAlign &a, Sink &t) {
         sam_line(qual, m.read_len, true, a.reverse != 0u, S.phred_offset, t);
         sam_tags(m, ops, t);
+    }
+    template <class Sink>
+    static RSQ_HD void tail_open(const DevSim &S, const ReadMeta &m, const WordColumn &qual, const WordColumn &ops, const SamAlign &a, Sink &t) {      // ... up to where more tags go
+        sam_line(qual, m.read_len, true, a.reverse != 0u, S.phred_offset, t);
+        sam_tags_open(m, ops, t);
     }
     static RSQ_HD uint32_t tail_at(const Mate &e, const ReadMeta &m) { return e.bytes - sam_tags_size(m) - m.read_len; }
     template <class P>
@@ -601,13 +613,14 @@ RSQ_HD void sam_var_head(const DevSim &S, const NameTable &names, bool has_f, co
     }
 }
 template <class Sink>
-RSQ_HD void sam_var_tags(const ReadMeta &m, const WordColumn &ops, const SamVarId &id, Sink &t) {
-    t.str("\tXC:Z:", 6);
-    cigar_replay(ops, m, t);
-    t.str("\tXE:i:", 6);
-    t.num((uint32_t)m.num_errors);
+RSQ_HD void sam_var_tags_open(const ReadMeta &m, const WordColumn &ops, const SamVarId &id, Sink &t) {
+    sam_tags_open(m, ops, t);
     t.str("\tXI:i:", 6);
     t.num(id.xi);
+}
+template <class Sink>
+RSQ_HD void sam_var_tags(const ReadMeta &m, const WordColumn &ops, const SamVarId &id, Sink &t) {
+    sam_var_tags_open(m, ops, id, t);
     t.ch('\n');
 }
 RSQ_HD uint32_t sam_var_tags_size(const ReadMeta &m, const SamVarId &id) { return sam_tags_size(m) + 6u + digits_u32(id.xi); }
@@ -615,9 +628,10 @@ RSQ_HD uint32_t sam_var_tags_size(const ReadMeta &m, const SamVarId &id) { retur
 // SAM text of a reference with variants as a format.  What differs from SamFormat's members: the FragmentVar's part (SamVarId) where the QNAME or the tags are
 // written, and the alignment comes from the entries (sam_var_align).
 struct SamVarFormat {
-    static constexpr bool kVariants = true;
+    static constexpr bool kVariants = true, kMd = false, kBam = false;
     using Mate = SamVarMate;
     using Pair = SamVarPair;
+    static RSQ_HD void grow(Mate &e, uint32_t n) { e.w.bytes += n; }
     static RSQ_HD const SamVarMate &var(const Mate &e) { return e; }
     static RSQ_HD uint32_t bytes(const Mate &e) { return e.w.bytes; }
     static RSQ_HD Mate mate(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, const SamVarId &id, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &,
@@ -638,6 +652,11 @@ struct SamVarFormat {
     static RSQ_HD void tail(const DevSim &S, const ReadMeta &m, const SamVarId &id, const WordColumn &qual, const WordColumn &ops, const SamAlign &a, Sink &t) {
         sam_line(qual, m.read_len, true, a.reverse != 0u, S.phred_offset, t);
         sam_var_tags(m, ops, id, t);
+    }
+    template <class Sink>
+    static RSQ_HD void tail_open(const DevSim &S, const ReadMeta &m, const SamVarId &id, const WordColumn &qual, const WordColumn &ops, const SamAlign &a, Sink &t) {
+        sam_line(qual, m.read_len, true, a.reverse != 0u, S.phred_offset, t);
+        sam_var_tags_open(m, ops, id, t);
     }
     static RSQ_HD uint32_t tail_at(const Mate &e, const ReadMeta &m, const SamVarId &id) { return e.w.bytes - sam_var_tags_size(m, id) - m.read_len; }
     template <class P>
@@ -674,12 +693,22 @@ __global__ void __launch_bounds__(256) k_truth_sizes(DevSim S, NameTable names, 
         const SamVarId id = sam_var_id(S, f, has_fv, fv);
         uint32_t n0, n1;
         const SamVarMate w0 = sam_var_walk(S, has_f, f, has_fv, fv, 0u, ops0, m0, n0), w1 = sam_var_walk(S, has_f, f, has_fv, fv, 1u, ops1, m1, n1);
-        p.mate[0] = Format::mate(S, names, has_f, f, id, ao_number, m0, ops0, w0, n0, sam_var_align(has_f, f, 0u, w0, w1));
-        p.mate[1] = Format::mate(S, names, has_f, f, id, ao_number, m1, ops1, w1, n1, sam_var_align(has_f, f, 1u, w0, w1));
+        if constexpr (Format::kMd) {                                    // (rsq_md.h: the entry also takes what comparing SEQ with the reference comes to)
+            p.mate[0] = Format::mate(S, names, has_f, f, id, ao_number, m0, raw.seq_of(row), ops0, w0, n0, sam_var_align(has_f, f, 0u, w0, w1));
+            p.mate[1] = Format::mate(S, names, has_f, f, id, ao_number, m1, raw.seq_of(n_pairs + row), ops1, w1, n1, sam_var_align(has_f, f, 1u, w0, w1));
+        } else {
+            p.mate[0] = Format::mate(S, names, has_f, f, id, ao_number, m0, ops0, w0, n0, sam_var_align(has_f, f, 0u, w0, w1));
+            p.mate[1] = Format::mate(S, names, has_f, f, id, ao_number, m1, ops1, w1, n1, sam_var_align(has_f, f, 1u, w0, w1));
+        }
     } else {
         const SamMate w0 = sam_walk(ops0, m0), w1 = sam_walk(ops1, m1);
-        p.mate[0] = Format::mate(S, names, has_f, f, ao_number, m0, ops0, w0, sam_align(has_f, f, 0u, w0, w1));
-        p.mate[1] = Format::mate(S, names, has_f, f, ao_number, m1, ops1, w1, sam_align(has_f, f, 1u, w0, w1));
+        if constexpr (Format::kMd) {
+            p.mate[0] = Format::mate(S, names, has_f, f, ao_number, m0, raw.seq_of(row), ops0, w0, sam_align(has_f, f, 0u, w0, w1));
+            p.mate[1] = Format::mate(S, names, has_f, f, ao_number, m1, raw.seq_of(n_pairs + row), ops1, w1, sam_align(has_f, f, 1u, w0, w1));
+        } else {
+            p.mate[0] = Format::mate(S, names, has_f, f, ao_number, m0, ops0, w0, sam_align(has_f, f, 0u, w0, w1));
+            p.mate[1] = Format::mate(S, names, has_f, f, ao_number, m1, ops1, w1, sam_align(has_f, f, 1u, w0, w1));
+        }
     }
     side[row] = p;
     sizes[pair] = Format::bytes(p.mate[0]) + Format::bytes(p.mate[1]);
@@ -735,6 +764,7 @@ __global__ void __launch_bounds__(64) k_truth_write(DevSim S, NameTable names, c
         if (im.active) {
             ImageSink t(im.item_text(s_truth) + rec_at + (half ? Format::tail_at(e, m, id) : 0u));
             if (half == 0u) Format::head(S, names, has_f, f, id, ao_number, m, seq, ops, e, a, t);
+            else if constexpr (Format::kMd) Format::tail(S, f, m, id, seq, qual, ops, e, a, t);      // (the tail lane compares SEQ with the reference again and prints MD)
             else Format::tail(S, m, id, qual, ops, a, t);
             t.finish();
         }
@@ -748,6 +778,7 @@ __global__ void __launch_bounds__(64) k_truth_write(DevSim S, NameTable names, c
         if (im.active) {
             ImageSink t(im.item_text(s_truth) + rec_at + (half ? Format::tail_at(e, m) : 0u));
             if (half == 0u) Format::head(S, names, has_f, f, ao_number, m, seq, ops, e, a, t);
+            else if constexpr (Format::kMd) Format::tail(S, f, m, seq, qual, ops, e, a, t);
             else Format::tail(S, m, qual, ops, a, t);
             t.finish();
         }

@@ -30,6 +30,7 @@
 #include "rsq_format.h"
 #include "rsq_sam.h"
 #include "rsq_bam.h"
+#include "rsq_md.h"
 #include "rsq_bamsort.h"
 #include "rsq_pack.h"
 #include "rsq_prepass.h"
@@ -259,9 +260,11 @@ struct rsq_sim : PrepassSim {
     uint64_t sam_pair_bytes = 1100;          // that of the last call and a few bytes (sam_stage sizes the writer's LDS image with it)
     uint64_t bam_pair_bytes = 700;           // the same for a call that writes BAM records
     bool truth_variants = false;             // rsq_sim_truth_variants: truth alignments of a reference with variants, in reference coordinates (SamVarFormat, BamVarFormat)
+    bool truth_md = false;                   // rsq_sim_truth_md: NM:i and MD:Z behind every mapped truth record's tags (rsq_md.h: the four formats as MdFormat)
     // rsq_sim_bam_sorted_*: a run of calls whose BAM records leave in coordinate order (rsq_bamsort.h)
     struct BamSorted {
         bool active = false;
+        bool open = false;                   // between rsq_sim_bam_sorted_begin and the flush: rsq_sim_truth_md may not change
         uint64_t stream_at = 0;              // the uncompressed offset in the file of the next final record
         uint32_t next_block = 0;             // where the next call begins (0: the run's first call begins where it likes)
         uint64_t prev_cut = 0;               // the cut of the call before: no record of a later call lies below it
@@ -759,7 +762,7 @@ template <class Format>
 static void truth_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_first, const ReadsDone &rd, char *r1, size_t r1_cap, char *r2, size_t r2_cap, const SamOut &sam,
                         uint32_t part, hipStream_t st, const FragmentVar *fvars) {
     using Pair = typename Format::Pair;
-    constexpr bool bam = std::is_same<Format, BamFormat>::value || std::is_same<Format, BamVarFormat>::value;
+    constexpr bool bam = Format::kBam;
     const char *sizes_timer = bam ? "bam_sizes" : "sam_sizes", *write_timer = bam ? "bam_write" : "sam_write";
     rsq_sim::Workspace &w = *s.cur;
     DevBuf &side = bam ? w.bam_side : w.sam_side;
@@ -788,6 +791,12 @@ static void truth_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uin
 static void sam_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_first, const ReadsDone &rd, char *r1, size_t r1_cap, char *r2, size_t r2_cap, const SamOut &sam,
                       uint32_t part, hipStream_t st, const FragmentVar *fvars = nullptr) {
     // a reference with variants (accepted only with rsq_sim_truth_variants): the formats in reference coordinates; every other simulator launches what it always did
+    // rsq_sim_truth_md (mapped pairs only: an adapter-only call's records carry no such tags and are written by the formats without): the same four with the tags
+    if (s.truth_md && frags) {
+        if (s.has_variants) (sam.bam ? truth_stage<BamVarMdFormat> : truth_stage<SamVarMdFormat>)(s, frags, n_pairs, adapter_first, rd, r1, r1_cap, r2, r2_cap, sam, part, st, fvars);
+        else (sam.bam ? truth_stage<BamMdFormat> : truth_stage<SamMdFormat>)(s, frags, n_pairs, adapter_first, rd, r1, r1_cap, r2, r2_cap, sam, part, st, nullptr);
+        return;
+    }
     if (s.has_variants) (sam.bam ? truth_stage<BamVarFormat> : truth_stage<SamVarFormat>)(s, frags, n_pairs, adapter_first, rd, r1, r1_cap, r2, r2_cap, sam, part, st, fvars);
     else (sam.bam ? truth_stage<BamFormat> : truth_stage<SamFormat>)(s, frags, n_pairs, adapter_first, rd, r1, r1_cap, r2, r2_cap, sam, part, st, nullptr);
 }
@@ -2039,6 +2048,23 @@ int rsq_sim_truth_variants(rsq_sim *s, int on) {
     s->truth_variants = on != 0;
     return RSQ_OK;
 }
+// NM:i and MD:Z behind every mapped truth record's tags (rsq_md.h).  The writer's image is sized by the longest pair of the call before: the first call with the
+// tags gets room for them.
+int rsq_sim_truth_md(rsq_sim *s, int on) {
+    REQUIRE(s, "null argument");
+    const bool want = on != 0;
+    if (want == s->truth_md) return RSQ_OK;
+    if (s->bam_sorted.open) {
+        g_last_error = "rsq_sim_truth_md cannot change inside a sorted run (between rsq_sim_bam_sorted_begin and rsq_sim_bam_sorted_flush)";
+        return RSQ_ESTATE;
+    }
+    s->truth_md = want;
+    if (want) {
+        s->sam_pair_bytes += 64;
+        s->bam_pair_bytes += 48;
+    }
+    return RSQ_OK;
+}
 static int pairs_truth(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len, char *out_dev,
                        size_t out_cap, size_t *out_len, uint64_t *n_pairs, rsq_fragment *frags_dev, size_t frags_cap, void *stream, bool bam) {
     REQUIRE(s && r1_len && r2_len && out_len && n_pairs, "null argument");
@@ -2069,6 +2095,7 @@ int rsq_sim_bam_sorted_begin(rsq_sim *s, uint64_t first_record_offset) {
         uint32_t longest = 0;
         for (const uint32_t l : s->seq_len) longest = std::max(longest, l);
         b.active = true;
+        b.open = true;
         b.stream_at = first_record_offset;
         b.next_block = 0;
         b.prev_cut = 0;
@@ -2136,6 +2163,7 @@ int rsq_sim_bam_sorted_flush(rsq_sim *s, char *bam_dev, size_t bam_cap, size_t *
         uint64_t n_records = 0;
         const int rc = sorted_finish(*s, RSQ_OK, kBamCutAll, b.next_block, bam_dev, bam_cap, bam_len, &n_records, n_mapped, 0, 0, st);
         *n_unmapped = n_records - *n_mapped;
+        if (rc == RSQ_OK) b.open = false;
         return rc;
     });
 }

@@ -3,6 +3,9 @@
 step, one call per step) through rsq_sim_pairs and through rsq_sim_pairs_sam: pairs/s of both, kernel ms and launches of format_write, sam_sizes and sam_write
 (of the last step), the bytes of the three texts and the two writers' bytes/s.  One JSON line.
 
+--md: the truth calls again with rsq_sim_truth_md set (NM:i and MD:Z on every mapped record), beside the ones above -- "with_md": pairs/s, kernel ms of the sizes
+and the write kernel and bytes per pair of the SAM call and, where --bam / --sorted are given, of theirs; with --variants in both halves.
+
 --bam: the same through rsq_sim_pairs_bam beside them -- its pairs/s, kernel ms of bam_sizes / bam_write, the bytes per pair of SAM and BAM, and what the device's
 deflater (rsq_sim_gzip_device) makes of both and of the BAM bytes' first 256 MiB against zlib level 1 on those same bytes.
 
@@ -25,9 +28,9 @@ sys.path.insert(0, ROOT)
 
 from reseq_amd import api, synth, workloads  # noqa: E402
 
-with_bam, with_sorted, with_variants = "--bam" in sys.argv, "--sorted" in sys.argv, "--variants" in sys.argv
+with_bam, with_sorted, with_variants, with_md = "--bam" in sys.argv, "--sorted" in sys.argv, "--variants" in sys.argv, "--md" in sys.argv
 assert with_bam or not with_sorted, "--sorted goes with --bam"
-argv = [a for a in sys.argv[1:] if a not in ("--bam", "--sorted", "--variants")]
+argv = [a for a in sys.argv[1:] if a not in ("--bam", "--sorted", "--variants", "--md")]
 pairs = int(argv[0]) if len(argv) > 0 else 10_000_000
 steps = int(argv[1]) if len(argv) > 1 else 3
 tmp = tempfile.mkdtemp(prefix="rsq_sam_")
@@ -145,6 +148,38 @@ def measure(vcf):
             })
         packed.free()
         bam.free()
+    md_part = {}
+    if with_md:
+        if with_sorted:                                                    # the switch does not change inside a sorted run: hand out what the last one holds
+            held = api.DeviceArray(0, sim.bam_sorted_flush_device(None)[0] + 4096)
+            assert sim.bam_sorted_flush_device(held)[3] == api.RSQ_OK
+            held.free()
+        sim.truth_md(True)
+        _, _, _, ls_md, rc = sim.pairs_sam_device(lo, hi, None, None, None)
+        assert rc == api.RSQ_ENOSPC, rc
+        sam_md = api.DeviceArray(0, ls_md + 4096)
+        md_s = timed(lambda: sim.pairs_sam_device(lo, hi, r1, r2, sam_md))
+        md_part = {"pairs_per_s_sam": round(n / md_s), "ms_per_call_sam": round(md_s * 1e3, 2), "kernels_of_a_sam_call": kernels(("sam_sizes", "sam_write")),
+                   "bytes_per_pair": {"sam": round(ls_md / n, 1)}}
+        md_part["GB_per_s_sam_write"] = gbps(ls_md, md_part["kernels_of_a_sam_call"]["sam_write"]["ms"])
+        sam_md.free()
+        if with_bam:
+            _, _, _, lb_md, rc = sim.pairs_bam_device(lo, hi, None, None, None)
+            assert rc == api.RSQ_ENOSPC, rc
+            bam_md = api.DeviceArray(0, lb_md + 4096)
+            md_s = timed(lambda: sim.pairs_bam_device(lo, hi, r1, r2, bam_md))
+            md_part.update({"pairs_per_s_bam": round(n / md_s), "ms_per_call_bam": round(md_s * 1e3, 2), "kernels_of_a_bam_call": kernels(("bam_sizes", "bam_write"))})
+            md_part["bytes_per_pair"]["bam"] = round(lb_md / n, 1)
+            md_part["GB_per_s_bam_write"] = gbps(lb_md, md_part["kernels_of_a_bam_call"]["bam_write"]["ms"])
+            if with_sorted:
+                def sorted_md_call():
+                    sim.bam_sorted_begin(0)
+                    return sim.pairs_bam_sorted_device(lo, hi, r1, r2, bam_md)
+
+                md_s = timed(sorted_md_call)
+                md_part.update({"pairs_per_s_bam_sorted": round(n / md_s), "ms_per_call_bam_sorted": round(md_s * 1e3, 2),
+                                "kernels_of_a_sorted_call": kernels(("bam_sizes", "bam_write", "bam_sort_keys", "bam_sort", "bam_gather", "bam_index"))})
+            bam_md.free()
     result = {
         "workload": f"P0, one sequence of {genome} bases, {n} pairs per call", "steps": steps,
         "pairs_per_s": {"rsq_sim_pairs": round(n / plain_s), "rsq_sim_pairs_sam": round(n / sam_s)},
@@ -154,6 +189,8 @@ def measure(vcf):
         "GB_per_s": {"format_write": gbps(l1 + l2, sam_kernels["format_write"]["ms"]), "sam_write": gbps(ls, sam_kernels["sam_write"]["ms"])},
         **bam_part,
     }
+    if with_md:
+        result["with_md"] = md_part
     for d in (r1, r2, sam):
         d.free()
     sim.close()
