@@ -253,7 +253,22 @@ struct rsq_sim : PrepassSim {
     hipEvent_t ev_call = nullptr, ev_fill = nullptr, ev_emit = nullptr;
     std::map<std::string, Timer> timers;
     uint32_t n_cu = 256;
-    uint64_t *mailbox = nullptr;   // pinned host words the hot path's few device-to-host scalars land in
+    // Pinned host words (one hipHostMalloc) the few device-to-host scalars of a call land in: one name, one meaning and one user each, 4 bytes wide where the copy is
+    struct Mailbox {
+        struct Sieve {                 // sieve_attempt -> sieve_collect, one per workspace: the sieve of part k + 1 is launched before the call of part k ends
+            uint64_t total, n_cands;   // pairs of the range; candidates its lists would have needed
+            uint32_t n_hits;
+        } sieve[2];
+        uint64_t r1_bytes, r2_bytes, truth_bytes;                // finish_call: one 16-byte copy fills the first two
+        uint32_t walk_error, longest_record, truth_longest;      // finish_call: the call's longest FASTQ record and longest pair of truth records
+        uint32_t bad_fragment;                         // check_fragment_lengths: the first record whose fragment length has no row, sent out as "none" and read back
+        uint64_t text_bytes, fasta_starts;             // error_model_text; rsq_sim_error_model_fasta: record starts in the block of text
+        uint32_t text_longest;                         // error_model_text
+        struct {                                       // rsq_sim_error_model_fasta: rsq_fasta.h `summary`, sent out as its initial state and read back
+            uint32_t longest, first_bad, stray_text, spare;
+        } fasta_summary;
+        uint32_t fasta_lead_end, fasta_last_start;     // rsq_sim_error_model_fasta: the first and the last record start
+    } *mailbox = nullptr;
     uint64_t format_record_bytes = 480;      // the longest FASTQ record of the last rsq_sim_pairs call and a few bytes (text_stage sizes the formatter's LDS image with it)
     DevBuf longest_record;                   // where a call's text stages leave it
     DevBuf sam_totals, sam_longest;          // rsq_sim_pairs_sam: [sub-ranges + 1] bytes of SAM text in front of a sub-range; the call's longest pair of records
@@ -274,6 +289,7 @@ struct rsq_sim : PrepassSim {
         uint64_t n_held = 0, held_bytes = 0;
         uint64_t call_pairs = 0;             // pairs of the running call's parts so far
         uint32_t call_parts = 1;             // its sub-ranges (option overlap): the staging buffer grows once, for all of them
+        uint64_t call_records = 0, call_mapped = 0;      // sorted_finish: the final records of the call (or the flush), and those of them with a position
         DevBuf keys[2], idx[2], hist, hist_at, sizes, at, flags, run_of, runs, result, out_of_order, windows, window_first;
         BamIndexState index;
     } bam_sorted;
@@ -665,64 +681,79 @@ static void launch_text_waves(K with_order, K in_order, const uint32_t *row_orde
 }
 
 // ---- the stages of one (sub-)range; they work on the simulator's current workspace (s.cur)
-// reads of n_pairs pairs into the raw arrays (fragments on the device, or adapter-only pairs when frags == nullptr) and their record sizes
-struct ReadsDone {
+// What a pairs call was given, built once by its C entry point: the two files' FASTQ buffers, the caller's stream, and where truth alignments and fragments go
+struct PairsCall {
+    struct Out {
+        char *dst = nullptr;
+        size_t cap = 0, *len = nullptr;
+        uint64_t room() const { return dst ? cap : 0; }      // what a kernel may write: nothing without a buffer
+        size_t bytes() const { return len ? *len : 0; }      // what the call came to (a sorted run's flush has no FASTQ outputs)
+    };
+    Out r1, r2;
+    hipStream_t st = nullptr;
+    Out truth;             // the caller's SAM or BAM buffer.  kNoTruth: the call launches no kernel of rsq_sam.h; else it launches the kernels of one format
+    // kBam: BAM records (rsq_bam.h BamFormat) in place of SAM text (SamFormat).  kSortedBam: those of a sorted run (rsq_bamsort.h): the parts write to its staging buffer, sorted_finish to `truth`
+    enum Truth { kNoTruth, kSam, kBam, kSortedBam } kind = kNoTruth;
+    rsq_fragment *frags_out = nullptr;      // rsq_sim_pairs*: the fragments themselves
+    size_t frags_cap = 0;
+    bool has_truth() const { return kind != kNoTruth; }
+    bool bam() const { return kind >= kBam; }
+    bool sorted() const { return kind == kSortedBam; }
+    std::string need() const { return "output buffers too small: need " + std::to_string(r1.bytes()) + " and " + std::to_string(r2.bytes()) + " bytes"; }
+};
+// What the stages of one part work on: its pairs (fragments on the device, or adapter-only pairs when frags == nullptr) and, once reads_stage has run, their reads
+struct Part {
+    const Fragment *frags;
+    const FragmentVar *fvars;      // variants of any kind (variants_mode 2), else nullptr
+    uint64_t n_pairs, adapter_first;
+    uint32_t part;
     RawLayout raw;
     const uint32_t *row_order;
 };
-static ReadsDone reads_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_first, hipStream_t st, const FragmentVar *fvars) {
-    RawLayout raw = raw_layout(s, 2 * n_pairs);
-    s.cur->sizes.reserve(2 * n_pairs * 4 + 16);
-    if (frags && s.dev.meth_ptr && !fvars) {                         // --methylation: CTConversion of both mates' templates first
-        s.cur->templates.reserve(2 * n_pairs * s.template_words * 8 + 16);
-        raw.templates = s.cur->templates.as<uint64_t>();
-        raw.template_words = s.template_words;
-        hipLaunchKernelGGL(k_methylation_templates, dim3(cdiv(2 * n_pairs, 256)), dim3(256), 0, st, s.dev, frags, n_pairs, raw);
+// reads of the part's pairs into the raw arrays and their record sizes
+static void reads_stage(rsq_sim &s, Part &p, hipStream_t st) {
+    p.raw = raw_layout(s, 2 * p.n_pairs);
+    s.cur->sizes.reserve(2 * p.n_pairs * 4 + 16);
+    if (p.frags && (p.fvars || s.dev.meth_ptr)) {                    // both mates' templates written out first
+        s.cur->templates.reserve(2 * p.n_pairs * s.template_words * 8 + 16);
+        p.raw.templates = s.cur->templates.as<uint64_t>();
+        p.raw.template_words = s.template_words;
+    }
+    if (p.frags && s.dev.meth_ptr && !p.fvars) {                     // --methylation: CTConversion of both mates' templates
+        hipLaunchKernelGGL(k_methylation_templates, dim3(cdiv(2 * p.n_pairs, 256)), dim3(256), 0, st, s.dev, p.frags, p.n_pairs, p.raw);
         HIP_CHECK(hipGetLastError());
     }
-    if (frags && fvars) {                                            // variants of any kind: both mates' templates with the allele's variants
-        s.cur->templates.reserve(2 * n_pairs * s.template_words * 8 + 16);
-        raw.templates = s.cur->templates.as<uint64_t>();
-        raw.template_words = s.template_words;
+    if (p.frags && p.fvars) {                                        // variants of any kind: the templates with the allele's variants
         s.timers["variant_templates"].start(st);
-        hipLaunchKernelGGL(k_variant_templates, dim3(cdiv(2 * n_pairs, 256)), dim3(256), 0, st, s.dev, frags, fvars, n_pairs, raw);
+        hipLaunchKernelGGL(k_variant_templates, dim3(cdiv(2 * p.n_pairs, 256)), dim3(256), 0, st, s.dev, p.frags, p.fvars, p.n_pairs, p.raw);
         s.timers["variant_templates"].stop(st);
         HIP_CHECK(hipGetLastError());
     }
-    const uint32_t *row_order = launch_fill_reads(s, frags, n_pairs, adapter_first, raw, st, fvars);
-    return ReadsDone{raw, row_order};
+    p.row_order = launch_fill_reads(s, p.frags, p.n_pairs, p.adapter_first, p.raw, st, p.fvars);
 }
 // FASTQ text of the pairs of reads_stage: their offsets continue at totals[2 * part] / [2 * part + 1] (bytes of text in front of this part, per
 // file), where the part ends goes to totals[2 * (part + 1)] / [.. + 1].  The kernel refuses to write past the caller's capacity.
-static void text_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_first, const ReadsDone &rd, char *r1, size_t r1_cap, char *r2, size_t r2_cap,
-                       uint32_t part, hipStream_t st, const FragmentVar *fvars) {
+static void text_stage(rsq_sim &s, const PairsCall &call, const Part &p, hipStream_t st) {
     rsq_sim::Workspace &w = *s.cur;
+    const uint64_t n_pairs = p.n_pairs;
     w.off_r1.reserve((n_pairs + 1) * 8);
     w.off_r2.reserve((n_pairs + 1) * 8);
     uint64_t *totals = s.totals.as<uint64_t>();
     s.timers["scan"].start(st);
     // both files' record sizes in one set of launches; the call's longest record (the next call's image size, below) comes out of the tile sums' pass
     exclusive_scans(s, ScanArrays{{w.sizes.as<uint32_t>(), w.sizes.as<uint32_t>() + n_pairs}, {w.off_r1.as<uint64_t>(), w.off_r2.as<uint64_t>()},
-                                  {totals + 2 * part, totals + 2 * part + 1}, {totals + 2 * (part + 1), totals + 2 * (part + 1) + 1}},
+                                  {totals + 2 * p.part, totals + 2 * p.part + 1}, {totals + 2 * (p.part + 1), totals + 2 * (p.part + 1) + 1}},
                     2, n_pairs, st, s.longest_record.as<uint32_t>());
     s.timers["scan"].stop(st);
     // the wave's LDS image: sized by the longest record of the call before (the first call takes room for records of 480 bytes); binned rows have a slot per
     // record, each with its own alignment.  This call's longest record goes to totals' last word for the next one.
-    const uint32_t lds = format_lds_bytes(s.format_record_bytes, rd.row_order != nullptr);
+    const uint32_t lds = format_lds_bytes(s.format_record_bytes, p.row_order != nullptr);
     s.timers["format_write"].start(st);
-    launch_text_waves(k_format_write<true>, k_format_write<false>, rd.row_order, dim3(cdiv(n_pairs, kFormatRecords), 2), lds, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw,
-                      w.off_r1.as<uint64_t>(), w.off_r2.as<uint64_t>(), r1, r2, (uint64_t)(r1 ? r1_cap : 0), (uint64_t)(r2 ? r2_cap : 0), fvars, rd.row_order, lds);
+    launch_text_waves(k_format_write<true>, k_format_write<false>, p.row_order, dim3(cdiv(n_pairs, kFormatRecords), 2), lds, st, s.dev, s.names, p.frags, n_pairs, p.adapter_first, p.raw,
+                      w.off_r1.as<uint64_t>(), w.off_r2.as<uint64_t>(), call.r1.dst, call.r2.dst, call.r1.room(), call.r2.room(), p.fvars, p.row_order, lds);
     s.timers["format_write"].stop(st);
     HIP_CHECK(hipGetLastError());
 }
-// What a call that also writes the truth alignments hands down: the caller's SAM (or BAM) buffer.  nullptr: the call launches no kernel of rsq_sam.h.
-struct SamOut {
-    char *dst;
-    size_t cap;
-    size_t *len;
-    bool bam = false;      // BAM records (rsq_bam.h BamFormat) in place of SAM text (SamFormat): a call launches the kernels of one format
-    bool sorted = false;   // BAM records of a sorted run (rsq_bamsort.h): written to the run's staging buffer, with a directory entry each; dst and cap are not used
-};
 // The truth records of the pairs of reads_stage in one format, behind their text_stage on the same stream (it reads the FASTQ offsets' totals: nothing is written
 // unless all three outputs fit so far).  Offsets continue at sam_totals[part]; where the part ends goes to sam_totals[part + 1].  A format has its own side array,
 // timer keys and image size; sizes, offsets and totals live in the same buffers (a call writes one kind).
@@ -748,130 +779,123 @@ static char *sorted_stage_room(rsq_sim &s, uint64_t n_pairs, uint32_t part, hipS
     cap = b.stage[b.cur].bytes() - 32u - b.held_bytes;
     return b.stage[b.cur].as<char>() + b.held_bytes;
 }
+// the directory entries of a sorted run's part, behind its records
 template <class Pair>
-static void sorted_directory(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, const ReadsDone &rd, const Pair *side, const uint64_t *offsets, hipStream_t st) {
+static void sorted_directory(rsq_sim &s, const Part &p, hipStream_t st) {
     rsq_sim::BamSorted &b = s.bam_sorted;
     s.timers["bam_sort_keys"].start(st);
-    hipLaunchKernelGGL(k_bam_sort_keys<Pair>, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, frags, n_pairs, rd.row_order, side, offsets, b.held_bytes,
-                       b.dir[b.cur].as<BamDirEntry>() + b.n_held + 2u * b.call_pairs, s.dev.n_seqs, b.prev_cut, b.plan.pos_bits, b.out_of_order.as<uint32_t>());
+    hipLaunchKernelGGL(k_bam_sort_keys<Pair>, dim3(cdiv(p.n_pairs, 256)), dim3(256), 0, st, p.frags, p.n_pairs, p.row_order, s.cur->bam_side.as<Pair>(), s.cur->off_sam.as<uint64_t>(),
+                       b.held_bytes, b.dir[b.cur].as<BamDirEntry>() + b.n_held + 2u * b.call_pairs, s.dev.n_seqs, b.prev_cut, b.plan.pos_bits, b.out_of_order.as<uint32_t>());
     s.timers["bam_sort_keys"].stop(st);
     HIP_CHECK(hipGetLastError());
-    b.call_pairs += n_pairs;
+    b.call_pairs += p.n_pairs;
 }
 template <class Format>
-static void truth_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_first, const ReadsDone &rd, char *r1, size_t r1_cap, char *r2, size_t r2_cap, const SamOut &sam,
-                        uint32_t part, hipStream_t st, const FragmentVar *fvars) {
+static void truth_stage(rsq_sim &s, const PairsCall &call, const Part &p, hipStream_t st) {
     using Pair = typename Format::Pair;
     constexpr bool bam = Format::kBam;
     const char *sizes_timer = bam ? "bam_sizes" : "sam_sizes", *write_timer = bam ? "bam_write" : "sam_write";
     rsq_sim::Workspace &w = *s.cur;
     DevBuf &side = bam ? w.bam_side : w.sam_side;
+    const uint64_t n_pairs = p.n_pairs;
     w.sam_sizes.reserve(n_pairs * 4 + 16);
     w.off_sam.reserve((n_pairs + 1) * 8);
     side.reserve(n_pairs * sizeof(Pair) + 16);
     uint64_t *totals = s.sam_totals.as<uint64_t>();
-    char *dst = sam.dst;
-    uint64_t cap = sam.dst ? sam.cap : 0;
-    const uint64_t cap1 = r1 ? r1_cap : 0, cap2 = r2 ? r2_cap : 0;
+    char *dst = call.truth.dst;
+    uint64_t cap = call.truth.room();
     s.timers[sizes_timer].start(st);
-    hipLaunchKernelGGL(k_truth_sizes<Format>, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw, rd.row_order, side.as<Pair>(),
-                       w.sam_sizes.as<uint32_t>(), fvars);
+    hipLaunchKernelGGL(k_truth_sizes<Format>, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, s.dev, s.names, p.frags, n_pairs, p.adapter_first, p.raw, p.row_order, side.as<Pair>(),
+                       w.sam_sizes.as<uint32_t>(), p.fvars);
     s.timers[sizes_timer].stop(st);
-    exclusive_scan(s, w.sam_sizes.as<uint32_t>(), n_pairs, w.off_sam.as<uint64_t>(), st, totals + part, totals + part + 1, s.sam_longest.as<uint32_t>());
-    const uint32_t lds = sam_lds_bytes(bam ? s.bam_pair_bytes : s.sam_pair_bytes, rd.row_order != nullptr);
-    if (sam.sorted) dst = sorted_stage_room(s, n_pairs, part, st, cap);
+    exclusive_scan(s, w.sam_sizes.as<uint32_t>(), n_pairs, w.off_sam.as<uint64_t>(), st, totals + p.part, totals + p.part + 1, s.sam_longest.as<uint32_t>());
+    const uint32_t lds = sam_lds_bytes(bam ? s.bam_pair_bytes : s.sam_pair_bytes, p.row_order != nullptr);
+    if (call.sorted()) dst = sorted_stage_room(s, n_pairs, p.part, st, cap);      // (the caller's buffer takes the sorted records: sorted_finish)
     s.timers[write_timer].start(st);
-    launch_text_waves(k_truth_write<Format, true>, k_truth_write<Format, false>, rd.row_order, dim3(cdiv(n_pairs, kSamPairs)), lds, st, s.dev, s.names, frags, n_pairs, adapter_first, rd.raw,
-                      side.as<Pair>(), w.off_sam.as<uint64_t>(), dst, cap, w.off_r1.as<uint64_t>() + n_pairs, w.off_r2.as<uint64_t>() + n_pairs, cap1, cap2, rd.row_order, lds, fvars);
+    launch_text_waves(k_truth_write<Format, true>, k_truth_write<Format, false>, p.row_order, dim3(cdiv(n_pairs, kSamPairs)), lds, st, s.dev, s.names, p.frags, n_pairs, p.adapter_first, p.raw,
+                      side.as<Pair>(), w.off_sam.as<uint64_t>(), dst, cap, w.off_r1.as<uint64_t>() + n_pairs, w.off_r2.as<uint64_t>() + n_pairs, call.r1.room(), call.r2.room(), p.row_order,
+                      lds, p.fvars);
     s.timers[write_timer].stop(st);
     HIP_CHECK(hipGetLastError());
     if constexpr (bam)
-        if (sam.sorted) sorted_directory(s, frags, n_pairs, rd, side.as<Pair>(), w.off_sam.as<uint64_t>(), st);
+        if (call.sorted()) sorted_directory<Pair>(s, p, st);
 }
-static void sam_stage(rsq_sim &s, const Fragment *frags, uint64_t n_pairs, uint64_t adapter_first, const ReadsDone &rd, char *r1, size_t r1_cap, char *r2, size_t r2_cap, const SamOut &sam,
-                      uint32_t part, hipStream_t st, const FragmentVar *fvars = nullptr) {
-    // a reference with variants (accepted only with rsq_sim_truth_variants): the formats in reference coordinates; every other simulator launches what it always did
-    // rsq_sim_truth_md (mapped pairs only: an adapter-only call's records carry no such tags and are written by the formats without): the same four with the tags
-    if (s.truth_md && frags) {
-        if (s.has_variants) (sam.bam ? truth_stage<BamVarMdFormat> : truth_stage<SamVarMdFormat>)(s, frags, n_pairs, adapter_first, rd, r1, r1_cap, r2, r2_cap, sam, part, st, fvars);
-        else (sam.bam ? truth_stage<BamMdFormat> : truth_stage<SamMdFormat>)(s, frags, n_pairs, adapter_first, rd, r1, r1_cap, r2, r2_cap, sam, part, st, nullptr);
-        return;
-    }
-    if (s.has_variants) (sam.bam ? truth_stage<BamVarFormat> : truth_stage<SamVarFormat>)(s, frags, n_pairs, adapter_first, rd, r1, r1_cap, r2, r2_cap, sam, part, st, fvars);
-    else (sam.bam ? truth_stage<BamFormat> : truth_stage<SamFormat>)(s, frags, n_pairs, adapter_first, rd, r1, r1_cap, r2, r2_cap, sam, part, st, nullptr);
-}
-static void begin_sam_totals(rsq_sim &s, uint32_t parts, hipStream_t st) {
-    s.sam_totals.reserve((size_t)(parts + 1) * 8 + 16);
-    s.sam_longest.reserve(8);
-    HIP_CHECK(hipMemsetAsync(s.sam_totals.as<uint64_t>(), 0, 8, st));
-    HIP_CHECK(hipMemsetAsync(s.sam_longest.as<uint32_t>(), 0, 4, st));
-}
-// the SAM side of finish_call: its copies are enqueued in front of it (finish_call waits for the stream), the result read behind it
-static void enqueue_sam_total(rsq_sim &s, uint32_t parts, hipStream_t text_stream) {
-    HIP_CHECK(hipMemcpyAsync(&s.mailbox[6], s.sam_totals.as<uint64_t>() + parts, 8, hipMemcpyDeviceToHost, text_stream));
-    s.mailbox[7] = 0;
-    HIP_CHECK(hipMemcpyAsync(&s.mailbox[7], s.sam_longest.as<uint32_t>(), 4, hipMemcpyDeviceToHost, text_stream));
-}
-static int finish_sam(rsq_sim &s, int rc, const SamOut &sam, size_t r1_len, size_t r2_len) {
-    *sam.len = s.mailbox[6];
-    if ((uint32_t)s.mailbox[7]) (sam.bam ? s.bam_pair_bytes : s.sam_pair_bytes) = (uint32_t)s.mailbox[7] + 16u;
-    if (sam.sorted) return rc;                                       // the staging buffer always fits; what the caller's must hold is known after the sort (sorted_finish)
-    if (rc == RSQ_ENOSPC || (rc == RSQ_OK && (*sam.len > sam.cap || !sam.dst))) {
-        g_last_error = "output buffers too small: need " + std::to_string(r1_len) + " and " + std::to_string(r2_len) + " bytes of FASTQ text and " + std::to_string(*sam.len) +
-                       (sam.bam ? " of BAM records" : " of SAM text");
-        return RSQ_ENOSPC;
-    }
-    return rc;
+// The part's truth records in the call's format.  A reference with variants (accepted only with rsq_sim_truth_variants): the formats in reference coordinates.
+// rsq_sim_truth_md (mapped pairs only: an adapter-only call's records carry no such tags): the same four with the tags.  The formats without variants never see a
+// FragmentVar: a part has them only with variants_mode 2, which rsq_pack.h sets only with variants (its loader of a packed reference trusts the file for that).
+static void sam_stage(rsq_sim &s, const PairsCall &call, const Part &p, hipStream_t st) {
+    using Stage = void (*)(rsq_sim &, const PairsCall &, const Part &, hipStream_t);
+    static const Stage stage[2][2][2] = {{{truth_stage<SamFormat>, truth_stage<BamFormat>}, {truth_stage<SamVarFormat>, truth_stage<BamVarFormat>}},
+                                         {{truth_stage<SamMdFormat>, truth_stage<BamMdFormat>}, {truth_stage<SamVarMdFormat>, truth_stage<BamVarMdFormat>}}};
+    stage[s.truth_md && p.frags][s.has_variants][call.bam()](s, call, p, st);
 }
 static void reset_call_timers(rsq_sim &s) {
     for (auto &t : s.timers) t.second.reset();
 }
-// what a call ends with: the bytes of text of `parts` parts, the variant walk's error flag; the call's streams are idle afterwards
-static int finish_call(rsq_sim &s, uint32_t parts, bool with_variants, char *r1, size_t r1_cap, size_t *r1_len, char *r2, size_t r2_cap, size_t *r2_len, hipStream_t text_stream) {
-    s.mailbox[4] = 0;
-    if (with_variants) HIP_CHECK(hipMemcpyAsync(&s.mailbox[4], s.dev.walk_error, 4, hipMemcpyDeviceToHost, text_stream));
-    HIP_CHECK(hipMemcpyAsync(&s.mailbox[2], s.totals.as<uint64_t>() + 2 * parts, 16, hipMemcpyDeviceToHost, text_stream));
-    HIP_CHECK(hipMemcpyAsync(&s.mailbox[5], s.longest_record.as<uint32_t>(), 4, hipMemcpyDeviceToHost, text_stream));
+// The frame of a pairs call, around its `parts` parts.  begin_call: the totals the parts' offsets continue from.  finish_call: the bytes of text and of truth
+// records, the variant walk's error flag, the image sizes of the next call; the call's streams are idle afterwards.  `mapped`: pairs from the reference, whose
+// walk can fail and whose longest record sizes the next FASTQ image.  An adapter-only call never updated format_record_bytes and must not begin to.
+static void begin_call(rsq_sim &s, const PairsCall &call, uint32_t parts, hipStream_t text_stream) {
+    s.totals.reserve((size_t)(parts + 1) * 16 + 16);
+    s.longest_record.reserve(8);
+    HIP_CHECK(hipMemsetAsync(s.totals.as<uint64_t>(), 0, 16, text_stream));
+    HIP_CHECK(hipMemsetAsync(s.longest_record.as<uint32_t>(), 0, 4, text_stream));
+    if (!call.has_truth()) return;
+    s.sam_totals.reserve((size_t)(parts + 1) * 8 + 16);
+    s.sam_longest.reserve(8);
+    HIP_CHECK(hipMemsetAsync(s.sam_totals.as<uint64_t>(), 0, 8, text_stream));
+    HIP_CHECK(hipMemsetAsync(s.sam_longest.as<uint32_t>(), 0, 4, text_stream));
+}
+static int finish_call(rsq_sim &s, const PairsCall &call, uint32_t parts, bool mapped, hipStream_t text_stream) {
+    rsq_sim::Mailbox &m = *s.mailbox;
+    if (call.has_truth()) {
+        HIP_CHECK(hipMemcpyAsync(&m.truth_bytes, s.sam_totals.as<uint64_t>() + parts, 8, hipMemcpyDeviceToHost, text_stream));
+        HIP_CHECK(hipMemcpyAsync(&m.truth_longest, s.sam_longest.as<uint32_t>(), 4, hipMemcpyDeviceToHost, text_stream));
+    }
+    m.walk_error = 0;
+    if (mapped && s.has_variants) HIP_CHECK(hipMemcpyAsync(&m.walk_error, s.dev.walk_error, 4, hipMemcpyDeviceToHost, text_stream));
+    static_assert(offsetof(rsq_sim::Mailbox, r2_bytes) == offsetof(rsq_sim::Mailbox, r1_bytes) + 8, "one copy fills both");
+    HIP_CHECK(hipMemcpyAsync(&m.r1_bytes, s.totals.as<uint64_t>() + 2 * parts, 16, hipMemcpyDeviceToHost, text_stream));
+    HIP_CHECK(hipMemcpyAsync(&m.longest_record, s.longest_record.as<uint32_t>(), 4, hipMemcpyDeviceToHost, text_stream));
     HIP_CHECK(hipStreamSynchronize(text_stream));
-    *r1_len = s.mailbox[2];
-    *r2_len = s.mailbox[3];
-    if ((uint32_t)s.mailbox[4]) {
+    *call.r1.len = m.r1_bytes;
+    *call.r2.len = m.r2_bytes;
+    int rc = RSQ_OK;
+    if (m.walk_error) {
         HIP_CHECK(hipMemsetAsync(s.dev.walk_error, 0, 4, text_stream));
         HIP_CHECK(hipStreamSynchronize(text_stream));
         g_last_error = kWalkErrorMessage;
-        return RSQ_EINVAL;
+        rc = RSQ_EINVAL;
+    } else if (*call.r1.len > call.r1.cap || *call.r2.len > call.r2.cap || !call.r1.dst || !call.r2.dst) {
+        g_last_error = call.need();
+        rc = RSQ_ENOSPC;
     }
-    if (*r1_len > r1_cap || *r2_len > r2_cap || !r1 || !r2) {
-        g_last_error = "output buffers too small: need " + std::to_string(*r1_len) + " and " + std::to_string(*r2_len) + " bytes";
-        return RSQ_ENOSPC;
+    if (call.has_truth() && m.truth_longest) (call.bam() ? s.bam_pair_bytes : s.sam_pair_bytes) = m.truth_longest + 16u;
+    if (call.has_truth() && !call.sorted()) {                        // (a sorted run's staging buffer always fits; what the caller's must hold is known after the sort: sorted_finish)
+        const uint64_t bytes = *call.truth.len = m.truth_bytes;
+        if (rc == RSQ_ENOSPC || (rc == RSQ_OK && (bytes > call.truth.cap || !call.truth.dst))) {
+            g_last_error = call.need() + " of FASTQ text and " + std::to_string(bytes) + (call.bam() ? " of BAM records" : " of SAM text");
+            rc = RSQ_ENOSPC;
+        }
     }
-    return RSQ_OK;
-}
-static void begin_totals(rsq_sim &s, uint32_t parts, hipStream_t st) {
-    s.totals.reserve((size_t)(parts + 1) * 16 + 16);
-    s.longest_record.reserve(8);
-    HIP_CHECK(hipMemsetAsync(s.totals.as<uint64_t>(), 0, 16, st));
-    HIP_CHECK(hipMemsetAsync(s.longest_record.as<uint32_t>(), 0, 4, st));
+    if (mapped && (rc == RSQ_OK || rc == RSQ_ENOSPC) && m.longest_record) s.format_record_bytes = m.longest_record + 8u;      // for the next call's text stage
+    return rc;
 }
 
 // reads + FASTQ text of adapter-only pairs (Simulator::SimulateAdapterOnlyPairs, Simulator.cpp:2359-2382): one part on the caller's stream
-static int adapter_only_pairs(rsq_sim &s, uint64_t n_pairs, uint64_t adapter_first, char *r1, size_t r1_cap, size_t *r1_len, char *r2, size_t r2_cap, size_t *r2_len, hipStream_t st,
-                              const SamOut *sam = nullptr) {
-    *r1_len = *r2_len = 0;
-    if (sam) *sam->len = 0;
+static int adapter_only_pairs(rsq_sim &s, const PairsCall &call, uint64_t n_pairs, uint64_t adapter_first) {
+    HIP_CHECK(hipSetDevice(s.device));
+    *call.r1.len = *call.r2.len = 0;
+    if (call.has_truth()) *call.truth.len = 0;
     if (!n_pairs) return RSQ_OK;
     reset_call_timers(s);
     s.cur = &s.ws[0];
-    begin_totals(s, 1, st);
-    if (sam) begin_sam_totals(s, 1, st);
-    const ReadsDone rd = reads_stage(s, nullptr, n_pairs, adapter_first, st, nullptr);
-    text_stage(s, nullptr, n_pairs, adapter_first, rd, r1, r1_cap, r2, r2_cap, 0, st, nullptr);
-    if (sam) {
-        sam_stage(s, nullptr, n_pairs, adapter_first, rd, r1, r1_cap, r2, r2_cap, *sam, 0, st);
-        enqueue_sam_total(s, 1, st);
-    }
-    const int rc = finish_call(s, 1, false, r1, r1_cap, r1_len, r2, r2_cap, r2_len, st);
-    return sam ? finish_sam(s, rc, *sam, *r1_len, *r2_len) : rc;
+    begin_call(s, call, 1, call.st);
+    Part p{nullptr, nullptr, n_pairs, adapter_first, 0};
+    reads_stage(s, p, call.st);
+    text_stage(s, call, p, call.st);
+    if (call.has_truth()) sam_stage(s, call, p, call.st);
+    return finish_call(s, call, 1, false, call.st);
 }
 
 // The sieve of one block range on the current workspace: attempt 0 is launched without waiting; collect() waits for it, and if a list overflowed
@@ -882,7 +906,7 @@ struct SieveRun {
     uint32_t n_hits = 0;
     const SlotInfo *slot_table = nullptr;
 };
-static void sieve_attempt(rsq_sim &s, SieveRun &r, int attempt, uint64_t *mail, hipStream_t st) {
+static void sieve_attempt(rsq_sim &s, SieveRun &r, int attempt, rsq_sim::Mailbox::Sieve &mail, hipStream_t st) {
     rsq_sim::Workspace &w = *s.cur;
     const int vm = s.variants_mode;
     if (r.cand_cap >= (1ull << 32)) throw Error("more than 2^32 sieve candidates in one call: use smaller block ranges");
@@ -950,13 +974,12 @@ static void sieve_attempt(rsq_sim &s, SieveRun &r, int attempt, uint64_t *mail, 
     s.timers["sieve"].stop(st);
     HIP_CHECK(hipGetLastError());
     exclusive_scan(s, w.pairs_of.as<uint32_t>(), cand_cap, w.pair_off.as<uint64_t>(), st);
-    mail[1] = 0;
-    HIP_CHECK(hipMemcpyAsync(&mail[0], w.pair_off.as<uint64_t>() + cand_cap, 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(&mail[1], w.hit_count.as<uint32_t>(), 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(&mail[5], w.offsets.as<uint64_t>() + n_slots, 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(&mail.total, w.pair_off.as<uint64_t>() + cand_cap, 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(&mail.n_hits, w.hit_count.as<uint32_t>(), 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(&mail.n_cands, w.offsets.as<uint64_t>() + n_slots, 8, hipMemcpyDeviceToHost, st));
 }
-// false: the range has no start position slots at all
-static bool sieve_launch(rsq_sim &s, SieveRun &r, uint32_t block_lo, uint32_t block_hi, uint64_t *mail, hipStream_t st) {
+// (a range without start position slots launches nothing: r.n_slots and r.total stay 0)
+static void sieve_launch(rsq_sim &s, SieveRun &r, uint32_t block_lo, uint32_t block_hi, rsq_sim::Mailbox::Sieve &mail, hipStream_t st) {
     rsq_sim::Workspace &w = *s.cur;
     const int vm = s.variants_mode;
     r = SieveRun{};
@@ -969,7 +992,7 @@ static bool sieve_launch(rsq_sim &s, SieveRun &r, uint32_t block_lo, uint32_t bl
         HIP_CHECK(hipMemcpy(&ptr[1], s.dev.block_extra_ptr + block_hi, 4, hipMemcpyDeviceToHost));
         r.n_slots += ptr[1] - ptr[0];
     }
-    if (!r.n_slots) return false;
+    if (!r.n_slots) return;
     if (r.n_slots >= (1ull << 32) - kSieveBlock)                     // slot indices are 32 bits wide inside one call
         throw Error("block range too large for one call: at most " + std::to_string(((1ull << 32) - kSieveBlock) / kBlockSize - 1) + " blocks");
     w.counts.reserve(r.n_slots * 4 + 16);
@@ -981,14 +1004,13 @@ static bool sieve_launch(rsq_sim &s, SieveRun &r, uint32_t block_lo, uint32_t bl
     r.cand_cap = std::max<uint64_t>(w.cands.bytes() / sizeof(SieveCand), (uint64_t)(expected_cands + 6.0 * sqrt(expected_cands + 1.0)) + 65536);
     r.hit_cap = std::max<uint64_t>(w.hits.bytes() / sizeof(SieveHit), 0 == vm ? r.cand_cap : r.cand_cap + r.cand_cap / 4);
     sieve_attempt(s, r, 0, mail, st);
-    return true;
 }
-static void sieve_collect(rsq_sim &s, SieveRun &r, uint64_t *mail, hipStream_t st) {
+static void sieve_collect(rsq_sim &s, SieveRun &r, rsq_sim::Mailbox::Sieve &mail, hipStream_t st) {
     for (int attempt = 0;; ++attempt) {
         HIP_CHECK(hipStreamSynchronize(st));
-        r.total = mail[0];
-        r.n_hits = (uint32_t)mail[1];
-        r.n_cands = mail[5];
+        r.total = mail.total;
+        r.n_hits = mail.n_hits;
+        r.n_cands = mail.n_cands;
         if (r.n_cands <= r.cand_cap && r.n_hits <= r.hit_cap) return;
         if (attempt >= 2) throw Error("sieve lists overflowed three times");
         // the candidate count is exact; the hit count is exact once the candidates fit, before that it is scaled up with them
@@ -1049,78 +1071,71 @@ static int check_block_range(const rsq_sim &s, uint32_t block_lo, uint32_t block
     }
     return RSQ_OK;
 }
-static int sim_pairs(rsq_sim &s, uint32_t block_lo, uint32_t block_hi, char *r1, size_t r1_cap, size_t *r1_len, char *r2, size_t r2_cap, size_t *r2_len, uint64_t *n_pairs,
-                     rsq_fragment *frags_out, size_t frags_cap, hipStream_t st, const SamOut *sam = nullptr) {
+static int sim_pairs(rsq_sim &s, const PairsCall &call, uint32_t block_lo, uint32_t block_hi, uint64_t *n_pairs) {
     if (const int rc = check_block_range(s, block_lo, block_hi)) return rc;
     HIP_CHECK(hipSetDevice(s.device));
     *n_pairs = 0;
-    *r1_len = *r2_len = 0;
-    if (sam) *sam->len = 0;
+    *call.r1.len = *call.r2.len = 0;
+    if (call.has_truth()) *call.truth.len = 0;
     if (block_lo == block_hi) return RSQ_OK;
     reset_call_timers(s);
-    const int vm = s.variants_mode;
     const uint32_t parts = pairs_parts(s, block_hi - block_lo);
     // one part: everything on the caller's stream; more: the reads stay there, sieve and text get their own
-    hipStream_t s_reads = st, s_sieve = parts > 1 ? s.side[0] : st, s_text = parts > 1 ? s.side[1] : st;
+    const hipStream_t st = call.st, s_reads = st, s_sieve = parts > 1 ? s.side[0] : st, s_text = parts > 1 ? s.side[1] : st;
     if (parts > 1) {                                                 // the side streams begin where the caller's stream is
         HIP_CHECK(hipEventRecord(s.ev_call, st));
         HIP_CHECK(hipStreamWaitEvent(s_sieve, s.ev_call, 0));
         HIP_CHECK(hipStreamWaitEvent(s_text, s.ev_call, 0));
     }
-    begin_totals(s, parts, s_text);
-    if (sam) begin_sam_totals(s, parts, s_text);
+    begin_call(s, call, parts, s_text);
     struct Abort {                                                   // an error in the middle: nothing of the call may still run when it returns
-        rsq_sim &s;
         bool armed = true;
         ~Abort() {
             if (armed) (void)hipDeviceSynchronize();
         }
-    } abort_guard{s};
+    } abort_guard;
     auto part_range = [&](uint32_t k) {
         const uint64_t n = block_hi - block_lo;
         return std::pair<uint32_t, uint32_t>(block_lo + (uint32_t)(n * k / parts), block_lo + (uint32_t)(n * (k + 1) / parts));
     };
     SieveRun run[2];
-    bool has_slots[2] = {false, false};
     s.cur = &s.ws[0];
-    has_slots[0] = sieve_launch(s, run[0], part_range(0).first, part_range(0).second, s.mailbox + 0, s_sieve);
+    sieve_launch(s, run[0], part_range(0).first, part_range(0).second, s.mailbox->sieve[0], s_sieve);
     uint64_t total_pairs = 0;
     static_assert(sizeof(rsq_fragment) == sizeof(Fragment), "ABI fragment layout");
     for (uint32_t k = 0; k < parts; ++k) {
         const uint32_t p = k & 1u;
         s.cur = &s.ws[p];
         SieveRun &r = run[p];
-        uint64_t *mail = s.mailbox + 8 * p;
-        if (has_slots[p]) sieve_collect(s, r, mail, s_sieve);
-        const uint64_t n = has_slots[p] ? r.total : 0;
-        const Fragment *frags = s.cur->frags.as<Fragment>();
-        const FragmentVar *fvars = nullptr;
+        if (r.n_slots) sieve_collect(s, r, s.mailbox->sieve[p], s_sieve);
+        const uint64_t n = r.total;
+        Part part{nullptr, nullptr, n, 0, k};
         if (n) {
             sieve_emit(s, r, s_sieve);
-            frags = s.cur->frags.as<Fragment>();
-            fvars = 2 == vm ? s.cur->fvars.as<FragmentVar>() : nullptr;
-            if (frags_out) {
-                if (frags_cap < total_pairs + n) {
+            part.frags = s.cur->frags.as<Fragment>();
+            part.fvars = 2 == s.variants_mode ? s.cur->fvars.as<FragmentVar>() : nullptr;
+            if (call.frags_out) {
+                if (call.frags_cap < total_pairs + n) {
                     g_last_error = "fragment buffer too small: need at least " + std::to_string(total_pairs + n) + " records";
                     return RSQ_ENOSPC;
                 }
-                HIP_CHECK(hipMemcpyAsync(frags_out + total_pairs, frags, n * sizeof(Fragment), hipMemcpyDeviceToDevice, s_sieve));
+                HIP_CHECK(hipMemcpyAsync(call.frags_out + total_pairs, part.frags, n * sizeof(Fragment), hipMemcpyDeviceToDevice, s_sieve));
             }
             if (parts > 1) {
                 HIP_CHECK(hipEventRecord(s.ev_emit, s_sieve));
                 HIP_CHECK(hipStreamWaitEvent(s_reads, s.ev_emit, 0));
                 if (k >= 2) HIP_CHECK(hipStreamWaitEvent(s_reads, s.cur->text_done, 0));       // the raw arrays of this workspace were last read by text(k - 2)
             }
-            const ReadsDone rd = reads_stage(s, frags, n, 0, s_reads, fvars);
+            reads_stage(s, part, s_reads);
             if (parts > 1) {
                 HIP_CHECK(hipEventRecord(s.ev_fill, s_reads));
                 HIP_CHECK(hipStreamWaitEvent(s_text, s.ev_fill, 0));
             }
-            text_stage(s, frags, n, 0, rd, r1, r1_cap, r2, r2_cap, k, s_text, fvars);
-            if (sam) sam_stage(s, frags, n, 0, rd, r1, r1_cap, r2, r2_cap, *sam, k, s_text, fvars);
+            text_stage(s, call, part, s_text);
+            if (call.has_truth()) sam_stage(s, call, part, s_text);
         } else {                                                     // no pairs in this part: its text ends where it begins
             HIP_CHECK(hipMemcpyAsync(s.totals.as<uint64_t>() + 2 * (k + 1), s.totals.as<uint64_t>() + 2 * k, 16, hipMemcpyDeviceToDevice, s_text));
-            if (sam) HIP_CHECK(hipMemcpyAsync(s.sam_totals.as<uint64_t>() + k + 1, s.sam_totals.as<uint64_t>() + k, 8, hipMemcpyDeviceToDevice, s_text));
+            if (call.has_truth()) HIP_CHECK(hipMemcpyAsync(s.sam_totals.as<uint64_t>() + k + 1, s.sam_totals.as<uint64_t>() + k, 8, hipMemcpyDeviceToDevice, s_text));
         }
         if (parts > 1) HIP_CHECK(hipEventRecord(s.cur->text_done, s_text));
         total_pairs += n;
@@ -1128,32 +1143,26 @@ static int sim_pairs(rsq_sim &s, uint32_t block_lo, uint32_t block_hi, char *r1,
             s.cur = &s.ws[p ^ 1u];
             if (n) HIP_CHECK(hipStreamWaitEvent(s_sieve, s.ev_fill, 0));
             if (k >= 1) HIP_CHECK(hipStreamWaitEvent(s_sieve, s.cur->text_done, 0));
-            has_slots[p ^ 1u] = sieve_launch(s, run[p ^ 1u], part_range(k + 1).first, part_range(k + 1).second, s.mailbox + 8 * (p ^ 1u), s_sieve);
+            sieve_launch(s, run[p ^ 1u], part_range(k + 1).first, part_range(k + 1).second, s.mailbox->sieve[p ^ 1u], s_sieve);
         }
     }
     *n_pairs = total_pairs;
-    if (sam && total_pairs) enqueue_sam_total(s, parts, s_text);
-    int rc = total_pairs ? finish_call(s, parts, s.has_variants, r1, r1_cap, r1_len, r2, r2_cap, r2_len, s_text) : (int)RSQ_OK;
-    if (sam && total_pairs) rc = finish_sam(s, rc, *sam, *r1_len, *r2_len);
-    if (total_pairs && (rc == RSQ_OK || rc == RSQ_ENOSPC) && (uint32_t)s.mailbox[5]) s.format_record_bytes = (uint32_t)s.mailbox[5] + 8u;      // for the next call's text stage
-    if (parts > 1) {                                                 // the caller's stream continues behind the whole call
-        HIP_CHECK(hipStreamSynchronize(s_sieve));
-        HIP_CHECK(hipStreamSynchronize(s_text));
-        HIP_CHECK(hipStreamSynchronize(s_reads));
-    } else HIP_CHECK(hipStreamSynchronize(st));
+    const int rc = total_pairs ? finish_call(s, call, parts, true, s_text) : (int)RSQ_OK;      // (no pairs at all: the lengths stay 0, nothing to wait for but the sieves)
+    if (parts > 1)                                                   // the caller's stream continues behind the whole call
+        for (hipStream_t side : {s_sieve, s_text}) HIP_CHECK(hipStreamSynchronize(side));
+    HIP_CHECK(hipStreamSynchronize(st));
     abort_guard.armed = false;
     return rc;
 }
 
 // The end of a sorted call (rsq_bamsort.h), behind its parts -- or, at the flush, over the held records alone: the sort of the directory's keys, the cut, and,
-// when every buffer of the call fits, the gather into the caller's buffer and the index material.  Until then nothing of the run's state has changed (the
-// held records and their entries lie untouched in front of the call's), so a call that ends with RSQ_ENOSPC can be repeated.  rc: what the parts came to.
-static int sorted_finish(rsq_sim &s, int rc, uint64_t cut, uint32_t block_hi, char *out, size_t cap, size_t *len, uint64_t *n_records, uint64_t *n_mapped, size_t r1_len, size_t r2_len,
-                         hipStream_t st) {
+// when every buffer of the call fits, the gather into the caller's buffer (call.truth) and the index material.  Until then nothing of the run's state has changed
+// (the held records and their entries lie untouched in front of the call's), so a call that ends with RSQ_ENOSPC can be repeated.  rc: what the parts came to.
+static int sorted_finish(rsq_sim &s, const PairsCall &call, int rc, uint64_t cut, uint32_t block_hi) {
     rsq_sim::BamSorted &b = s.bam_sorted;
+    const hipStream_t st = call.st;
     const uint64_t n = b.n_held + 2u * b.call_pairs;
-    *len = 0;
-    *n_records = *n_mapped = 0;
+    *call.truth.len = b.call_records = b.call_mapped = 0;
     if (n >= (1ull << 32)) throw Error("more than 2^32 BAM records in one sorted call: use smaller block ranges");
     if (!n) {
         if (rc == RSQ_OK) {
@@ -1198,12 +1207,11 @@ static int sorted_finish(rsq_sim &s, int rc, uint64_t cut, uint32_t block_hi, ch
         g_last_error = "sorted BAM: " + std::to_string(r[5]) + " records lie below the cut of the call before or outside their sequence: the stream would not be sorted";
         return RSQ_EINVAL;
     }
-    *len = final_bytes;
-    *n_records = n_final;
-    *n_mapped = mapped;
-    if (rc == RSQ_ENOSPC || (rc == RSQ_OK && (final_bytes > cap || (!out && final_bytes)))) {
-        g_last_error = "output buffers too small: need " + std::to_string(r1_len) + " and " + std::to_string(r2_len) + " bytes of FASTQ text and " + std::to_string(final_bytes) +
-                       " of sorted BAM records";
+    *call.truth.len = final_bytes;
+    b.call_records = n_final;
+    b.call_mapped = mapped;
+    if (rc == RSQ_ENOSPC || (rc == RSQ_OK && (final_bytes > call.truth.cap || (!call.truth.dst && final_bytes)))) {
+        g_last_error = call.need() + " of FASTQ text and " + std::to_string(final_bytes) + " of sorted BAM records";
         return RSQ_ENOSPC;
     }
     if (rc != RSQ_OK) return rc;
@@ -1212,7 +1220,7 @@ static int sorted_finish(rsq_sim &s, int rc, uint64_t cut, uint32_t block_hi, ch
     b.stage[other].reserve(held_bytes + 32u);
     b.dir[other].reserve(n_held * sizeof(BamDirEntry) + 8u);
     s.timers["bam_gather"].start(st);
-    hipLaunchKernelGGL(k_bam_gather, dim3((uint32_t)cdiv(n, 16)), dim3(256), 0, st, dir, idx, b.at.as<uint64_t>(), n, n_final, b.stage[b.cur].as<char>(), out, b.stage[other].as<char>(),
+    hipLaunchKernelGGL(k_bam_gather, dim3((uint32_t)cdiv(n, 16)), dim3(256), 0, st, dir, idx, b.at.as<uint64_t>(), n, n_final, b.stage[b.cur].as<char>(), call.truth.dst, b.stage[other].as<char>(),
                        b.dir[other].as<BamDirEntry>());
     s.timers["bam_gather"].stop(st);
     HIP_CHECK(hipGetLastError());
@@ -1650,7 +1658,7 @@ int rsq_sim_create(const rsq_profile *p, const rsq_ref *ref, int device, rsq_sim
         s->n_cu = (uint32_t)prop.multiProcessorCount;
         s->arch = prop.gcnArchName;
         s->specialize = s->opt.specialize != 0;
-        HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&s->mailbox), 16 * sizeof(uint64_t), hipHostMallocDefault));
+        HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&s->mailbox), sizeof(rsq_sim::Mailbox), hipHostMallocDefault));
         for (hipStream_t &st : s->side) HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
         for (rsq_sim::Workspace &w : s->ws) HIP_CHECK(hipEventCreateWithFlags(&w.text_done, hipEventDisableTiming));
         HIP_CHECK(hipEventCreateWithFlags(&s->ev_call, hipEventDisableTiming));
@@ -2010,11 +2018,6 @@ int rsq_sim_get_adapter_sys_errors(const rsq_sim *s, int seg, uint32_t adapter, 
     return download_sys(s, s->adapter_sys[seg] + a.seq_ptr[adapter], dom_out, rate_out, len);
 }
 
-int rsq_sim_pairs(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len,
-                  uint64_t *n_pairs, rsq_fragment *frags_dev, size_t frags_cap, void *stream) {
-    REQUIRE(s && r1_len && r2_len && n_pairs, "null argument");
-    return guard([&] { return sim_pairs(*s, block_lo, block_hi, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, n_pairs, frags_dev, frags_cap, (hipStream_t)stream); });
-}
 // Truth alignments, as SAM text or (bam) as BAM records.  A reference with variants is refused unless the caller has chosen the coordinate system of the record
 // (rsq_sim_truth_variants: reference coordinates, rsq_sam.h SamVarFormat).  What BAM cannot hold is refused as well, before anything is launched: l_read_name is a byte, so no QNAME may exceed 254 characters (the base
 // identifier, the longest reference name, every number at its widest), and the bins cover 2^29 bases.
@@ -2065,20 +2068,23 @@ int rsq_sim_truth_md(rsq_sim *s, int on) {
     }
     return RSQ_OK;
 }
-static int pairs_truth(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len, char *out_dev,
-                       size_t out_cap, size_t *out_len, uint64_t *n_pairs, rsq_fragment *frags_dev, size_t frags_cap, void *stream, bool bam) {
-    REQUIRE(s && r1_len && r2_len && out_len && n_pairs, "null argument");
-    if (truth_refusal(*s, bam)) return RSQ_EINVAL;
-    const SamOut out{out_dev, out_cap, out_len, bam};
-    return guard([&] { return sim_pairs(*s, block_lo, block_hi, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, n_pairs, frags_dev, frags_cap, (hipStream_t)stream, &out); });
+// the entry points of the pairs calls
+static int pairs_call(rsq_sim *s, const PairsCall &call, uint32_t block_lo, uint32_t block_hi, uint64_t *n_pairs) {
+    REQUIRE(s && call.r1.len && call.r2.len && (call.truth.len || !call.has_truth()) && n_pairs, "null argument");
+    if (call.has_truth() && truth_refusal(*s, call.bam())) return RSQ_EINVAL;
+    return guard([&] { return sim_pairs(*s, call, block_lo, block_hi, n_pairs); });
+}
+int rsq_sim_pairs(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len,
+                  uint64_t *n_pairs, rsq_fragment *frags_dev, size_t frags_cap, void *stream) {
+    return pairs_call(s, PairsCall{{r1_dev, r1_cap, r1_len}, {r2_dev, r2_cap, r2_len}, (hipStream_t)stream, {}, PairsCall::kNoTruth, frags_dev, frags_cap}, block_lo, block_hi, n_pairs);
 }
 int rsq_sim_pairs_sam(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len, char *sam_dev,
                       size_t sam_cap, size_t *sam_len, uint64_t *n_pairs, rsq_fragment *frags_dev, size_t frags_cap, void *stream) {
-    return pairs_truth(s, block_lo, block_hi, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, sam_dev, sam_cap, sam_len, n_pairs, frags_dev, frags_cap, stream, false);
+    return pairs_call(s, PairsCall{{r1_dev, r1_cap, r1_len}, {r2_dev, r2_cap, r2_len}, (hipStream_t)stream, {sam_dev, sam_cap, sam_len}, PairsCall::kSam, frags_dev, frags_cap}, block_lo, block_hi, n_pairs);
 }
 int rsq_sim_pairs_bam(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len, char *bam_dev,
                       size_t bam_cap, size_t *bam_len, uint64_t *n_pairs, rsq_fragment *frags_dev, size_t frags_cap, void *stream) {
-    return pairs_truth(s, block_lo, block_hi, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, bam_dev, bam_cap, bam_len, n_pairs, frags_dev, frags_cap, stream, true);
+    return pairs_call(s, PairsCall{{r1_dev, r1_cap, r1_len}, {r2_dev, r2_cap, r2_len}, (hipStream_t)stream, {bam_dev, bam_cap, bam_len}, PairsCall::kBam, frags_dev, frags_cap}, block_lo, block_hi, n_pairs);
 }
 
 // ---- the truth BAM sorted by coordinate (rsq_bamsort.h; include/reseq_amd.h rsq_sim_bam_sorted_*)
@@ -2135,14 +2141,14 @@ int rsq_sim_pairs_bam_sorted(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, c
         b.call_parts = block_hi > block_lo ? pairs_parts(*s, block_hi - block_lo) : 1u;
         HIP_CHECK(hipMemsetAsync(b.out_of_order.as<uint32_t>(), 0, 4, st));
         HIP_CHECK(hipStreamSynchronize(st));                         // (a pipelined call's parts run on other streams)
-        size_t unsorted_len = 0;
-        SamOut out{nullptr, 0, &unsorted_len, true, true};
-        const int rc = sim_pairs(*s, block_lo, block_hi, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, n_pairs, frags_dev, frags_cap, st, &out);
+        const PairsCall call{{r1_dev, r1_cap, r1_len}, {r2_dev, r2_cap, r2_len}, st, {bam_dev, bam_cap, bam_len}, PairsCall::kSortedBam, frags_dev, frags_cap};
+        const int rc = sim_pairs(*s, call, block_lo, block_hi, n_pairs);
         if (rc != RSQ_OK && rc != RSQ_ENOSPC) return rc;
         if (rc == RSQ_ENOSPC && !*n_pairs) return rc;                // the fragment buffer was too small: the call ended in the middle of its parts, no size is known yet
         const uint64_t cut = bam_cut_key(block_hi, s->total_blocks, s->dev.n_seqs, s->block_seq.data(), s->first_block.data(), kBlockSize);
-        uint64_t mapped = 0;
-        return sorted_finish(*s, rc, cut, block_hi, bam_dev, bam_cap, bam_len, n_records, &mapped, *r1_len, *r2_len, st);
+        const int end = sorted_finish(*s, call, rc, cut, block_hi);
+        *n_records = b.call_records;
+        return end;
     });
 }
 int rsq_sim_bam_sorted_flush(rsq_sim *s, char *bam_dev, size_t bam_cap, size_t *bam_len, uint64_t *n_mapped, uint64_t *n_unmapped, void *stream) {
@@ -2160,9 +2166,10 @@ int rsq_sim_bam_sorted_flush(rsq_sim *s, char *bam_dev, size_t bam_cap, size_t *
         reset_call_timers(*s);
         b.call_pairs = 0;
         HIP_CHECK(hipMemsetAsync(b.out_of_order.as<uint32_t>(), 0, 4, st));
-        uint64_t n_records = 0;
-        const int rc = sorted_finish(*s, RSQ_OK, kBamCutAll, b.next_block, bam_dev, bam_cap, bam_len, &n_records, n_mapped, 0, 0, st);
-        *n_unmapped = n_records - *n_mapped;
+        const PairsCall call{{}, {}, st, {bam_dev, bam_cap, bam_len}, PairsCall::kSortedBam};        // a sorted call without parts or FASTQ outputs
+        const int rc = sorted_finish(*s, call, RSQ_OK, kBamCutAll, b.next_block);
+        *n_mapped = b.call_mapped;
+        *n_unmapped = b.call_records - b.call_mapped;
         if (rc == RSQ_OK) b.open = false;
         return rc;
     });
@@ -2233,7 +2240,7 @@ int rsq_sim_job_generate(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, uint3
                 uint64_t n = 0;
                 char *dst[2];
                 for (int f = 0; f < 2; ++f) dst[f] = job.chunks[f].back()->as<char>() + job.used[f].back();
-                const int rc = sim_pairs(*s, lo, hi, dst[0], room(0), &len[0], dst[1], room(1), &len[1], &n, nullptr, 0, (hipStream_t)stream);
+                const int rc = sim_pairs(*s, PairsCall{{dst[0], room(0), &len[0]}, {dst[1], room(1), &len[1]}, (hipStream_t)stream}, lo, hi, &n);
                 if (rc == RSQ_ENOSPC && attempt < 2) {              // the estimate was too small (the first call has none): arrays for what the call asked
                     for (int f = 0; f < 2; ++f)
                         if (len[f] > room(f)) new_chunk(f, len[f] + len[f] / 16 + 65536);
@@ -2630,31 +2637,23 @@ int rsq_sim_job_read(rsq_sim *s, int file, uint64_t at, size_t bytes, char *dst_
     });
 }
 
+// the adapter-only entry points
+static int adapter_only_call(rsq_sim *s, const PairsCall &call, uint64_t first, uint64_t n) {
+    REQUIRE(s && call.r1.len && call.r2.len && (call.truth.len || !call.has_truth()) && s->prepared, "simulator not prepared");
+    if (call.has_truth() && truth_refusal(*s, call.bam())) return RSQ_EINVAL;
+    return guard([&] { return adapter_only_pairs(*s, call, n, first); });
+}
 int rsq_sim_adapter_only_pairs(rsq_sim *s, uint64_t first, uint64_t n, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len,
                                void *stream) {
-    REQUIRE(s && r1_len && r2_len && s->prepared, "simulator not prepared");
-    return guard([&] {
-        HIP_CHECK(hipSetDevice(s->device));
-        return adapter_only_pairs(*s, n, first, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, (hipStream_t)stream);
-    });
-}
-static int adapter_only_pairs_truth(rsq_sim *s, uint64_t first, uint64_t n, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len, char *out_dev,
-                                    size_t out_cap, size_t *out_len, void *stream, bool bam) {
-    REQUIRE(s && r1_len && r2_len && out_len && s->prepared, "simulator not prepared");
-    if (truth_refusal(*s, bam)) return RSQ_EINVAL;
-    const SamOut out{out_dev, out_cap, out_len, bam};
-    return guard([&] {
-        HIP_CHECK(hipSetDevice(s->device));
-        return adapter_only_pairs(*s, n, first, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, (hipStream_t)stream, &out);
-    });
+    return adapter_only_call(s, PairsCall{{r1_dev, r1_cap, r1_len}, {r2_dev, r2_cap, r2_len}, (hipStream_t)stream}, first, n);
 }
 int rsq_sim_adapter_only_pairs_sam(rsq_sim *s, uint64_t first, uint64_t n, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len, char *sam_dev,
                                    size_t sam_cap, size_t *sam_len, void *stream) {
-    return adapter_only_pairs_truth(s, first, n, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, sam_dev, sam_cap, sam_len, stream, false);
+    return adapter_only_call(s, PairsCall{{r1_dev, r1_cap, r1_len}, {r2_dev, r2_cap, r2_len}, (hipStream_t)stream, {sam_dev, sam_cap, sam_len}, PairsCall::kSam}, first, n);
 }
 int rsq_sim_adapter_only_pairs_bam(rsq_sim *s, uint64_t first, uint64_t n, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len, char *bam_dev,
                                    size_t bam_cap, size_t *bam_len, void *stream) {
-    return adapter_only_pairs_truth(s, first, n, r1_dev, r1_cap, r1_len, r2_dev, r2_cap, r2_len, bam_dev, bam_cap, bam_len, stream, true);
+    return adapter_only_call(s, PairsCall{{r1_dev, r1_cap, r1_len}, {r2_dev, r2_cap, r2_len}, (hipStream_t)stream, {bam_dev, bam_cap, bam_len}, PairsCall::kBam}, first, n);
 }
 
 // A profile with several read lengths draws a record's read length from tables over the fragment length (draw_read_length): a length outside them ends the call
@@ -2672,14 +2671,14 @@ static void check_fragment_lengths(rsq_sim *s, uint64_t n, const uint8_t *seg_de
     if (!any) return;
     s->cur->rec_count.reserve(16);
     uint32_t *flag = s->cur->rec_count.as<uint32_t>() + 2;            // (words 0 and 1 are the partition's counts)
-    uint32_t *mail = reinterpret_cast<uint32_t *>(&s->mailbox[6]);
-    mail[0] = 0xFFFFFFFFu;
-    HIP_CHECK(hipMemcpyAsync(flag, mail, 4, hipMemcpyHostToDevice, st));
+    uint32_t &mail = s->mailbox->bad_fragment;
+    mail = 0xFFFFFFFFu;
+    HIP_CHECK(hipMemcpyAsync(flag, &mail, 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_fragment_range, dim3(cdiv(n, 256)), dim3(256), 0, st, seg_dev, frag_len_dev, n, range, flag);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(mail, flag, 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(&mail, flag, 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
-    const uint32_t bad = mail[0];
+    const uint32_t bad = mail;
     if (bad == 0xFFFFFFFFu) return;
     uint32_t fl = 0;
     uint8_t seg = 0;
@@ -2766,11 +2765,11 @@ static int error_model_text(rsq_sim *s, const RawLayout &raw, uint64_t n, const 
                       (uint64_t)text_cap, lds);
     s->timers["format_write"].stop(st);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(&s->mailbox[2], s->cur->off_r1.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(&s->mailbox[5], s->longest_record.as<uint32_t>(), 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(&s->mailbox->text_bytes, s->cur->off_r1.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(&s->mailbox->text_longest, s->longest_record.as<uint32_t>(), 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
-    *text_len = s->mailbox[2];
-    if ((uint32_t)s->mailbox[5]) s->record_text_bytes = (uint32_t)s->mailbox[5] + 8u;
+    *text_len = s->mailbox->text_bytes;
+    if (s->mailbox->text_longest) s->record_text_bytes = s->mailbox->text_longest + 8u;
     if (*text_len > text_cap) {
         g_last_error = "text buffer too small: need " + std::to_string(*text_len) + " bytes";
         return (int)RSQ_ENOSPC;
@@ -2847,9 +2846,10 @@ int rsq_sim_error_model_fasta(rsq_sim *s, uint64_t first_index, const char *text
         const dim3 tgrid(cdiv(n_tiles, fasta::kStartsBlock / 64u)), tblock(fasta::kStartsBlock);
         hipLaunchKernelGGL(fasta::k_fasta_count, tgrid, tblock, 0, st, text, (uint64_t)text_len, n_tiles, w.fa_counts.as<uint32_t>());
         exclusive_scan(*s, w.fa_counts.as<uint32_t>(), n_tiles, w.fa_first.as<uint64_t>(), st);
-        HIP_CHECK(hipMemcpyAsync(&s->mailbox[0], w.fa_first.as<uint64_t>() + n_tiles, 8, hipMemcpyDeviceToHost, st));
+        rsq_sim::Mailbox &mail = *s->mailbox;
+        HIP_CHECK(hipMemcpyAsync(&mail.fasta_starts, w.fa_first.as<uint64_t>() + n_tiles, 8, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
-        const uint64_t starts = s->mailbox[0];
+        const uint64_t starts = mail.fasta_starts;
         if (starts >= 0xFFFFFFFFull) throw Error("more than 2^32 records in one block of text");
         w.fa_at.reserve(roomy((starts + 1) * 4));
         hipLaunchKernelGGL(fasta::k_fasta_starts, tgrid, tblock, 0, st, text, (uint64_t)text_len, n_tiles, w.fa_first.as<uint64_t>(), w.fa_at.as<uint32_t>());
@@ -2861,15 +2861,13 @@ int rsq_sim_error_model_fasta(rsq_sim *s, uint64_t first_index, const char *text
         w.fa_seg.reserve(roomy(n));
         w.fa_codes.reserve(roomy(2 * (text_len + 8)));                // a half-word per byte of text: a record's codes lie at its own offset
         uint32_t *summary = w.fa_summary.as<uint32_t>();
-        const uint32_t init[4] = {0u, 0xFFFFFFFFu, 0u, 0u};
-        uint32_t *mail = reinterpret_cast<uint32_t *>(&s->mailbox[0]);              // [0..3] summary, [4] the first start, [5] the last start
-        memcpy(mail, init, sizeof init);
-        HIP_CHECK(hipMemcpyAsync(summary, mail, sizeof init, hipMemcpyHostToDevice, st));
+        mail.fasta_summary = {0u, 0xFFFFFFFFu, 0u, 0u};
+        HIP_CHECK(hipMemcpyAsync(summary, &mail.fasta_summary, 16, hipMemcpyHostToDevice, st));
         // text in front of the first record: [0, at[0]) -- at[0] = text_len without any record
-        HIP_CHECK(hipMemcpyAsync(&mail[4], w.fa_at.as<uint32_t>(), 4, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(&mail[5], w.fa_at.as<uint32_t>() + (starts ? starts - 1 : 0), 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(&mail.fasta_lead_end, w.fa_at.as<uint32_t>(), 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(&mail.fasta_last_start, w.fa_at.as<uint32_t>() + (starts ? starts - 1 : 0), 4, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
-        const uint32_t lead_end = mail[4], last_start = mail[5];
+        const uint32_t lead_end = mail.fasta_lead_end, last_start = mail.fasta_last_start;
         reset_call_timers(*s);
         s->timers["parse_records"].start(st);
         const fasta::Records rec{w.fa_at.as<uint32_t>(), w.fa_len.as<uint32_t>(), w.fa_id_len.as<uint32_t>(), w.fa_frag_len.as<uint32_t>(), w.fa_seg.as<uint8_t>()};
@@ -2882,10 +2880,10 @@ int rsq_sim_error_model_fasta(rsq_sim *s, uint64_t first_index, const char *text
         }
         s->timers["parse_records"].stop(st);
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(mail, summary, 16, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(&mail.fasta_summary, summary, 16, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
-        const uint32_t longest = mail[0], first_bad = mail[1];
-        if (mail[2]) {
+        const uint32_t longest = mail.fasta_summary.longest, first_bad = mail.fasta_summary.first_bad;
+        if (mail.fasta_summary.stray_text) {
             g_last_error = "sequence data without a header line in the input";
             return (int)RSQ_EIO;
         }

@@ -104,6 +104,35 @@ def test_pipelined_sub_ranges_and_binned_rows(tiny, workdir, rsq_options, option
         c.close()
 
 
+def test_parts_without_pairs(workdir, rsq_options):
+    """a pipelined truth call some of whose parts hold no pair: 40 pairs on TINY's nine blocks leave a block in the middle (and the last one) empty, and
+    option overlap = the number of blocks makes every block a part of its own.  Such a part's text, SAM text and records end where they begin, on the
+    workspace it alternates to; the three outputs are those of the call in one part."""
+    sparse = lambda: Case(workdir, "tiny_e2e", synth.TINY, [5000, 80, 3210], 7, 40)
+    c = sparse()
+    try:
+        tb = c.tb
+        want_sam = c.sim.pairs_sam(1, tb + 1)
+        want_sorted = run_sorted(c.sim, [1, tb + 1])
+    finally:
+        c.close()
+    rsq_options("overlap", tb)
+    c = sparse()
+    try:
+        # the teeth: part k of tb parts over [1, tb + 1) is block k + 1 alone
+        per_block = [len(c.sim.pairs(b, b + 1)[0]) for b in range(1, tb + 1)]
+        assert 0 in per_block[1:-1] and per_block[0] > 0 and sum(per_block) == len(want_sam[0]) > 0, per_block
+        filled = sum(n > 0 for n in per_block)
+        frags, f1, f2, sam = c.sim.pairs_sam(1, tb + 1)
+        assert c.sim.last_kernel_launches("sam_write") == filled
+        assert frags.tobytes() == want_sam[0].tobytes() and (f1, f2, sam) == want_sam[1:]
+        stream, calls, f1, f2, frags, flush = run_sorted(c.sim, [1, tb + 1])
+        assert (stream, f1, f2, frags) == (want_sorted[0], want_sorted[2], want_sorted[3], want_sorted[4]) and flush == want_sorted[5]
+        assert len(stream) > 0 and (f1, f2) == want_sam[1:3]
+    finally:
+        c.close()
+
+
 def test_launch_counts(tiny):
     sim, tb = tiny.sim, tiny.tb
     new = lambda: {k: sim.last_kernel_launches(k) for k in NEW_KERNELS}

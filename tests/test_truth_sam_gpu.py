@@ -172,6 +172,20 @@ def test_adapter_only_pairs(tiny):
     assert tiny.sim.adapter_only_pairs_sam(10, 0) == (b"", b"", b"")
 
 
+def test_calls_of_two_kinds_take_turns_on_one_simulator(tiny, workdir):
+    """the pinned words a call's sizes arrive in belong to one kind of call each: an adapter-only call between two calls over the reference changes neither, and
+    is itself the call of a simulator that has made no other"""
+    first = tiny.sim.pairs_sam(1, tiny.tb + 1)
+    between = tiny.sim.adapter_only_pairs_sam(0, 150)
+    third = tiny.sim.pairs_sam(1, tiny.tb + 1)
+    assert first[0].tobytes() == third[0].tobytes() == tiny.whole[0].tobytes() and first[1:] == third[1:] == tiny.whole[1:]
+    fresh = tiny_case(workdir)
+    try:
+        assert fresh.sim.adapter_only_pairs_sam(0, 150) == between and len(between[2]) > 0
+    finally:
+        fresh.close()
+
+
 def test_enospc_leaves_the_buffer_alone(tiny):
     frags, f1, f2, sam = tiny.whole
     dev = tiny.sim.device
