@@ -20,6 +20,8 @@
 //
 // Host and device alike (tests/hostemu/bam_sort_trial.cpp runs them on the CPU): bam_sort_key, bam_sort_plan, bam_sort_digit, bam_dir_entry, bam_lower_bound,
 // bam_sort_pass_host (a pass's tile / digit / rank arithmetic as a loop), BamIndexState and bam_bai_bytes (plain host code).
+// tests/hostemu/kernel_trial.cpp runs the sort's passes (bam_sort_passes), the cut, the gather and the index kernels alone on crafted keys, entries and
+// records (tests/test_kernel_trial_gpu.py): the ballot ranking and the byte funnel have no host form.
 #pragma once
 #include <algorithm>
 #include <map>
@@ -312,6 +314,21 @@ __global__ void __launch_bounds__(kBamSortBlock) k_bam_sort_scatter(const uint64
         keys_out[place] = key[r];
         idx_out[place] = idx[i];
     }
+}
+// The passes of the sort: per pass the tiles' digit counts, their exclusive scan (scan(hist, tiles * kBamSortBins, hist_at): the library's, on the same stream) and
+// the scatter into the other pair of buffers.  keys[0] / idx[0] hold the input, hist has tiles * kBamSortBins words and hist_at one more, with
+// tiles = ceil(n / kBamSortTile); n >= 1.  Returns which pair of buffers the sorted items lie in.
+template <class Scan>
+inline int bam_sort_passes(uint64_t *const keys[2], uint32_t *const idx[2], uint64_t n, const BamSortPlan &plan, uint32_t *hist, uint64_t *hist_at, Scan &&scan, hipStream_t st) {
+    const uint32_t tiles = (uint32_t)((n + kBamSortTile - 1u) / kBamSortTile);
+    int from = 0;
+    for (uint32_t pass = 0; pass < plan.passes; ++pass, from ^= 1) {
+        hipLaunchKernelGGL(k_bam_sort_hist, dim3(tiles), dim3(kBamSortBlock), 0, st, (const uint64_t *)keys[from], n, pass, plan.pos_bits, hist);
+        scan((const uint32_t *)hist, (uint64_t)tiles * kBamSortBins, hist_at);
+        hipLaunchKernelGGL(k_bam_sort_scatter, dim3(tiles), dim3(kBamSortBlock), 0, st, (const uint64_t *)keys[from], (const uint32_t *)idx[from], n, pass, plan.pos_bits,
+                           (const uint64_t *)hist_at, keys[from ^ 1], idx[from ^ 1]);
+    }
+    return from;
 }
 // the records' sizes in sorted order (their scan gives every record its place)
 __global__ void __launch_bounds__(256) k_bam_sorted_sizes(const BamDirEntry *dir, const uint32_t *idx, uint64_t n, uint32_t *sizes) {

@@ -198,8 +198,9 @@ RSQ_HD RecordError parse_record(P rec, uint64_t size, const Out &out, RecordFiel
 #if RSQ_DEVICE_BUILD
 constexpr uint32_t kTileBytes = 4096, kStartsBlock = 256;        // a wave per tile, four tiles per workgroup
 // record starts in tile `tile`: f(position, rank within the tile) for each, returns their number.  A lane takes 16 bytes of a step's 1024 as two words: the '>'
-// bytes whose byte in front is a line end (zero_bytes of the words; the byte in front of the lane's first one is the lane before's last), counted with popcounts
-// and ranked by a prefix sum over the lanes.  [A byte per lane and a ballot per 64 bytes read the text at 0.4 TB/s.]
+// bytes whose byte in front is a line end (zero_bytes of the words; the byte in front of the lane's first one is read from the text, text[p - 1], and none
+// stands in front of the text), counted with popcounts and ranked by a prefix sum over the lanes.  [A byte per lane and a ballot per 64 bytes read the text at
+// 0.4 TB/s.]  No host form: tests/hostemu/kernel_trial.cpp runs it alone, with starts on either side of every seam (tests/test_kernel_trial_gpu.py).
 template <class F>
 __device__ uint32_t tile_starts(const uint8_t *text, uint64_t text_len, uint64_t tile, F &&f) {
     const uint32_t lane = threadIdx.x & 63u;

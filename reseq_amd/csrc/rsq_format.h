@@ -256,6 +256,7 @@ constexpr uint32_t kBinKeysLds = RSQ_BIN_KEYS_LDS;      // up to so many bin key
 constexpr uint32_t kBinItemsPerThread = 16, kBinBlock = 256;
 
 // bin keys of the items + their histogram.  Pairs: key = tile (TileId() once per pair, Simulator.cpp:701-704); records: key = segment * n_tiles + tile.
+// (tests/hostemu/kernel_trial.cpp runs bin_count_key, k_bins_plan and k_bin_scatter alone on given keys, on either side of kBinKeysLds)
 __device__ inline void bin_count_key(uint32_t key, bool valid, uint32_t n_keys, uint32_t *hist, uint32_t *s_hist) {
     if (n_keys <= kBinKeysLds) {
         for (uint32_t k = threadIdx.x; k < n_keys; k += blockDim.x) s_hist[k] = 0;

@@ -1,5 +1,6 @@
 // rsq_scan.h -- the exclusive prefix sum the sieve and the record partition place their output by (library only):
-//   k_scan_tile_sums, k_scan_tiles, k_scan_apply
+//   k_scan_tile_sums, k_scan_tiles, k_scan_apply, and scan_launch, the three launches of one scan
+// tests/hostemu/kernel_trial.cpp runs these kernels alone, through scan_launch, on inputs no simulation makes (tests/test_kernel_trial_gpu.py).
 #pragma once
 #include "rsq_types.h"
 
@@ -154,6 +155,14 @@ __global__ void __launch_bounds__(kScanBlock) k_scan_apply(ScanArrays a, uint64_
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = *a.total[blockIdx.y];
+}
+// The three launches of a scan of `arrays` (1 or 2) arrays of n elements each: a.total[0 .. arrays) are set, tile_sums has arrays * (tiles + 1) words with
+// tiles = ceil(n / kScanTile), longest as in k_scan_tile_sums.  n >= 1: a grid of no tiles is not launched, so out[0] and *total would stay unwritten.
+inline void scan_launch(const ScanArrays &a, uint32_t arrays, uint64_t n, uint64_t *tile_sums, hipStream_t st, uint32_t *longest) {
+    const uint32_t tiles = (uint32_t)((n + kScanTile - 1u) / kScanTile);
+    hipLaunchKernelGGL(k_scan_tile_sums, dim3(tiles, arrays), dim3(kScanBlock), 0, st, a, n, tile_sums, longest);
+    hipLaunchKernelGGL(k_scan_tiles, dim3(arrays), dim3(kScanTilesBlock), 0, st, a, tile_sums, tiles);
+    hipLaunchKernelGGL(k_scan_apply, dim3(tiles, arrays), dim3(kScanBlock), 0, st, a, n, (const uint64_t *)tile_sums);
 }
 #endif
 

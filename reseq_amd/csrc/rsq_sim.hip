@@ -466,16 +466,14 @@ struct DevicePrepass : PrepassBackend {
 // --------------------------------------------------------------------------------------------- hot path
 // out[i] = *init + in[0] + ... + in[i-1] for i = 0 .. n (init nullptr: 0); the total also goes to *total_out if given
 // `arrays` (1 or 2) of n elements each in one set of launches; longest (nullptr: not wanted) takes the largest element by atomicMax
+// n >= 1 (scan_launch): every caller returns early, or leaves the stage out, for a call, a part or a block of text without items
 static void exclusive_scans(rsq_sim &s, ScanArrays a, uint32_t arrays, uint64_t n, hipStream_t st, uint32_t *longest = nullptr) {
     const uint32_t tiles = cdiv(n, kScanTile);
     s.cur->tile_sums.reserve((size_t)arrays * (tiles + 1) * 8);
     s.cur->scan_total.reserve(16);
     for (uint32_t i = 0; i < arrays; ++i)
         if (!a.total[i]) a.total[i] = s.cur->scan_total.as<uint64_t>() + i;
-    uint64_t *tile_sums = s.cur->tile_sums.as<uint64_t>();
-    hipLaunchKernelGGL(k_scan_tile_sums, dim3(tiles, arrays), dim3(kScanBlock), 0, st, a, n, tile_sums, longest);
-    hipLaunchKernelGGL(k_scan_tiles, dim3(arrays), dim3(kScanTilesBlock), 0, st, a, tile_sums, tiles);
-    hipLaunchKernelGGL(k_scan_apply, dim3(tiles, arrays), dim3(kScanBlock), 0, st, a, n, (const uint64_t *)tile_sums);
+    scan_launch(a, arrays, n, s.cur->tile_sums.as<uint64_t>(), st, longest);
     HIP_CHECK(hipGetLastError());
 }
 static void exclusive_scan(rsq_sim &s, const uint32_t *in, uint64_t n, uint64_t *out, hipStream_t st, const uint64_t *init = nullptr, uint64_t *total_out = nullptr, uint32_t *longest = nullptr) {
@@ -1183,15 +1181,12 @@ static int sorted_finish(rsq_sim &s, const PairsCall &call, int rc, uint64_t cut
     b.sizes.reserve(n * 4u);
     b.at.reserve((n + 1u) * 8u);
     b.result.reserve(64);
-    int from = 0;
+    uint64_t *const sort_keys[2] = {b.keys[0].as<uint64_t>(), b.keys[1].as<uint64_t>()};
+    uint32_t *const sort_idx[2] = {b.idx[0].as<uint32_t>(), b.idx[1].as<uint32_t>()};
     s.timers["bam_sort"].start(st);
-    hipLaunchKernelGGL(k_bam_sort_init, dim3(blocks), dim3(256), 0, st, dir, n, b.keys[0].as<uint64_t>(), b.idx[0].as<uint32_t>());
-    for (uint32_t pass = 0; pass < b.plan.passes; ++pass, from ^= 1) {
-        hipLaunchKernelGGL(k_bam_sort_hist, dim3(tiles), dim3(kBamSortBlock), 0, st, b.keys[from].as<uint64_t>(), n, pass, b.plan.pos_bits, b.hist.as<uint32_t>());
-        exclusive_scan(s, b.hist.as<uint32_t>(), (uint64_t)tiles * kBamSortBins, b.hist_at.as<uint64_t>(), st);
-        hipLaunchKernelGGL(k_bam_sort_scatter, dim3(tiles), dim3(kBamSortBlock), 0, st, b.keys[from].as<uint64_t>(), b.idx[from].as<uint32_t>(), n, pass, b.plan.pos_bits,
-                           b.hist_at.as<uint64_t>(), b.keys[from ^ 1].as<uint64_t>(), b.idx[from ^ 1].as<uint32_t>());
-    }
+    hipLaunchKernelGGL(k_bam_sort_init, dim3(blocks), dim3(256), 0, st, dir, n, sort_keys[0], sort_idx[0]);
+    const int from = bam_sort_passes(sort_keys, sort_idx, n, b.plan, b.hist.as<uint32_t>(), b.hist_at.as<uint64_t>(),
+                                     [&](const uint32_t *in, uint64_t count, uint64_t *out) { exclusive_scan(s, in, count, out, st); }, st);
     const uint64_t *keys = b.keys[from].as<uint64_t>();
     const uint32_t *idx = b.idx[from].as<uint32_t>();
     hipLaunchKernelGGL(k_bam_sorted_sizes, dim3(blocks), dim3(256), 0, st, dir, idx, n, b.sizes.as<uint32_t>());
