@@ -318,8 +318,8 @@ int rsq_sim_adapter_only_pairs(rsq_sim *s, uint64_t first, uint64_t n, char *r1_
  * aligned base, positive for the mate with the smaller POS (segment 0 on a tie); flags 99 / 147 (strand 0), 83 / 163 (strand 1).  Adapter-only pairs (fragment
  * length 0, and all pairs of rsq_sim_adapter_only_pairs_sam) are unmapped: flags 77 / 141, "*" / 0 fields, SEQ and QUAL as in the FASTQ.
  * rsq_ref_sam_header gives the header.  RSQ_ENOSPC: all three needed sizes are reported; the SAM text is written only if all three texts fit, each FASTQ text as by
- * rsq_sim_pairs.  A simulator whose reference has variants (rsq_ref_read_variants) is refused with RSQ_EINVAL unless rsq_sim_truth_variants (below) has chosen
- * the record's coordinate system.  Methylation is fine (only bases change).  Kernel times: "sam_sizes", "sam_write".  rsq_sim_pairs, rsq_sim_adapter_only_pairs and
+ * rsq_sim_pairs.  A simulator whose reference has variants (rsq_ref_read_variants) is refused with RSQ_EINVAL unless rsq_sim_truth_variants or rsq_sim_truth_alleles
+ * (below) has chosen the record's coordinate system.  Methylation is fine (only bases change).  Kernel times: "sam_sizes", "sam_write".  rsq_sim_pairs, rsq_sim_adapter_only_pairs and
  * the job calls launch neither. */
 int rsq_sim_pairs_sam(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len,
                       char *sam_dev, size_t sam_cap, size_t *sam_len, uint64_t *n_pairs, rsq_fragment *frags_dev, size_t frags_cap, void *stream);
@@ -334,7 +334,7 @@ int rsq_sim_adapter_only_pairs_sam(rsq_sim *s, uint64_t first, uint64_t n, char 
  * gives that ("BAM\1", l_text, the text of rsq_ref_sam_header, n_ref, then l_name, name NUL, l_ref per sequence; the `need` / RSQ_ENOSPC contract of
  * rsq_ref_sam_header), and rsq_sim_gzip_device makes the BGZF blocks of a .bam file from header and records as one byte stream (rsq_gzip_eof_member ends it).
  * RSQ_ENOSPC as above: all three sizes are reported, the records are written only if all three buffers fit.  Refused with RSQ_EINVAL before anything is launched:
- * a reference with variants (unless rsq_sim_truth_variants is set); a reference name and base identifier with which a read name could exceed 254 characters (l_read_name is a byte); a sequence of more
+ * a reference with variants (unless rsq_sim_truth_variants or rsq_sim_truth_alleles is set); a reference name and base identifier with which a read name could exceed 254 characters (l_read_name is a byte); a sequence of more
  * than 2^29 bases (the bins' range).  Kernel times: "bam_sizes", "bam_write"; the plain calls and the _sam calls launch neither, these launch neither of the
  * _sam calls' kernels. */
 int rsq_sim_pairs_bam(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len,
@@ -390,6 +390,44 @@ int rsq_sim_bam_sorted_index(rsq_sim *s, const uint64_t *block_u, const uint64_t
  * written by simulators with variants only.  Substitution-only variant sets (allele copies) take the arithmetic of the calls above, with "_allele<a>" and XI:i:0.
  * BAM's QNAME limit counts "_allele<a>". */
 int rsq_sim_truth_variants(rsq_sim *s, int on);
+
+/* The alleles of a reference with variants (rsq_ref_read_variants) as sequences of their own: the sequences the fragments are drawn from
+ * (reseq_amd/csrc/rsq_alleles.h).  Allele a of a sequence is the sequence as the simulator holds it (after rsq_ref_replace_n) with every variant of that allele
+ * applied: a replacement of length 0 deletes the base, one of length 1 substitutes it, one of length n > 1 leaves one base standing with n - 1 inserted bases
+ * behind it.  Alleles are numbered as in the read ids ("_allele<a>").
+ *   The FASTA text has one record per (sequence, allele) in order of seq * num_alleles + allele: ">" the first word of the sequence's name "_allele<a>" "\n"
+ * (the suffix is there with one allele as well), then the bases as ACGT in lines of 70 like rsq_ref_write_fasta's, every line -- the last one too -- ended by
+ * "\n"; an allele without bases is its header line alone.  A record therefore takes header + n + ceil(n / 70) bytes.
+ *   Host code, no device; RSQ_EINVAL for a reference without variants:
+ * rsq_ref_allele_length: the bases of one allele.  rsq_ref_alleles_fasta_size: the bytes of the whole text.  rsq_ref_alleles_fai: its index as samtools faidx
+ * writes it, "NAME\tLENGTH\tOFFSET\t70\t71\n" per record (`need` / RSQ_ENOSPC as for rsq_ref_sam_header).  rsq_ref_sam_header_alleles /
+ * rsq_ref_bam_header_alleles: rsq_ref_sam_header / rsq_ref_bam_header with the alleles as the sequences -- one @SQ / reference entry per record of the text, in
+ * its order, SN its name, LN its length; RSQ_EINVAL when an allele has no bases (a header cannot list it).
+ *   rsq_sim_alleles_fasta writes bytes [at, at + bytes) of the text into device memory at dst_dev, for any at, any bytes and any alignment of dst_dev: a text of
+ * any size is fetched in pieces, and a piece's bytes do not depend on how the text is cut.  Valid after rsq_sim_create on a reference with variants (nothing of
+ * rsq_sim_prepare is needed); RSQ_EINVAL without variants or when at + bytes lies behind the text's end.  One kernel launch per call, complete when the call
+ * returns; kernel time: "alleles_fasta".  No other call launches it, and it changes nothing the other calls read. */
+int rsq_ref_allele_length(const rsq_ref *r, uint32_t seq, uint32_t allele, uint64_t *out);
+int rsq_ref_alleles_fasta_size(const rsq_ref *r, uint64_t *bytes);
+int rsq_ref_alleles_fai(const rsq_ref *r, char *out, size_t cap, size_t *need);
+int rsq_ref_sam_header_alleles(const rsq_ref *r, char *out, size_t cap, size_t *need);
+int rsq_ref_bam_header_alleles(const rsq_ref *r, char *out, size_t cap, size_t *need);
+int rsq_sim_alleles_fasta(rsq_sim *s, uint64_t at, size_t bytes, char *dst_dev, void *stream);
+
+/* Truth alignments in ALLELE coordinates: on != 0, rsq_sim_pairs_sam, rsq_sim_pairs_bam and the adapter-only calls accept a reference with variants and write every
+ * mapped record against the allele the fragment was drawn from -- a record of the text above, a sequence of rsq_ref_sam_header_alleles / rsq_ref_bam_header_alleles
+ * (the headers of these files).  In its allele a fragment is the stretch [hs, he) and the record is the PLAIN record of the calls without variants with start := hs
+ * and end := he: POS = hs + 1 (+ dropped D) for the forward mate, he - template bases + 1 (+ dropped D) for the reverse mate; the CIGAR has the read's own M / I / D
+ * and one S, no element comes from a variant, and XE counts sequencing errors only; TLEN, PNEXT, FLAG, SEQ, QUAL by the plain rules.  RNAME is "<name>_allele<a>",
+ * BAM's refID = next_refID = seq * num_alleles + allele, its bin reg2bin over allele positions.  QNAME and the tags are those of the reference-coordinate record
+ * (rsq_sim_truth_variants: "_allele<a>" when the id has it, XC:Z, XE:i, XI:i -- XI ties the record to the id's reference positions); unmapped records are the
+ * same as there.  hs is the allele coordinate of (start position, XI), the start position's own with a substitution-only set; he is where the reverse mate's
+ * template ends, hs + fragment length except for a fragment that lies inside one insertion.  Every CIGAR can be walked over the alleles' FASTA text.
+ *   A record has one coordinate system: with rsq_sim_truth_variants on this call returns RSQ_EINVAL, and so does that one with this on (on == 0 takes either back).
+ * RSQ_EINVAL too for a simulator whose reference has no variants.  Refused by the truth calls with RSQ_EINVAL before anything is launched: rsq_sim_truth_md on beside
+ * this (MD against the allele is not offered); an allele without bases; for BAM an allele of more than 2^29 bases.  rsq_sim_bam_sorted_begin returns RSQ_EINVAL:
+ * the records of the alleles of one sequence arrive interleaved, so the run's bounded hold-back does not apply.  Kernel times as for the other truth calls. */
+int rsq_sim_truth_alleles(rsq_sim *s, int on);
 
 /* NM:i and MD:Z on every MAPPED truth record, computed on the device in the same call.  Valid after rsq_sim_create; on == 0 (the default): the truth calls write
  * the bytes and launch the kernels they always did.  on != 0 shapes rsq_sim_pairs_sam, rsq_sim_pairs_bam, rsq_sim_pairs_bam_sorted and rsq_sim_bam_sorted_flush;

@@ -60,6 +60,12 @@ SYMBOLS = {
     "rsq_ref_sam_header": (C.c_int, [_vp, C.c_char_p, _sz, _psz]),
     "rsq_ref_bam_header": (C.c_int, [_vp, C.c_char_p, _sz, _psz]),
     "rsq_ref_bam_header_so": (C.c_int, [_vp, C.c_int, C.c_char_p, _sz, _psz]),
+    "rsq_ref_allele_length": (C.c_int, [_vp, _u32, _u32, C.POINTER(_u64)]),
+    "rsq_ref_alleles_fasta_size": (C.c_int, [_vp, C.POINTER(_u64)]),
+    "rsq_ref_alleles_fai": (C.c_int, [_vp, C.c_char_p, _sz, _psz]),
+    "rsq_ref_sam_header_alleles": (C.c_int, [_vp, C.c_char_p, _sz, _psz]),
+    "rsq_ref_bam_header_alleles": (C.c_int, [_vp, C.c_char_p, _sz, _psz]),
+    "rsq_sim_alleles_fasta": (C.c_int, [_vp, _u64, _sz, _vp, _vp]),
     "rsq_ref_load_fasta": (C.c_int, [C.c_char_p, _pp]),
     "rsq_ref_replace_n": (C.c_int, [_vp, _u64]),
     "rsq_ref_free": (None, [_vp]),
@@ -109,6 +115,7 @@ SYMBOLS = {
     "rsq_sim_pairs_bam": (C.c_int, [_vp, _u32, _u32, _vp, _sz, _psz, _vp, _sz, _psz, _vp, _sz, _psz, C.POINTER(_u64), _vp, _sz, _vp]),
     "rsq_sim_adapter_only_pairs_bam": (C.c_int, [_vp, _u64, _u64, _vp, _sz, _psz, _vp, _sz, _psz, _vp, _sz, _psz, _vp]),
     "rsq_sim_truth_variants": (C.c_int, [_vp, C.c_int]),
+    "rsq_sim_truth_alleles": (C.c_int, [_vp, C.c_int]),
     "rsq_sim_truth_md": (C.c_int, [_vp, C.c_int]),
     "rsq_sim_bam_sorted_begin": (C.c_int, [_vp, _u64]),
     "rsq_sim_pairs_bam_sorted": (C.c_int, [_vp, _u32, _u32, _vp, _sz, _psz, _vp, _sz, _psz, _vp, _sz, _psz, C.POINTER(_u64), C.POINTER(_u64), _vp, _sz, _vp]),
@@ -336,6 +343,29 @@ class Reference:
         """rsq_ref_bam_header_so: bam_header() (coordinate 0), or the header of the coordinate-sorted file (1: "@HD VN:1.6 SO:coordinate")"""
         return self._header(lambda h, out, cap, need: lib().rsq_ref_bam_header_so(h, coordinate, out, cap, need))
 
+    # the alleles of a reference with variants as sequences of their own (include/reseq_amd.h "The alleles of a reference with variants")
+    def allele_length(self, seq, allele):
+        v = _u64()
+        _check(lib().rsq_ref_allele_length(self.h, seq, allele, C.byref(v)))
+        return v.value
+
+    def alleles_fasta_size(self):
+        """bytes of the alleles' FASTA text (Simulator.alleles_fasta writes it)"""
+        v = _u64()
+        _check(lib().rsq_ref_alleles_fasta_size(self.h, C.byref(v)))
+        return v.value
+
+    def alleles_fai(self):
+        """the .fai index of that text"""
+        return self._header(lib().rsq_ref_alleles_fai)
+
+    def sam_header_alleles(self):
+        """sam_header() with the alleles as the sequences: one @SQ per record of the alleles' FASTA text"""
+        return self._header(lib().rsq_ref_sam_header_alleles)
+
+    def bam_header_alleles(self):
+        return self._header(lib().rsq_ref_bam_header_alleles)
+
     def read_variants(self, path):
         """Reference::PrepareVariantFile + ReadFirstVariants: returns the number of alleles"""
         _check(lib().rsq_ref_read_variants(self.h, str(path).encode()))
@@ -413,6 +443,7 @@ class Simulator:
 
     def __init__(self, profile, reference=None, device=0):
         self.device = device
+        self.reference = reference
         self.h = C.c_void_p()
         _check(lib().rsq_sim_create(profile.h, reference.h if reference is not None else None, device, C.byref(self.h)))
 
@@ -608,6 +639,25 @@ class Simulator:
     def truth_md(self, on=True):
         """rsq_sim_truth_md: the truth calls append NM:i and MD:Z to every mapped record (computed on the device against the reference as loaded)"""
         _check(lib().rsq_sim_truth_md(self.h, 1 if on else 0))
+
+    def alleles_fasta_device(self, at, nbytes, dst_dev, stream=None):
+        """rsq_sim_alleles_fasta: bytes [at, at + nbytes) of the alleles' FASTA text to dst_dev, a DeviceArray or an address in device memory; returns the return code"""
+        return lib().rsq_sim_alleles_fasta(self.h, at, nbytes, dst_dev.ptr if isinstance(dst_dev, DeviceArray) else dst_dev, stream)
+
+    def alleles_fasta(self, at=0, bytes=None):
+        """bytes [at, at + bytes) of the alleles' FASTA text (bytes None: up to its end), made on the device and downloaded"""
+        n = self.reference.alleles_fasta_size() - at if bytes is None else bytes
+        dst = DeviceArray(self.device, max(n, 8))
+        try:
+            _check(self.alleles_fasta_device(at, n, dst))
+            return dst.to_numpy(np.uint8, n).tobytes()
+        finally:
+            dst.free()
+
+    def truth_alleles(self, on=True):
+        """rsq_sim_truth_alleles: the truth calls accept a reference with variants and write their records in allele coordinates (RNAME <name>_allele<a>; the
+        sequences of Reference.sam_header_alleles / bam_header_alleles and of alleles_fasta)"""
+        _check(lib().rsq_sim_truth_alleles(self.h, 1 if on else 0))
 
     def truth_variants(self, on=True):
         """rsq_sim_truth_variants: the truth calls accept a reference with variants and write their records in reference coordinates (with the XI:i tag)"""

@@ -66,7 +66,7 @@ const std::map<std::string, std::string> kShort = {{"-j", "threads"}, {"-h", "he
                                                    {"-v", "vcfIn"},   {"-p", "probabilitiesIn"}, {"-P", "probabilitiesOut"}, {"-1", "firstReadsOut"},
                                                    {"-2", "secondReadsOut"}, {"-c", "coverage"}, {"-R", "refSim"}, {"-V", "vcfSim"}, {"-i", "input"}, {"-o", "output"}};
 const std::set<std::string> kFlags = {"help", "version", "noBias", "noTiles", "statsOnly", "tiles", "stopAfterEstimation", "noInDelErrors", "noSubstitutionErrors", "maxLenDeletion", "maxReadLength",
-                                      "dumpArchiveLayout", "traceStages", "hostGzip", "truthBamSort", "truthVariants", "truthMD"};
+                                      "dumpArchiveLayout", "traceStages", "hostGzip", "truthBamSort", "truthVariants", "truthMD", "truthAlleles"};
 
 bool parse(int argc, char **argv, int first, Args &a) {
     for (int i = first; i < argc; ++i) {
@@ -398,6 +398,62 @@ struct TruthOut {
           adapter_only(bam_ ? rsq_sim_adapter_only_pairs_bam : rsq_sim_adapter_only_pairs_sam) {}
 };
 
+// --writeAlleles alleles.fa[.gz]: the alleles of the variant file as FASTA (rsq_sim_alleles_fasta), fetched from the device in pieces; .gz: every piece's text as
+// gzip members made on the device, the file ended by the end-of-file member; a plain file gets its index alleles.fa.fai beside it.  A failure leaves no file.
+bool write_alleles(rsq_sim *sim, const rsq_ref *ref, int device, const std::string &path) {
+    constexpr uint64_t kPiece = 64ull << 20;
+    const bool gz = rsq::textio::has_suffix(path, ".gz");
+    INFO("Writing the alleles to " << path);
+    uint64_t total = 0, at_file = 0;
+    bool ok = check(rsq_ref_alleles_fasta_size(ref, &total), "--writeAlleles");
+    if (ok) {
+        const int fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (fd < 0) {
+            ERR("Could not open '" << path << "' for writing.");
+            return false;
+        }
+        ::close(fd);
+    }
+    DevBuffer text, packed;
+    text.device = packed.device = device;
+    for (uint64_t at = 0; ok && at < total; at += kPiece) {
+        size_t n = (size_t)std::min(kPiece, total - at);
+        ok = text.ensure(n) && check(rsq_sim_alleles_fasta(sim, at, n, (char *)text.p, nullptr), "--writeAlleles");
+        const void *src = text.p;
+        if (ok && gz) {
+            ok = packed.ensure(rsq_gzip_bound(n)) && check(rsq_sim_gzip_device(sim, (const char *)text.p, n, (char *)packed.p, packed.cap, &n, nullptr), "Compressing the alleles failed");
+            src = packed.p;
+        }
+        ok = ok && check(rsq_dev_pwrite(device, src, n, path.c_str(), at_file), "Writing the alleles failed");
+        at_file += n;
+    }
+    if (ok && gz) {
+        char eof[32];
+        const size_t n = rsq_gzip_eof_member(eof, sizeof eof);
+        const int fd = ::open(path.c_str(), O_WRONLY);
+        ok = fd >= 0 && pwrite(fd, eof, n, (off_t)at_file) == (ssize_t)n;
+        if (fd >= 0) ::close(fd);
+        if (!ok) ERR("Writing the alleles failed");
+    }
+    if (ok && !gz) {
+        size_t need = 0;
+        rsq_ref_alleles_fai(ref, nullptr, 0, &need);
+        std::string fai(need, '\0');
+        ok = check(rsq_ref_alleles_fai(ref, &fai[0], need, &need), "--writeAlleles");
+        std::ofstream out(path + ".fai", std::ios::binary);
+        out.write(fai.data(), (std::streamsize)fai.size());
+        if (ok && !out.good()) {
+            ERR("Could not write '" << path << ".fai'.");
+            ok = false;
+        }
+    }
+    if (!ok) {
+        remove(path.c_str());
+        remove((path + ".fai").c_str());
+    }
+    return ok;
+}
+
 // illuminaPE on several devices inside one process (Simulator::Simulate starts its own worker threads, Simulator.cpp:2830-2836, and hands them blocks, :2384-2401).
 // N host threads, one simulator each on device (worker % devices): every worker prepares, simulates its contiguous share of the blocks with the text kept in device
 // memory (rsq_sim_job_generate), the exclusive scan of the workers' text sizes gives every worker its place in the two files, and all workers write at once
@@ -410,7 +466,7 @@ struct PeJob {
     uint64_t seed, num_reads;
     double coverage;
     int ref_bias_mode;
-    std::string ref_bias_file, sys_read, sys_write, methylation, out1, out2, base_identifier;
+    std::string ref_bias_file, sys_read, sys_write, methylation, out1, out2, base_identifier, alleles_out;
 };
 struct Worker {
     int device = 0;
@@ -453,6 +509,7 @@ int illumina_pe_on_workers(const PeJob &job, int n_workers, int n_devices) {
         if (!job.ref_bias_file.empty() && w.fail(rsq_sim_set_ref_bias_file(w.sim, job.ref_bias_file.c_str()), "refBiasFile")) return;
         if (!job.methylation.empty() && w.fail(rsq_sim_read_methylation(w.sim, job.methylation.c_str()), "Could not read methylation file")) return;
     });
+    if (ok && !job.alleles_out.empty()) ok = write_alleles(workers[0].sim, job.ref, workers[0].device, job.alleles_out);      // once: the first worker's simulator
     std::string sys_read = job.sys_read;
     if (ok && !job.sys_write.empty()) {                       // main.cpp:351-397: one worker draws and writes the profile, all read it
         INFO("Writing systematic error profile to " << job.sys_write);
@@ -674,7 +731,7 @@ int illumina_pe(const Args &a) {
             ERR("--truthSam: bzip2 output is not supported (write .gz or plain SAM)");
             return 1;
         }
-        if (!vcf_path.empty() && !a.has("truthVariants")) {
+        if (!vcf_path.empty() && !a.has("truthVariants") && !a.has("truthAlleles")) {
             ERR(t.option << ": truth alignments are not available for a reference with variants (-V) unless --truthVariants chooses reference coordinates for them");
             return 1;
         }
@@ -699,11 +756,47 @@ int illumina_pe(const Args &a) {
         ERR("--truthVariants chooses the coordinates of --truthSam / --truthBam: give one of them as well");
         return 1;
     }
+    if (a.has("truthAlleles")) {                                 // allele coordinates: the sequences of --writeAlleles
+        if (!any_truth) {
+            ERR("--truthAlleles chooses the coordinates of --truthSam / --truthBam: give one of them as well");
+            return 1;
+        }
+        if (vcf_path.empty()) {
+            ERR("--truthAlleles writes the truth alignments against the alleles of a variant file: give -V calls.vcf as well");
+            return 1;
+        }
+        if (a.has("truthVariants")) {
+            ERR("--truthAlleles and --truthVariants: a record has one coordinate system, the alleles' or the reference's");
+            return 1;
+        }
+        if (a.has("truthMD")) {
+            ERR("--truthAlleles: NM:i and MD:Z (--truthMD) are not offered against the alleles");
+            return 1;
+        }
+        if (a.has("truthBamSort")) {
+            ERR("--truthAlleles: --truthBamSort is not available in allele coordinates (the records of one sequence's alleles arrive interleaved)");
+            return 1;
+        }
+        for (TruthOut &t : truths) t.header = t.bam ? rsq_ref_bam_header_alleles : rsq_ref_sam_header_alleles;
+    }
     if (a.has("truthMD") && !any_truth) {
         ERR("--truthMD adds the tags NM:i and MD:Z to the records of --truthSam / --truthBam: give one of them as well");
         return 1;
     }
     const char *truth_option = any_truth ? truths.front().option : "";
+    const std::string alleles_out = a.get("writeAlleles", "");
+    if (a.has("writeAlleles") && alleles_out.empty()) {
+        ERR("--writeAlleles needs a file name");
+        return 1;
+    }
+    if (!alleles_out.empty() && vcf_path.empty()) {
+        ERR("--writeAlleles writes the alleles of a variant file: give -V calls.vcf as well");
+        return 1;
+    }
+    if (rsq::textio::has_suffix(alleles_out, ".bz2")) {
+        ERR("--writeAlleles: bzip2 output is not supported (write .gz or plain FASTA)");
+        return 1;
+    }
     rsq_profile *prof = nullptr;
     rsq_ref *ref = nullptr;
     rsq_sim *sim = nullptr;
@@ -764,7 +857,7 @@ int illumina_pe(const Args &a) {
         if (ok && a.has("coverage")) ok = parse_double(a, "coverage", coverage);
         int rc = 1;
         if (ok) {
-            const PeJob job{a, prof, ref, seed, num_reads, coverage, ref_bias_mode, ref_bias_file, sys_read, sys_write, a.get("methylation", ""), out1, out2, a.get("recordBaseIdentifier", "ReseqRead")};
+            const PeJob job{a, prof, ref, seed, num_reads, coverage, ref_bias_mode, ref_bias_file, sys_read, sys_write, a.get("methylation", ""), out1, out2, a.get("recordBaseIdentifier", "ReseqRead"), alleles_out};
             rc = illumina_pe_on_workers(job, n_workers, n_devices);
         }
         rsq_ref_free(ref);
@@ -775,8 +868,10 @@ int illumina_pe(const Args &a) {
     if (ok && a.has("device")) ok = parse_u64(a, "device", device);
     ok = ok && check(rsq_sim_create(prof, ref, (int)device, &sim), "Could not set up the simulator");
     if (ok && a.has("truthVariants")) ok = check(rsq_sim_truth_variants(sim, 1), "--truthVariants");
+    if (ok && a.has("truthAlleles")) ok = check(rsq_sim_truth_alleles(sim, 1), "--truthAlleles");
     if (ok && a.has("truthMD")) ok = check(rsq_sim_truth_md(sim, 1), "--truthMD");
     trace.at("simulator created");
+    if (ok && !alleles_out.empty()) ok = write_alleles(sim, ref, (int)device, alleles_out);
     if (ok && !sys_write.empty()) {
         INFO("Writing systematic error profile to " << sys_write);
         ok = check(rsq_sim_create_sys_error_profile(sim, seed, sys_write.c_str(), nullptr), "Could not write systematic error profile");
@@ -1201,11 +1296,13 @@ const char *kUsage =
     "Usage:  reseq <command> [options]\n"
     "Commands:\n"
     "  illuminaPE\t\tsimulates illumina paired-end data from a fitted profile (-s) and a reference (-R)\n"
-    "                 \t--truthBam truth.bam: the same records as BAM (BGZF blocks made on the device; unsorted, no index; may be given beside --truthSam; with -V only with --truthVariants; not with --hostGzip, one worker)\n"
+    "                 \t--writeAlleles alleles.fa[.gz]: with -V, the sequences the reads are drawn from -- every allele of every sequence as a FASTA record <name>_allele<a>, written on the device before generation (plain: with its index alleles.fa.fai; .gz: BGZF blocks)\n"
+    "                 \t--truthAlleles: with -V, --truthSam / --truthBam write their records in ALLELE coordinates: against the sequences of --writeAlleles (RNAME <name>_allele<a>, the plain CIGAR, tag XI:i; not with --truthVariants, --truthMD, --truthBamSort)\n"
+    "                 \t--truthBam truth.bam: the same records as BAM (BGZF blocks made on the device; unsorted, no index; may be given beside --truthSam; with -V only with --truthVariants or --truthAlleles; not with --hostGzip, one worker)\n"
     "                 \t--truthBamSort: with --truthBam, the records sorted by coordinate on the device (@HD SO:coordinate) and the index truth.bam.bai beside the file\n"
     "                 \t--truthVariants: with -V, --truthSam / --truthBam [--truthBamSort] write their records in reference coordinates (inserted bases as I, deleted ones as D, tag XI:i)\n"
     "                 \t--truthMD: --truthSam / --truthBam [--truthBamSort] [--truthVariants] append NM:i and MD:Z to every mapped record (computed on the device against the reference as loaded, as samtools calmd would)\n"
-    "                 \t--truthSam truth.sam[.gz]: where every read really came from, as SAM records (header, two records per pair in the files' order; with -V only with --truthVariants; one worker)\n"
+    "                 \t--truthSam truth.sam[.gz]: where every read really came from, as SAM records (header, two records per pair in the files' order; with -V only with --truthVariants or --truthAlleles; one worker)\n"
     "  seqToIllumina\t\tapplies illumina quality and error model to input sequences (alias: replaceQuals)\n"
     "                 \t-i in.fa[.gz|.bz2] (stdin) -o out.fq[.gz|.bz2] (stdout) -s profile; --readThreads N, --traceStages;\n"
     "                 \t--inputFrom / --inputTo BYTE, --firstRecord K: a share of a plain input (python -m reseq_amd.simulate seqToIllumina works them out)\n"

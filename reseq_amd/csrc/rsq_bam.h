@@ -271,4 +271,31 @@ struct BamVarFormat {
     }
 };
 
+// ------------------------------------------------------------------------------------------------ ... in allele coordinates (rsq_sam.h SamAlleleFormat)
+// The same re-encoding of that record: refID = next_refID = seq * num_alleles + allele, the index of the allele's record in the alleles' FASTA text and in the
+// header of rsq_ref_bam_header_alleles; pos and the bin over allele positions; the CIGAR's words from the plain walk.  The entry is BamVarFormat's.
+struct BamAlleleFormat : BamVarFormat {
+    static constexpr bool kAlleles = true;
+    template <class Sink>
+    static RSQ_HD void head(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, const SamVarId &id, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &seq,
+                            const WordColumn &ops, const Mate &e, const SamAlign &a, Sink &t) {
+        Fragment in_allele = f;
+        in_allele.seq = f.seq * S.num_alleles + f.allele;
+        bam_fixed_span(in_allele, m, e.v.ref_bases, a, e.l_read_name, e.n_cigar, e.v.w.bytes - 4u, t);
+        sam_qname_at(S, names, has_f, f, id.end, id.allele != 0u, adapter_only_number, m, t);
+        t.ch(0);
+        bam_cigar(ops, m, e.v.w, a, t);
+        bam_seq(seq, m.read_len, a.reverse != 0u, t);
+    }
+    template <class P>
+    static RSQ_HD uint32_t record(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, const SamVarId &id, uint64_t adapter_only_number, const ReadMeta &m,
+                                  const WordColumn &seq, const WordColumn &qual, const WordColumn &ops, const Mate &e, const SamAlign &a, P dst) {
+        WordSinkT<P> t(dst);
+        head(S, names, has_f, f, id, adapter_only_number, m, seq, ops, e, a, t);
+        tail(S, m, id, qual, ops, a, t);
+        t.finish();
+        return t.n;
+    }
+};
+
 }  // namespace rsq

@@ -670,6 +670,87 @@ struct SamVarFormat {
     }
 };
 
+// ------------------------------------------------------------------------------------------------ a reference with variants, in ALLELE coordinates (rsq_sim_truth_alleles)
+// The record against the sequence the fragment was drawn from: allele a of its sequence, a record of the alleles' FASTA text (rsq_alleles.h).  There the fragment is
+// the stretch [hs, he) of the allele and the alignment is the PLAIN one of SamFormat with start := hs and end := he: no I or D comes from a variant, POS = hs + 1 +
+// dL (forward) or he - t + 1 + dL (reverse).  RNAME is "<name>_allele<a>" (always, as the text's records are named); QNAME and the tags are those of the record in
+// reference coordinates ("_allele<a>" when the id has it, XC, XE, XI:i -- XI ties the record to the id's reference positions).  hs is the allele coordinate of (start
+// position, start variant); he is where allele_template ends the reverse mate's template -- inside inserted bases behind end_var_pos of them, else in front of
+// whatever replaces the end position --, hs + len but for allele_cell's fragment inside one insertion.  One placement per pair (the bisection that finds hs; the
+// entries up to the end position are walked from there: they lie inside the fragment), kept in the side entry: the writer neither searches nor walks the map.
+// A format says so with kAlleles (formats without the member: AlleleCoordinates is false, and k_truth_sizes is the code it was).
+template <class Format, class = void>
+struct AlleleCoordinates {
+    static constexpr bool value = false;
+};
+template <class Format>
+struct AlleleCoordinates<Format, decltype((void)Format::kAlleles)> {
+    static constexpr bool value = Format::kAlleles;
+};
+struct AlleleSpan {
+    uint32_t hs, he;
+};
+RSQ_HD AlleleSpan sam_allele_span(const DevSim &S, bool has_f, const Fragment &f, bool has_fv, const FragmentVar &fv) {
+    if (!has_f || !f.len) return AlleleSpan{0u, 0u};
+    if (!has_fv) return AlleleSpan{f.start, f.start + f.len};           // allele copies: as long as the sequence
+    const AlleleView a = allele_view(S, f.seq, f.allele);
+    const uint32_t at = fv.start_var_pos ? a.r.v[fv.start_var].pos : f.start, end = fv.end_var_pos ? a.r.v[fv.end_var].pos : fv.end;
+    uint32_t j = a.entries_before(at);                                  // the pair's one bisection
+    const int64_t hs = (int64_t)at + a.e[j].shift + fv.start_var_pos;
+    while (j < a.n && a.e[j].pos < end) ++j;                            // entries_before(end)
+    return AlleleSpan{(uint32_t)hs, (uint32_t)((int64_t)end + a.e[j].shift + fv.end_var_pos)};
+}
+// a mate's entry: the plain walk (pad 0: sam_cigar writes the CIGAR), placed in the allele
+RSQ_HD SamVarMate sam_allele_walk(bool has_f, const Fragment &f, const AlleleSpan &span, uint32_t seg, const WordColumn &ops, const ReadMeta &m) {
+    SamVarMate e{};
+    e.w = sam_walk(ops, m);
+    if (!has_f || !f.len) return e;
+    const bool rev = seg != f.strand;
+    e.ref_bases = (uint32_t)e.w.t - e.w.lead - e.w.trail;
+    e.pos = (rev ? span.he - e.w.t : span.hs) + (rev ? e.w.trail : e.w.lead);
+    e.at = span.hs;
+    return e;
+}
+RSQ_HD uint32_t sam_allele_name_size(const Fragment &f, const SamAlign &a) { return a.mapped ? 7u + digits_u32(f.allele) : 0u; }
+struct SamAlleleFormat : SamVarFormat {
+    static constexpr bool kAlleles = true;
+    static RSQ_HD Mate mate(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, const SamVarId &id, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &ops,
+                            const SamVarMate &w, uint32_t n_cigar, const SamAlign &a) {
+        Mate e = SamVarFormat::mate(S, names, has_f, f, id, adapter_only_number, m, ops, w, n_cigar, a);
+        e.w.bytes += sam_allele_name_size(f, a);
+        return e;
+    }
+    template <class Sink>
+    static RSQ_HD void head(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, const SamVarId &id, uint64_t adapter_only_number, const ReadMeta &m, const WordColumn &seq,
+                            const WordColumn &ops, const Mate &e, const SamAlign &a, Sink &t) {
+        sam_qname_at(S, names, has_f, f, id.end, id.allele != 0u, adapter_only_number, m, t);
+        t.ch('\t');
+        t.num(a.flag);
+        t.ch('\t');
+        if (a.mapped) {
+            t.str(names.names + names.name_ptr[f.seq], names.name_ptr[f.seq + 1] - names.name_ptr[f.seq]);
+            t.str("_allele", 7);
+            t.num((uint32_t)f.allele);
+            t.ch('\t');
+            t.num(a.pos);
+            t.str("\t60\t", 4);
+            sam_cigar(ops, m, e.w, a.reverse != 0u, t);
+            sam_head_back(a, t);
+        } else t.str("*\t0\t0\t*\t*\t0\t0\t", 14);
+        sam_line(seq, m.read_len, false, a.reverse != 0u, S.phred_offset, t);
+        t.ch('\t');
+    }
+    template <class P>
+    static RSQ_HD uint32_t record(const DevSim &S, const NameTable &names, bool has_f, const Fragment &f, const SamVarId &id, uint64_t adapter_only_number, const ReadMeta &m,
+                                  const WordColumn &seq, const WordColumn &qual, const WordColumn &ops, const Mate &e, const SamAlign &a, P dst) {
+        WordSinkT<P> t(dst);
+        head(S, names, has_f, f, id, adapter_only_number, m, seq, ops, e, a, t);
+        tail(S, m, id, qual, ops, a, t);
+        t.finish();
+        return t.n;
+    }
+};
+
 #if RSQ_DEVICE_BUILD
 // One lane per raw row pair (row i of both segments: the two mates of pair perm[i], or of pair i): both mates' entries into side[row], the pair's bytes into
 // sizes[pair].  fvars: read by the formats of a reference with variants only (nullptr: allele copies)
@@ -691,6 +772,15 @@ __global__ void __launch_bounds__(256) k_truth_sizes(DevSim S, NameTable names, 
         FragmentVar fv{};
         if (has_fv) fv = fvars[pair];
         const SamVarId id = sam_var_id(S, f, has_fv, fv);
+        if constexpr (AlleleCoordinates<Format>::value) {               // (allele coordinates: the pair's one placement, two plain walks)
+            const AlleleSpan span = sam_allele_span(S, has_f, f, has_fv, fv);
+            const SamVarMate w0 = sam_allele_walk(has_f, f, span, 0u, ops0, m0), w1 = sam_allele_walk(has_f, f, span, 1u, ops1, m1);
+            p.mate[0] = Format::mate(S, names, has_f, f, id, ao_number, m0, ops0, w0, 0u, sam_var_align(has_f, f, 0u, w0, w1));
+            p.mate[1] = Format::mate(S, names, has_f, f, id, ao_number, m1, ops1, w1, 0u, sam_var_align(has_f, f, 1u, w0, w1));
+            side[row] = p;
+            sizes[pair] = Format::bytes(p.mate[0]) + Format::bytes(p.mate[1]);
+            return;
+        }
         uint32_t n0, n1;
         const SamVarMate w0 = sam_var_walk(S, has_f, f, has_fv, fv, 0u, ops0, m0, n0), w1 = sam_var_walk(S, has_f, f, has_fv, fv, 1u, ops1, m1, n1);
         if constexpr (Format::kMd) {                                    // (rsq_md.h: the entry also takes what comparing SEQ with the reference comes to)

@@ -32,6 +32,7 @@
 #include "rsq_bam.h"
 #include "rsq_md.h"
 #include "rsq_bamsort.h"
+#include "rsq_alleles.h"
 #include "rsq_pack.h"
 #include "rsq_prepass.h"
 #include "rsq_spec.h"
@@ -275,6 +276,7 @@ struct rsq_sim : PrepassSim {
     uint64_t sam_pair_bytes = 1100;          // that of the last call and a few bytes (sam_stage sizes the writer's LDS image with it)
     uint64_t bam_pair_bytes = 700;           // the same for a call that writes BAM records
     bool truth_variants = false;             // rsq_sim_truth_variants: truth alignments of a reference with variants, in reference coordinates (SamVarFormat, BamVarFormat)
+    bool truth_alleles = false;              // rsq_sim_truth_alleles: the same truth alignments in allele coordinates (SamAlleleFormat, BamAlleleFormat); never beside truth_variants
     bool truth_md = false;                   // rsq_sim_truth_md: NM:i and MD:Z behind every mapped truth record's tags (rsq_md.h: the four formats as MdFormat)
     // rsq_sim_bam_sorted_*: a run of calls whose BAM records leave in coordinate order (rsq_bamsort.h)
     struct BamSorted {
@@ -294,6 +296,12 @@ struct rsq_sim : PrepassSim {
         BamIndexState index;
     } bam_sorted;
     uint64_t record_text_bytes = 480;        // the same for the seqToIllumina records' text (error_model_text)
+    // rsq_sim_alleles_fasta (rsq_alleles.h): the records of the alleles' FASTA text, made at the first call (n == 0: not yet; a reference taken in later starts over)
+    struct AllelesText {
+        DevBuf records;
+        uint32_t n = 0;
+        uint64_t bytes = 0;
+    } alleles_text;
     int force_fill_mode = -1;      // RSQ_FILL_MODE=0: every draw in double precision from HBM (tests run both paths)
     // read kernels compiled for this simulator's profile (rsq_spec.h); `specialize`: option specialize when the simulator was created
     SpecKernels spec;
@@ -825,6 +833,7 @@ static void sam_stage(rsq_sim &s, const PairsCall &call, const Part &p, hipStrea
     using Stage = void (*)(rsq_sim &, const PairsCall &, const Part &, hipStream_t);
     static const Stage stage[2][2][2] = {{{truth_stage<SamFormat>, truth_stage<BamFormat>}, {truth_stage<SamVarFormat>, truth_stage<BamVarFormat>}},
                                          {{truth_stage<SamMdFormat>, truth_stage<BamMdFormat>}, {truth_stage<SamVarMdFormat>, truth_stage<BamVarMdFormat>}}};
+    if (s.truth_alleles) return (call.bam() ? truth_stage<BamAlleleFormat> : truth_stage<SamAlleleFormat>)(s, call, p, st);      // (never with truth_md: truth_refusal)
     stage[s.truth_md && p.frags][s.has_variants][call.bam()](s, call, p, st);
 }
 static void reset_call_timers(rsq_sim &s) {
@@ -1549,6 +1558,103 @@ int rsq_ref_bam_header_so(const rsq_ref *r, int coordinate, char *out, size_t ca
     return RSQ_OK;
 }
 
+// ---- the alleles of a reference with variants as sequences of their own (rsq_alleles.h): lengths, the FASTA text's size and index, the truth headers that name them
+// bases of every (sequence, allele): the sequence's, and per variant of the allele the bases of its replacement minus the one it replaces
+static std::vector<uint64_t> allele_lengths(const rsq_ref &r) {
+    const uint32_t na = r.variants.num_alleles;
+    std::vector<uint64_t> len(r.r.codes.size() * na);
+    for (size_t seq = 0; seq < r.r.codes.size(); ++seq) {
+        std::vector<int64_t> n(na, (int64_t)r.r.codes[seq].size());
+        for (const Variant &v : r.variants.by_seq[seq])
+            for (uint32_t w = 0; w < 2u; ++w)
+                for (uint64_t bits = v.allele[w]; bits; bits &= bits - 1u) {
+                    const uint32_t a = 64u * w + (uint32_t)__builtin_ctzll(bits);
+                    if (a < na) n[a] += (int64_t)v.var_seq.size() - 1;
+                }
+        for (uint32_t a = 0; a < na; ++a) len[seq * na + a] = (uint64_t)n[a];
+    }
+    return len;
+}
+static std::vector<std::string> first_parts(const rsq_ref &r) {
+    std::vector<std::string> names;
+    for (size_t seq = 0; seq < r.r.codes.size(); ++seq) names.push_back(r.r.first_part(seq));
+    return names;
+}
+static int put_text(const std::string &text, const char *what, char *out, size_t cap, size_t *need) {
+    *need = text.size();
+    if (!out || cap < text.size()) {
+        g_last_error = std::string(what) + " buffer too small: need " + std::to_string(text.size()) + " bytes";
+        return RSQ_ENOSPC;
+    }
+    memcpy(out, text.data(), text.size());
+    if (cap > text.size()) out[text.size()] = 0;
+    return RSQ_OK;
+}
+#define REQUIRE_VARIANTS(r) REQUIRE((r)->has_variants, "the reference has no variants (rsq_ref_read_variants): it has no alleles to write")
+int rsq_ref_allele_length(const rsq_ref *r, uint32_t seq, uint32_t allele, uint64_t *out) {
+    REQUIRE(r && out, "null argument");
+    REQUIRE_VARIANTS(r);
+    REQUIRE(seq < r->r.codes.size() && allele < r->variants.num_alleles, "no such sequence or allele");
+    int64_t n = (int64_t)r->r.codes[seq].size();
+    for (const Variant &v : r->variants.by_seq[seq])
+        if (v.in_allele(allele)) n += (int64_t)v.var_seq.size() - 1;
+    *out = (uint64_t)n;
+    return RSQ_OK;
+}
+int rsq_ref_alleles_fasta_size(const rsq_ref *r, uint64_t *bytes) {
+    REQUIRE(r && bytes, "null argument");
+    REQUIRE_VARIANTS(r);
+    *bytes = allele_records(first_parts(*r), r->variants.num_alleles, allele_lengths(*r)).back().at;
+    return RSQ_OK;
+}
+// samtools faidx's index of that text: NAME, LENGTH, OFFSET of the first base, bases per line, bytes per line
+int rsq_ref_alleles_fai(const rsq_ref *r, char *out, size_t cap, size_t *need) {
+    REQUIRE(r && need, "null argument");
+    REQUIRE_VARIANTS(r);
+    const std::vector<std::string> names = first_parts(*r);
+    const uint32_t na = r->variants.num_alleles;
+    const std::vector<AlleleRecord> rec = allele_records(names, na, allele_lengths(*r));
+    std::string text;
+    for (size_t m = 0; m + 1 < rec.size(); ++m)
+        text += names[m / na] + "_allele" + std::to_string(m % na) + "\t" + std::to_string(rec[m].length) + "\t" + std::to_string(rec[m].at + rec[m].header) + "\t" + std::to_string(kFastaLine) + "\t" +
+                std::to_string(kFastaLine + 1u) + "\n";
+    return put_text(text, "index", out, cap, need);
+}
+// the headers of truth alignments in allele coordinates: the sequences are the records of that text, in its order
+static int alleles_header(const rsq_ref *r, bool bam, char *out, size_t cap, size_t *need) {
+    REQUIRE(r && need, "null argument");
+    REQUIRE_VARIANTS(r);
+    const std::vector<std::string> names = first_parts(*r);
+    const uint32_t na = r->variants.num_alleles;
+    const std::vector<uint64_t> len = allele_lengths(*r);
+    std::string text = "@HD\tVN:1.6\tSO:unsorted\tGO:query\n", entries;
+    auto put32 = [](std::string &h, uint32_t v) {
+        for (int k = 0; k < 4; ++k) h += (char)((v >> (8 * k)) & 0xFFu);
+    };
+    for (size_t m = 0; m < len.size(); ++m) {
+        const std::string name = names[m / na] + "_allele" + std::to_string(m % na);
+        if (!len[m]) {
+            g_last_error = "allele " + name + " has no bases: a header cannot list a sequence of length 0";
+            return RSQ_EINVAL;
+        }
+        text += "@SQ\tSN:" + name + "\tLN:" + std::to_string(len[m]) + "\n";
+        put32(entries, (uint32_t)name.size() + 1u);
+        entries += name;
+        entries += '\0';
+        put32(entries, (uint32_t)len[m]);
+    }
+    text += "@PG\tID:reseq_amd\tPN:reseq_amd\n";
+    if (!bam) return put_text(text, "header", out, cap, need);
+    std::string h = "BAM\1";
+    put32(h, (uint32_t)text.size());
+    h += text;
+    put32(h, (uint32_t)len.size());
+    h += entries;
+    return put_text(h, "header", out, cap, need);
+}
+int rsq_ref_sam_header_alleles(const rsq_ref *r, char *out, size_t cap, size_t *need) { return alleles_header(r, false, out, cap, need); }
+int rsq_ref_bam_header_alleles(const rsq_ref *r, char *out, size_t cap, size_t *need) { return alleles_header(r, true, out, cap, need); }
+
 int rsq_ref_load_fasta(const char *path, rsq_ref **out) {
     REQUIRE(path && out, "null argument");
     try {
@@ -1828,6 +1934,49 @@ int rsq_sim_reference_sequence(rsq_sim *s, uint32_t seq, uint32_t start_pos, uin
         return RSQ_OK;
     });
 }
+// bases of every (sequence, allele) of a simulator with variants: the sequence's length and the total shift of the allele's map (its sentinel)
+static std::vector<int64_t> sim_allele_lengths(const rsq_sim &s) {
+    std::vector<int64_t> length(s.seq_len.size() * s.num_alleles);
+    for (size_t m = 0; m < length.size(); ++m) length[m] = (int64_t)s.seq_len[m / s.num_alleles] + s.allele_map[s.allele_map_ptr[m + 1] - 1u].shift;
+    return length;
+}
+// Bytes [at, at + bytes) of the alleles' FASTA text (rsq_alleles.h) into device memory: one launch, whatever the piece and the destination's alignment
+int rsq_sim_alleles_fasta(rsq_sim *s, uint64_t at, size_t bytes, char *dst_dev, void *stream) {
+    REQUIRE(s && (dst_dev || !bytes), "null argument");
+    REQUIRE(s->has_ref && s->has_variants, "rsq_sim_alleles_fasta needs a reference with variants (rsq_ref_read_variants): there are no alleles to write");
+    return guard([&] {
+        HIP_CHECK(hipSetDevice(s->device));
+        hipStream_t st = (hipStream_t)stream;
+        rsq_sim::AllelesText &text = s->alleles_text;
+        if (!text.n) {
+            const uint32_t na = s->num_alleles;
+            const std::vector<int64_t> bases = sim_allele_lengths(*s);
+            std::vector<uint64_t> length(bases.size());
+            for (size_t m = 0; m < bases.size(); ++m) {
+                if (bases[m] < 0 || bases[m] > 0xFFFFFFFFll) throw Error("rsq_sim_alleles_fasta: an allele of " + s->ref_first_names[m / na] + " has more than 2^32 bases");
+                length[m] = (uint64_t)bases[m];
+            }
+            const std::vector<AlleleRecord> records = allele_records(s->ref_first_names, na, length);
+            text.records.upload(records);
+            text.bytes = records.back().at;
+            text.n = (uint32_t)records.size() - 1u;
+        }
+        if (at > text.bytes || bytes > text.bytes - at)
+            throw Error("rsq_sim_alleles_fasta: bytes " + std::to_string(at) + " to " + std::to_string(at + bytes) + " were asked for, the text has " + std::to_string(text.bytes));
+        reset_call_timers(*s);
+        if (!bytes) return RSQ_OK;
+        const uint32_t lead = (uint32_t)(reinterpret_cast<uintptr_t>(dst_dev) & 15u);
+        const uint64_t tiles = (lead + (uint64_t)bytes + kTileBytes - 1u) / kTileBytes;
+        if (tiles > 0x7FFFFFFFull) throw Error("rsq_sim_alleles_fasta: at most 2^45 bytes per call");
+        Timer &timer = s->timers["alleles_fasta"];
+        timer.start(st);
+        hipLaunchKernelGGL(k_alleles_fasta, dim3((uint32_t)tiles), dim3(kTileLanes), 0, st, s->dev, s->names, text.records.as<AlleleRecord>(), text.n, at, (uint64_t)bytes, lead, dst_dev);
+        timer.stop(st);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(st));
+        return RSQ_OK;
+    });
+}
 int rsq_sim_export_reference(rsq_sim *s, const char *path) {
     REQUIRE(s && path, "null argument");
     return guard([&] {
@@ -1844,6 +1993,7 @@ int rsq_sim_import_reference(rsq_sim *s, const char *path) {
         MappedFile m(path);
         s->sieve_tracks.drop();
         import_reference(*s, s->up, m.data, m.size, path);
+        s->alleles_text.n = 0;
         return RSQ_OK;
     });
 }
@@ -2017,15 +2167,33 @@ int rsq_sim_get_adapter_sys_errors(const rsq_sim *s, int seg, uint32_t adapter, 
 // (rsq_sim_truth_variants: reference coordinates, rsq_sam.h SamVarFormat).  What BAM cannot hold is refused as well, before anything is launched: l_read_name is a byte, so no QNAME may exceed 254 characters (the base
 // identifier, the longest reference name, every number at its widest), and the bins cover 2^29 bases.
 static bool truth_refusal(const rsq_sim &s, bool bam) {
-    if (s.has_variants && !s.truth_variants) {
+    if (s.has_variants && !s.truth_variants && !s.truth_alleles) {
         g_last_error = std::string("truth alignments (") + (bam ? "BAM" : "SAM") + ") are not available for a reference with variants (rsq_ref_read_variants)";
         return true;
     }
-    if (!bam) return false;
     size_t longest_name = 0;
     uint32_t longest_seq = 0;
     for (const std::string &n : s.ref_first_names) longest_name = std::max(longest_name, n.size());
     for (const uint32_t l : s.seq_len) longest_seq = std::max(longest_seq, l);
+    if (s.truth_alleles) {                                           // the records' sequences are the alleles
+        if (s.truth_md) {
+            g_last_error = "truth alignments in allele coordinates (rsq_sim_truth_alleles) do not carry NM:i and MD:Z: switch rsq_sim_truth_md off";
+            return true;
+        }
+        const std::vector<int64_t> length = sim_allele_lengths(s);
+        for (size_t m = 0; m < length.size(); ++m) {
+            const std::string name = s.ref_first_names[m / s.num_alleles] + "_allele" + std::to_string(m % s.num_alleles);
+            if (length[m] <= 0) {
+                g_last_error = "truth alignments in allele coordinates (rsq_sim_truth_alleles): " + name + " has no bases";
+                return true;
+            }
+            if (bam && length[m] > (int64_t)kBamMaxRefLen) {
+                g_last_error = "truth alignments (BAM) in allele coordinates (rsq_sim_truth_alleles): " + name + " has " + std::to_string(length[m]) + " bases, more than the 2^29 that BAM's bins cover";
+                return true;
+            }
+        }
+    }
+    if (!bam) return false;
     if (longest_seq > kBamMaxRefLen) {
         g_last_error = "truth alignments (BAM): a reference sequence of " + std::to_string(longest_seq) + " bases is longer than the 2^29 that BAM's bins cover";
         return true;
@@ -2043,7 +2211,23 @@ static bool truth_refusal(const rsq_sim &s, bool bam) {
 }
 int rsq_sim_truth_variants(rsq_sim *s, int on) {
     REQUIRE(s, "null argument");
+    REQUIRE(!on || !s->truth_alleles, "rsq_sim_truth_variants: rsq_sim_truth_alleles has chosen allele coordinates for the truth alignments; a record has one coordinate system (switch that off first)");
     s->truth_variants = on != 0;
+    return RSQ_OK;
+}
+int rsq_sim_truth_alleles(rsq_sim *s, int on) {
+    REQUIRE(s, "null argument");
+    if (!on) {
+        s->truth_alleles = false;
+        return RSQ_OK;
+    }
+    REQUIRE(!s->truth_variants, "rsq_sim_truth_alleles: rsq_sim_truth_variants has chosen reference coordinates for the truth alignments; a record has one coordinate system (switch that off first)");
+    REQUIRE(s->has_ref && s->has_variants, "rsq_sim_truth_alleles needs a reference with variants (rsq_ref_read_variants): without them there are no alleles");
+    if (s->bam_sorted.open) {
+        g_last_error = "rsq_sim_truth_alleles cannot change inside a sorted run (between rsq_sim_bam_sorted_begin and rsq_sim_bam_sorted_flush)";
+        return RSQ_ESTATE;
+    }
+    s->truth_alleles = true;
     return RSQ_OK;
 }
 // NM:i and MD:Z behind every mapped truth record's tags (rsq_md.h).  The writer's image is sized by the longest pair of the call before: the first call with the
@@ -2089,6 +2273,8 @@ int rsq_sim_bam_sorted_begin(rsq_sim *s, uint64_t first_record_offset) {
         g_last_error = "rsq_sim_prepare with a reference must run before rsq_sim_bam_sorted_begin";
         return RSQ_ESTATE;
     }
+    REQUIRE(!s->truth_alleles, "rsq_sim_bam_sorted_begin: a sorted run is not available in allele coordinates (rsq_sim_truth_alleles): the records of one sequence's alleles arrive "
+                               "interleaved, so no record could be handed out before the sequence ends");
     if (truth_refusal(*s, true)) return RSQ_EINVAL;
     return guard([&] {
         HIP_CHECK(hipSetDevice(s->device));

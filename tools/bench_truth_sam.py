@@ -15,7 +15,12 @@ pairs/s, kernel ms of bam_sort_keys / bam_sort / bam_gather / bam_index beside b
 --variants: everything above twice in one run, on the same reference -- "without_variants" as ever, and "with_variants": a synthetic phased VCF at the human-sized
 configuration's density (workloads.human_sized: 4.4 variants per 3100 bases, one in eleven an insertion or a deletion of at most 20 bases, two alleles) with
 rsq_sim_truth_variants set -- and "variants_over_plain", the ratios of the truth kernels' times.  The simulators differ in more than the truth kernels (the sieve
-and the read kernel walk the alleles), so the ratios to read are those of sam_sizes / sam_write / bam_sizes / bam_write."""
+and the read kernel walk the alleles), so the ratios to read are those of sam_sizes / sam_write / bam_sizes / bam_write.
+
+--variants --alleles: in the "with_variants" half also "in_allele_coordinates" -- the SAM call (with --bam: and the BAM call) of the SAME simulator with
+rsq_sim_truth_alleles in place of rsq_sim_truth_variants: pairs/s, kernel ms of the sizes and the write kernel, bytes per pair, to be read beside the half's own
+reference-coordinate figures and the plain calls of "without_variants" -- and "alleles_fasta": the bytes of the alleles' FASTA text of that reference
+(rsq_sim_alleles_fasta, the whole text in one call), the kernel's ms (the median of the steps) and GB/s of text written."""
 import json
 import os
 import sys
@@ -29,8 +34,10 @@ sys.path.insert(0, ROOT)
 from reseq_amd import api, synth, workloads  # noqa: E402
 
 with_bam, with_sorted, with_variants, with_md = "--bam" in sys.argv, "--sorted" in sys.argv, "--variants" in sys.argv, "--md" in sys.argv
+with_alleles = "--alleles" in sys.argv
 assert with_bam or not with_sorted, "--sorted goes with --bam"
-argv = [a for a in sys.argv[1:] if a not in ("--bam", "--sorted", "--variants", "--md")]
+assert with_variants or not with_alleles, "--alleles goes with --variants"
+argv = [a for a in sys.argv[1:] if a not in ("--bam", "--sorted", "--variants", "--md", "--alleles")]
 pairs = int(argv[0]) if len(argv) > 0 else 10_000_000
 steps = int(argv[1]) if len(argv) > 1 else 3
 tmp = tempfile.mkdtemp(prefix="rsq_sam_")
@@ -148,6 +155,44 @@ def measure(vcf):
             })
         packed.free()
         bam.free()
+    alleles_part = {}
+    if vcf and with_alleles:
+        if with_sorted:                                                    # the switch does not change inside a sorted run: hand out what the last one holds
+            held = api.DeviceArray(0, sim.bam_sorted_flush_device(None)[0] + 4096)
+            assert sim.bam_sorted_flush_device(held)[3] == api.RSQ_OK
+            held.free()
+        sim.truth_variants(False)
+        sim.truth_alleles(True)
+        _, _, _, ls_al, rc = sim.pairs_sam_device(lo, hi, None, None, None)
+        assert rc == api.RSQ_ENOSPC, rc
+        sam_al = api.DeviceArray(0, ls_al + 4096)
+        al_s = timed(lambda: sim.pairs_sam_device(lo, hi, r1, r2, sam_al))
+        in_alleles = {"pairs_per_s_sam": round(n / al_s), "ms_per_call_sam": round(al_s * 1e3, 2), "kernels_of_a_sam_call": kernels(("sam_sizes", "sam_write")),
+                      "bytes_per_pair": {"sam": round(ls_al / n, 1)}}
+        in_alleles["GB_per_s_sam_write"] = gbps(ls_al, in_alleles["kernels_of_a_sam_call"]["sam_write"]["ms"])
+        sam_al.free()
+        if with_bam:
+            _, _, _, lb_al, rc = sim.pairs_bam_device(lo, hi, None, None, None)
+            assert rc == api.RSQ_ENOSPC, rc
+            bam_al = api.DeviceArray(0, lb_al + 4096)
+            al_s = timed(lambda: sim.pairs_bam_device(lo, hi, r1, r2, bam_al))
+            in_alleles.update({"pairs_per_s_bam": round(n / al_s), "ms_per_call_bam": round(al_s * 1e3, 2), "kernels_of_a_bam_call": kernels(("bam_sizes", "bam_write"))})
+            in_alleles["bytes_per_pair"]["bam"] = round(lb_al / n, 1)
+            in_alleles["GB_per_s_bam_write"] = gbps(lb_al, in_alleles["kernels_of_a_bam_call"]["bam_write"]["ms"])
+            bam_al.free()
+        sim.truth_alleles(False)
+        sim.truth_variants(True)
+        text_bytes = ref.alleles_fasta_size()
+        text = api.DeviceArray(0, text_bytes + 16)
+        fasta_ms = []
+        for _ in range(steps + 2):                                         # (the first call uploads the records' table)
+            assert sim.alleles_fasta_device(0, text_bytes, text) == api.RSQ_OK
+            fasta_ms.append(sim.last_kernel_ms("alleles_fasta"))
+        text.free()
+        fasta_ms = sorted(fasta_ms[2:])
+        alleles_part = {"in_allele_coordinates": in_alleles,
+                        "alleles_fasta": {"bytes": text_bytes, "ms": round(fasta_ms[len(fasta_ms) // 2], 4), "ms_of_every_step": [round(x, 4) for x in fasta_ms],
+                                          "GB_per_s": gbps(text_bytes, fasta_ms[len(fasta_ms) // 2])}}
     md_part = {}
     if with_md:
         if with_sorted:                                                    # the switch does not change inside a sorted run: hand out what the last one holds
@@ -188,6 +233,7 @@ def measure(vcf):
         "bytes": {"fastq1": l1, "fastq2": l2, "sam": ls},
         "GB_per_s": {"format_write": gbps(l1 + l2, sam_kernels["format_write"]["ms"]), "sam_write": gbps(ls, sam_kernels["sam_write"]["ms"])},
         **bam_part,
+        **alleles_part,
     }
     if with_md:
         result["with_md"] = md_part
