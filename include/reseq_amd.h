@@ -462,6 +462,41 @@ int rsq_sim_truth_alleles(rsq_sim *s, int on);
  * block_size covers them. */
 int rsq_sim_truth_md(rsq_sim *s, int on);
 
+/* Truth depth: the per-base coverage of the simulated reads, accumulated on the device while the pairs are simulated (reseq_amd/csrc/rsq_depth.h), and its bedGraph
+ * text.  The rule, in every mode: depth[seq][p] = the number of MAPPED truth records -- the records rsq_sim_pairs_sam writes for the same pairs, with variants the
+ * reference-coordinate ones of rsq_sim_truth_variants -- whose CIGAR has an M column on reference position p of sequence seq.  Both mates of a pair count, overlapping
+ * mates add; D, I, S and the D runs dropped at either end do not count (the default of `samtools depth`); with variants M on an inserted allele base is I and the
+ * positions an allele deleted are D, so neither counts, and a mate wholly inside an insertion adds nothing; unmapped records (fragment length 0, adapter-only calls)
+ * add nothing; methylation changes nothing.  Depth is a uint32; the sums are integers, so the result does not depend on how blocks are cut into calls, nor on options
+ * overlap and image_tiles.
+ *   rsq_sim_depth_begin opens a run: one zeroed device array of 4 bytes per reference base and 4 per sequence.  After rsq_sim_prepare with a reference, else
+ * RSQ_ESTATE; RSQ_ESTATE while a run is open; RSQ_EINVAL while rsq_sim_truth_alleles is on (depth is in reference coordinates only; rsq_sim_truth_alleles(s, 1)
+ * returns RSQ_ESTATE while a run is open).  rsq_sim_truth_variants is not needed: its switch only authorises the truth calls.
+ *   While a run is open, rsq_sim_pairs, rsq_sim_pairs_sam, rsq_sim_pairs_bam and rsq_sim_pairs_bam_sorted add their pairs to it if and only if they return RSQ_OK
+ * (the sorted call: once its records have been handed out): a call repeated after RSQ_ENOSPC counts its pairs once.  Which of the four is called does not matter,
+ * and the texts they write are what they write without a run.  Such a call runs as one part whatever option overlap says (a measurement option: results never
+ * depend on it).  The adapter-only calls add nothing.  rsq_sim_job_generate, rsq_sim_job_write, rsq_sim_job_compress and rsq_sim_job_read return RSQ_ESTATE while
+ * a run is open.
+ *   rsq_sim_depth_finish turns the array into depths (a prefix sum in place).  Afterwards the pairs calls return RSQ_ESTATE until rsq_sim_depth_end.  RSQ_EINVAL if
+ * an alignment lay outside its sequence (the records' rules exclude it).
+ *   rsq_sim_depth_counts (after finish, else RSQ_ESTATE): the depths of positions [lo, hi) of sequence seq into depth_dev, any window in any order; RSQ_EINVAL for
+ * a window that is not inside the sequence.
+ *   rsq_sim_depth_bedgraph (after finish): bedGraph text, lines "<name>\t<start>\t<end>\t<depth>\n", 0-based and half-open, <name> the RNAME of rsq_ref_sam_header,
+ * one line per maximal run of equal depth, zero-depth runs included (`bedtools genomecov -bga`), no track line: the lines of a sequence tile [0, length).  The text
+ * of a sequence is fetched in pieces [lo, hi) that are contiguous and rise from 0.  A piece holds the lines of the runs that END in (lo, hi] -- a run ends at b when
+ * b is the sequence's length or depth[b] != depth[b - 1] --; a run still open at hi is written whole by the piece it ends in (the simulator carries its start), so
+ * the concatenated text does not depend on how the sequence is cut.  *len = the piece's bytes, *n_lines its lines.  RSQ_ENOSPC (cap < *len, or dst_dev NULL):
+ * nothing is written and the carried start is unchanged, the call can be repeated.  A piece with lo != 0 that does not continue the piece before it of the same
+ * sequence: RSQ_ESTATE; lo == 0 always restarts.
+ *   rsq_sim_depth_end frees the run's memory (RSQ_OK without a run as well); a new run may begin.
+ * Kernel times: "depth_add" (the pairs calls), "depth_scan" (finish), "depth_lines" and "depth_text" (bedgraph).  With no run open no call launches any of them,
+ * and every other call is, launch for launch and byte for byte, what it is without these entry points. */
+int rsq_sim_depth_begin(rsq_sim *s);
+int rsq_sim_depth_finish(rsq_sim *s, void *stream);
+int rsq_sim_depth_counts(rsq_sim *s, uint32_t seq, uint64_t lo, uint64_t hi, uint32_t *depth_dev, void *stream);
+int rsq_sim_depth_bedgraph(rsq_sim *s, uint32_t seq, uint64_t lo, uint64_t hi, char *dst_dev, size_t cap, size_t *len, uint64_t *n_lines, void *stream);
+int rsq_sim_depth_end(rsq_sim *s);
+
 /* Simulator::ApplyErrorsAndQualityToFastaInput with the FASTA header already parsed (reseq/Simulator.cpp:2403-2512):
  * n records of `read_len` template bases each.  Inputs (device): seqs[n][read_len] base codes 0..3, seg[n] template
  * segment 0/1, frag_len[n], dom[n][read_len] dominant-error base codes 0..4, rate[n][read_len] error percent.

@@ -117,6 +117,11 @@ SYMBOLS = {
     "rsq_sim_truth_variants": (C.c_int, [_vp, C.c_int]),
     "rsq_sim_truth_alleles": (C.c_int, [_vp, C.c_int]),
     "rsq_sim_truth_md": (C.c_int, [_vp, C.c_int]),
+    "rsq_sim_depth_begin": (C.c_int, [_vp]),
+    "rsq_sim_depth_finish": (C.c_int, [_vp, _vp]),
+    "rsq_sim_depth_counts": (C.c_int, [_vp, _u32, _u64, _u64, _vp, _vp]),
+    "rsq_sim_depth_bedgraph": (C.c_int, [_vp, _u32, _u64, _u64, _vp, _sz, _psz, C.POINTER(_u64), _vp]),
+    "rsq_sim_depth_end": (C.c_int, [_vp]),
     "rsq_sim_bam_sorted_begin": (C.c_int, [_vp, _u64]),
     "rsq_sim_pairs_bam_sorted": (C.c_int, [_vp, _u32, _u32, _vp, _sz, _psz, _vp, _sz, _psz, _vp, _sz, _psz, C.POINTER(_u64), C.POINTER(_u64), _vp, _sz, _vp]),
     "rsq_sim_bam_sorted_flush": (C.c_int, [_vp, _vp, _sz, _psz, C.POINTER(_u64), C.POINTER(_u64), _vp]),
@@ -662,6 +667,61 @@ class Simulator:
     def truth_variants(self, on=True):
         """rsq_sim_truth_variants: the truth calls accept a reference with variants and write their records in reference coordinates (with the XI:i tag)"""
         _check(lib().rsq_sim_truth_variants(self.h, 1 if on else 0))
+
+    def depth_begin(self):
+        """rsq_sim_depth_begin: opens a depth run; every pairs call that returns RSQ_OK adds the M columns of its mapped truth records to it"""
+        _check(lib().rsq_sim_depth_begin(self.h))
+
+    def depth_finish(self, stream=None):
+        """rsq_sim_depth_finish: the run's differences become depths; depth() and depth_bedgraph() read them, the pairs calls are refused until depth_end()"""
+        _check(lib().rsq_sim_depth_finish(self.h, stream))
+
+    def depth_end(self):
+        """rsq_sim_depth_end: frees the run's memory; a new run may begin"""
+        _check(lib().rsq_sim_depth_end(self.h))
+
+    def depth_counts_device(self, seq, lo, hi, depth_dev, stream=None):
+        """rsq_sim_depth_counts: the depths of [lo, hi) of sequence seq to depth_dev, a DeviceArray or an address in device memory; returns the return code"""
+        return lib().rsq_sim_depth_counts(self.h, seq, lo, hi, depth_dev.ptr if isinstance(depth_dev, DeviceArray) else depth_dev, stream)
+
+    def depth(self, seq, lo=0, hi=None):
+        """the depths of positions [lo, hi) of sequence seq (hi None: up to its end) as a numpy uint32 array"""
+        hi = self.sequence_lengths()[seq] if hi is None else hi
+        dst = DeviceArray(self.device, max(4 * (hi - lo), 8))
+        try:
+            _check(self.depth_counts_device(seq, lo, hi, dst))
+            return dst.to_numpy(np.uint32, max(hi - lo, 0))
+        finally:
+            dst.free()
+
+    def depth_bedgraph_device(self, seq, lo, hi, dst, stream=None):
+        """rsq_sim_depth_bedgraph into a caller-owned DeviceArray (None: only the sizes): the lines of the runs of equal depth of sequence seq that end in (lo, hi].
+        Returns (len, n_lines, rc)."""
+        n, lines = C.c_size_t(), C.c_uint64()
+        rc = lib().rsq_sim_depth_bedgraph(self.h, seq, lo, hi, dst.ptr if dst else None, dst.nbytes if dst else 0, C.byref(n), C.byref(lines), stream)
+        return n.value, lines.value, rc
+
+    def depth_bedgraph(self, piece=1 << 22, seqs=None):
+        """the bedGraph text of the whole reference (seqs: of these sequences) as bytes, fetched in pieces of `piece` positions"""
+        lengths = self.sequence_lengths()
+        out, dst = [], None
+        try:
+            for seq in (range(len(lengths)) if seqs is None else seqs):
+                for lo in range(0, max(int(lengths[seq]), 1), piece):
+                    hi = min(lo + piece, int(lengths[seq]))
+                    n, _, rc = self.depth_bedgraph_device(seq, lo, hi, dst)
+                    if rc == RSQ_ENOSPC:                            # (nothing was written and the carried start is unchanged: the same piece again, with room)
+                        if dst is not None:
+                            dst.free()
+                        dst = DeviceArray(self.device, n + n // 4 + 64)
+                        n, _, rc = self.depth_bedgraph_device(seq, lo, hi, dst)
+                    _check(rc)
+                    if n:
+                        out.append(dst.to_numpy(np.uint8, n).tobytes())
+            return b"".join(out)
+        finally:
+            if dst is not None:
+                dst.free()
 
     def pairs_sam_device(self, block_lo, block_hi, r1, r2, sam, frags=None, stream=None):
         """rsq_sim_pairs_sam into caller-owned DeviceArrays (None: only the sizes).  Returns (n_pairs, len1, len2, sam_len, rc)."""

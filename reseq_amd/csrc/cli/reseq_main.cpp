@@ -454,6 +454,59 @@ bool write_alleles(rsq_sim *sim, const rsq_ref *ref, int device, const std::stri
     return ok;
 }
 
+// --truthDepth depth.bedgraph[.gz]: the per-base coverage of the simulated reads (rsq_sim_depth_*) as bedGraph text, fetched from the device after the last batch in
+// pieces of a bounded number of positions; .gz: every piece's text as gzip members made on the device, the file ended by the end-of-file member.  A failure leaves
+// no file.
+bool write_depth(rsq_sim *sim, const rsq_ref *ref, int device, const std::string &path) {
+    constexpr uint64_t kPiece = 4ull << 20;                      // positions: at most a line each
+    const bool gz = rsq::textio::has_suffix(path, ".gz");
+    INFO("Writing the truth depth to " << path);
+    uint64_t at_file = 0;
+    uint32_t n_seqs = 0;
+    bool ok = check(rsq_sim_depth_finish(sim, nullptr), "--truthDepth") && check(rsq_ref_num_sequences(ref, &n_seqs), "--truthDepth");
+    if (ok) {
+        const int fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (fd < 0) {
+            ERR("Could not open '" << path << "' for writing.");
+            return false;
+        }
+        ::close(fd);
+    }
+    DevBuffer text, packed;
+    text.device = packed.device = device;
+    for (uint32_t seq = 0; ok && seq < n_seqs; ++seq) {
+        uint32_t length = 0;
+        ok = check(rsq_ref_sequence_length(ref, seq, &length), "--truthDepth");
+        for (uint64_t lo = 0; ok && lo < length; lo += kPiece) {
+            const uint64_t hi = std::min<uint64_t>(length, lo + kPiece);
+            size_t n = 0;
+            uint64_t lines = 0;
+            int rc = rsq_sim_depth_bedgraph(sim, seq, lo, hi, (char *)text.p, text.cap, &n, &lines, nullptr);
+            if (rc == RSQ_ENOSPC && text.ensure(n + n / 8 + 4096)) rc = rsq_sim_depth_bedgraph(sim, seq, lo, hi, (char *)text.p, text.cap, &n, &lines, nullptr);
+            ok = check(rc, "--truthDepth");
+            if (!ok || !n) continue;
+            const void *src = text.p;
+            if (gz) {
+                ok = packed.ensure(rsq_gzip_bound(n)) && check(rsq_sim_gzip_device(sim, (const char *)text.p, n, (char *)packed.p, packed.cap, &n, nullptr), "Compressing the truth depth failed");
+                src = packed.p;
+            }
+            ok = ok && check(rsq_dev_pwrite(device, src, n, path.c_str(), at_file), "Writing the truth depth failed");
+            at_file += n;
+        }
+    }
+    if (ok && gz) {
+        char eof[32];
+        const size_t n = rsq_gzip_eof_member(eof, sizeof eof);
+        const int fd = ::open(path.c_str(), O_WRONLY);
+        ok = fd >= 0 && pwrite(fd, eof, n, (off_t)at_file) == (ssize_t)n;
+        if (fd >= 0) ::close(fd);
+        if (!ok) ERR("Writing the truth depth failed");
+    }
+    rsq_sim_depth_end(sim);
+    if (!ok) remove(path.c_str());
+    return ok;
+}
+
 // illuminaPE on several devices inside one process (Simulator::Simulate starts its own worker threads, Simulator.cpp:2830-2836, and hands them blocks, :2384-2401).
 // N host threads, one simulator each on device (worker % devices): every worker prepares, simulates its contiguous share of the blocks with the text kept in device
 // memory (rsq_sim_job_generate), the exclusive scan of the workers' text sizes gives every worker its place in the two files, and all workers write at once
@@ -783,6 +836,31 @@ int illumina_pe(const Args &a) {
         ERR("--truthMD adds the tags NM:i and MD:Z to the records of --truthSam / --truthBam: give one of them as well");
         return 1;
     }
+    // --truthDepth: the coverage of the same records as bedGraph (rsq_sim_depth_*)
+    const std::string depth_out = a.get("truthDepth", "");
+    if (a.has("truthDepth")) {
+        if (depth_out.empty()) {
+            ERR("--truthDepth needs a file name");
+            return 1;
+        }
+        if (rsq::textio::has_suffix(depth_out, ".bz2")) {
+            ERR("--truthDepth: bzip2 output is not supported (write .gz or plain bedGraph)");
+            return 1;
+        }
+        if (a.has("truthAlleles")) {
+            ERR("--truthDepth: depth is in reference coordinates; it is not offered beside --truthAlleles");
+            return 1;
+        }
+        if (truths.size() == 2) {
+            ERR("--truthDepth: a batch is simulated once for each of --truthSam and --truthBam and would be counted twice; give at most one of them beside --truthDepth");
+            return 1;
+        }
+        for (const TruthOut &t : truths)
+            if (t.path == depth_out) {
+                ERR("--truthDepth and " << t.option << " name the same file");
+                return 1;
+            }
+    }
     const char *truth_option = any_truth ? truths.front().option : "";
     const std::string alleles_out = a.get("writeAlleles", "");
     if (a.has("writeAlleles") && alleles_out.empty()) {
@@ -827,6 +905,15 @@ int illumina_pe(const Args &a) {
             ok = false;
         }
         if (ok) n_workers = a.has("gpus") ? (int)asked : (int)std::min<uint64_t>(std::max<uint64_t>(asked, 1), (uint64_t)n_devices);
+        if (ok && n_workers > 1 && !any_truth && !depth_out.empty()) {
+            if (a.has("gpus")) {
+                ERR("--truthDepth: the truth depth is accumulated by one worker only (run without --gpus, or with --gpus 1)");
+                ok = false;
+            } else {
+                WARN("-j: the truth depth (--truthDepth) is accumulated by one worker only; one worker runs");
+                n_workers = 1;
+            }
+        }
         if (ok && n_workers > 1 && any_truth) {
             if (a.has("gpus")) {
                 ERR(truth_option << ": truth alignments are written by one worker only (run without --gpus, or with --gpus 1)");
@@ -902,6 +989,7 @@ int illumina_pe(const Args &a) {
         ok = check(rsq_sim_prepare(sim, seed, num_reads, coverage, ref_bias_mode, a.get("recordBaseIdentifier", "ReseqRead").c_str(), nullptr), "Preparation failed");
     }
     if (ok && !sys_read.empty()) ok = check(rsq_sim_read_sys_errors(sim, sys_read.c_str()), "Could not read systematic error profile");
+    if (ok && !depth_out.empty()) ok = check(rsq_sim_depth_begin(sim), "--truthDepth");      // every batch's pairs count once, whichever call simulates them
     trace.at("prepared");
     AsyncOut f1, f2;
     // .gz outputs: the text of every call becomes gzip members on the device (rsq_sim_gzip_device) -- a third of the bytes cross the link and the writer threads
@@ -909,7 +997,7 @@ int illumina_pe(const Args &a) {
     int64_t host_gzip = 0;
     rsq_get_option("host_gzip", &host_gzip);
     const bool gz1 = !host_gzip && rsq::textio::has_suffix(out1, ".gz"), gz2 = !host_gzip && rsq::textio::has_suffix(out2, ".gz");
-    bool truth_gz = false;
+    bool truth_gz = rsq::textio::has_suffix(depth_out, ".gz");     // (text of another kind than FASTQ: no Huffman code is kept over the calls)
     for (TruthOut &t : truths) {
         t.gz = t.bam || (!host_gzip && rsq::textio::has_suffix(t.path, ".gz"));
         t.text.device = t.packed.device = (int)device;
@@ -1037,6 +1125,7 @@ int illumina_pe(const Args &a) {
                   [&](TruthOut &t) { return t.adapter_only(sim, first, n, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)t.text.p, t.text.cap, &t.len, nullptr); }, false,
                   "Simulation of adapter-only pairs failed", n);
         }
+        if (ok && !depth_out.empty()) ok = write_depth(sim, ref, (int)device, depth_out);
     }
     for (TruthOut &t : truths) {                                 // truth.bam.bai: the block table ends with the end-of-file member
         if (!ok || !t.sorted) continue;
@@ -1077,6 +1166,7 @@ int illumina_pe(const Args &a) {
             remove(t.path.c_str());
             if (t.sorted) remove((t.path + ".bai").c_str());
         }
+        if (!depth_out.empty()) remove(depth_out.c_str());
         return 1;
     }
     INFO("Simulation finished succesfully");
@@ -1298,6 +1388,7 @@ const char *kUsage =
     "  illuminaPE\t\tsimulates illumina paired-end data from a fitted profile (-s) and a reference (-R)\n"
     "                 \t--writeAlleles alleles.fa[.gz]: with -V, the sequences the reads are drawn from -- every allele of every sequence as a FASTA record <name>_allele<a>, written on the device before generation (plain: with its index alleles.fa.fai; .gz: BGZF blocks)\n"
     "                 \t--truthAlleles: with -V, --truthSam / --truthBam write their records in ALLELE coordinates: against the sequences of --writeAlleles (RNAME <name>_allele<a>, the plain CIGAR, tag XI:i; not with --truthVariants, --truthMD, --truthBamSort)\n"
+    "                 \t--truthDepth depth.bedgraph[.gz]: the per-base coverage of the simulated reads (the M columns of the mapped truth records, as `samtools depth` counts them) accumulated on the device and written after the last batch as bedGraph, one line per run of equal depth, zero runs included; with or without --truthSam / --truthBam (at most one of them), with -V in reference coordinates; not with --truthAlleles; one worker\n"
     "                 \t--truthBam truth.bam: the same records as BAM (BGZF blocks made on the device; unsorted, no index; may be given beside --truthSam; with -V only with --truthVariants or --truthAlleles; not with --hostGzip, one worker)\n"
     "                 \t--truthBamSort: with --truthBam, the records sorted by coordinate on the device (@HD SO:coordinate) and the index truth.bam.bai beside the file\n"
     "                 \t--truthVariants: with -V, --truthSam / --truthBam [--truthBamSort] write their records in reference coordinates (inserted bases as I, deleted ones as D, tag XI:i)\n"

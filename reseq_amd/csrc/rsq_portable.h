@@ -189,8 +189,20 @@ RSQ_HD void image_or(RSQ_LDS uint32_t *w, uint32_t v) {
 #endif
 }
 
+// v added modulo 2^32 to a counter in device memory that lanes of any workgroup add to as well (rsq_depth.h): a global atomic add whose result nobody reads.  The
+// host: one lane at a time.  Domain: p is a multiple of four.  (Its table and its two programs are its own: tests/hostemu/counter_trial.cpp,
+// tests/test_portable_counter.py -- the host form against the meaning stated here, the device form word for word the same.)
+RSQ_HD void counter_add(uint32_t *p, uint32_t v) {
+#if RSQ_ON_DEVICE
+    (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    RSQ_DOMAIN((uintptr_t)p % 4u == 0u);
+    *p += v;
+#endif
+}
+
 // ------------------------------------------------------------------------------------------------ arithmetic
-// x / d.  Domain: x < 2^24, 1 <= d, a quotient below 2^17 (the percentages: at most 65535 + d / 2 over d).  The device has no integer division: the compiler's
+// x / d. Domain: x < 2^24, 1 <= d, a quotient below 2^17 (the percentages: at most 65535 + d / 2 over d).  The device has no integer division: the compiler's
 // sequence for a 32-bit one is about 28 instructions.  Here: both operands are exact in single precision, the product with the reciprocal (1 ulp) is off by less than
 // 2^17 * 2^-22 of the true quotient, so its integer part is the quotient or one beside it, and the remainder says which.
 RSQ_HD uint32_t div_small(uint32_t x, uint32_t d) {

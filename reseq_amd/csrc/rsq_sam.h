@@ -164,15 +164,17 @@ RSQ_HD SamAlign sam_align_at(bool has_f, const Fragment &f, uint32_t seg, const 
     a.tlen = leftmost ? span : -span;
     return a;
 }
+// POS - 1 of one mate from its own walk (a mapped pair's): what sam_align makes POS of, and where the depth of rsq_depth.h begins to count the mate
+RSQ_HD uint32_t sam_mate_pos(const Fragment &f, uint32_t seg, const SamMate &w) {
+    const bool rev = seg != f.strand;                                   // fragment_src (rsq_reads.h): src.reverse = seg != f.strand
+    return (rev ? f.start + f.len - w.t : f.start) + (rev ? w.trail : w.lead);
+}
 RSQ_HD SamAlign sam_align(bool has_f, const Fragment &f, uint32_t seg, const SamMate &w0, const SamMate &w1) {
-    const uint32_t end = f.start + f.len;
     int32_t pos[2], last[2];
     for (uint32_t s = 0; s < 2u; ++s) {
         const SamMate &w = s ? w1 : w0;
-        const bool rev = s != f.strand;                                 // fragment_src (rsq_reads.h): src.reverse = seg != f.strand
-        const uint32_t d_left = rev ? w.trail : w.lead, d_right = rev ? w.lead : w.trail;
-        pos[s] = (int32_t)((rev ? end - w.t : f.start) + 1u + d_left);
-        last[s] = pos[s] + (int32_t)((uint32_t)w.t - d_left - d_right) - 1;
+        pos[s] = (int32_t)(sam_mate_pos(f, s, w) + 1u);
+        last[s] = pos[s] + (int32_t)((uint32_t)w.t - w.lead - w.trail) - 1;
     }
     return sam_align_at(has_f, f, seg, pos, last);
 }

@@ -32,6 +32,7 @@
 #include "rsq_bam.h"
 #include "rsq_md.h"
 #include "rsq_bamsort.h"
+#include "rsq_depth.h"
 #include "rsq_alleles.h"
 #include "rsq_pack.h"
 #include "rsq_prepass.h"
@@ -296,6 +297,23 @@ struct rsq_sim : PrepassSim {
         BamIndexState index;
     } bam_sorted;
     uint64_t record_text_bytes = 480;        // the same for the seqToIllumina records' text (error_model_text)
+    // rsq_sim_depth_*: a run that accumulates the truth depth of the pairs calls (rsq_depth.h)
+    struct Depth {
+        bool open = false, finished = false;      // between rsq_sim_depth_begin and rsq_sim_depth_end; rsq_sim_depth_finish has turned the differences into depths
+        DevBuf diff, bad, tile_sums;              // the array (differences, then depths); elements that fell outside their sequence; the prefix sum's scratch
+        uint64_t words = 0;                       // of the array: depth_words()
+        // the part of the running pairs call (a call is one part while a run is open), added once the call's return code is RSQ_OK
+        bool have_part = false;
+        const Fragment *frags = nullptr;
+        const FragmentVar *fvars = nullptr;
+        uint64_t n_pairs = 0;
+        RawLayout raw{};
+        const uint32_t *row_order = nullptr;
+        // rsq_sim_depth_bedgraph: the sequence and the end of the piece before, and where the run that was open there began
+        uint32_t bg_seq = 0xFFFFFFFFu, bg_carry = 0;
+        uint64_t bg_next = 0;
+        DevBuf flags, rank, ends, sizes, offsets;
+    } depth;
     // rsq_sim_alleles_fasta (rsq_alleles.h): the records of the alleles' FASTA text, made at the first call (n == 0: not yet; a reference taken in later starts over)
     struct AllelesText {
         DevBuf records;
@@ -1059,6 +1077,7 @@ static uint32_t pairs_parts(const rsq_sim &s, uint32_t n_blocks) {
     // formatter both live on the memory system (gathers in the 24 MB surrounding table; 15 GB of raw arrays and text), so side by side each takes nearly as long
     // as the two in a row, and every part adds a read-kernel tail.  One part unless asked (option overlap = n, tests).
     const int64_t opt = s.opt.overlap;
+    if (s.depth.open) return 1u;                                     // a depth run adds the call's part once its return code is known (depth_take): the part's arrays must still be there
     return opt > 0 ? (uint32_t)std::min<int64_t>(opt, std::max<uint32_t>(n_blocks, 1u)) : 1u;
 }
 // what rsq_sim_pairs and rsq_sim_job_generate ask of a block range before anything is sized from it
@@ -1084,6 +1103,7 @@ static int sim_pairs(rsq_sim &s, const PairsCall &call, uint32_t block_lo, uint3
     *n_pairs = 0;
     *call.r1.len = *call.r2.len = 0;
     if (call.has_truth()) *call.truth.len = 0;
+    s.depth.have_part = false;
     if (block_lo == block_hi) return RSQ_OK;
     reset_call_timers(s);
     const uint32_t parts = pairs_parts(s, block_hi - block_lo);
@@ -1140,6 +1160,15 @@ static int sim_pairs(rsq_sim &s, const PairsCall &call, uint32_t block_lo, uint3
             }
             text_stage(s, call, part, s_text);
             if (call.has_truth()) sam_stage(s, call, part, s_text);
+            if (s.depth.open) {                                      // (one part: pairs_parts)
+                rsq_sim::Depth &d = s.depth;
+                d.have_part = true;
+                d.frags = part.frags;
+                d.fvars = part.fvars;
+                d.n_pairs = part.n_pairs;
+                d.raw = part.raw;
+                d.row_order = part.row_order;
+            }
         } else {                                                     // no pairs in this part: its text ends where it begins
             HIP_CHECK(hipMemcpyAsync(s.totals.as<uint64_t>() + 2 * (k + 1), s.totals.as<uint64_t>() + 2 * k, 16, hipMemcpyDeviceToDevice, s_text));
             if (call.has_truth()) HIP_CHECK(hipMemcpyAsync(s.sam_totals.as<uint64_t>() + k + 1, s.sam_totals.as<uint64_t>() + k, 8, hipMemcpyDeviceToDevice, s_text));
@@ -1160,6 +1189,32 @@ static int sim_pairs(rsq_sim &s, const PairsCall &call, uint32_t block_lo, uint3
     HIP_CHECK(hipStreamSynchronize(st));
     abort_guard.armed = false;
     return rc;
+}
+
+// A depth run (rsq_depth.h) takes the pairs of a call that has returned RSQ_OK -- and of no other, so a call repeated after RSQ_ENOSPC counts its pairs once: the
+// call was one part, whose fragments and raw arrays still lie in the workspace.  The stream is idle afterwards (the next call may reuse the arrays on another).
+static void depth_take(rsq_sim &s, hipStream_t st) {
+    rsq_sim::Depth &d = s.depth;
+    if (!d.have_part || !d.n_pairs) return;
+    d.have_part = false;
+    const dim3 grid((uint32_t)cdiv(2u * d.n_pairs, 256)), block(256);
+    s.timers["depth_add"].start(st);
+    if (s.has_variants) hipLaunchKernelGGL(k_depth_add<true>, grid, block, 0, st, s.dev, d.frags, d.fvars, d.n_pairs, d.raw, d.row_order, d.diff.as<uint32_t>(), d.bad.as<uint32_t>());
+    else hipLaunchKernelGGL(k_depth_add<false>, grid, block, 0, st, s.dev, d.frags, d.fvars, d.n_pairs, d.raw, d.row_order, d.diff.as<uint32_t>(), d.bad.as<uint32_t>());
+    s.timers["depth_add"].stop(st);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+// what a depth run refuses of the calls that simulate: pairs after rsq_sim_depth_finish
+static bool depth_refusal(const rsq_sim &s) {
+    if (!s.depth.open || !s.depth.finished) return false;
+    g_last_error = "the depth run is finished (rsq_sim_depth_finish): rsq_sim_depth_end must run before more pairs are simulated";
+    return true;
+}
+static bool depth_refuses_job(const rsq_sim &s, const char *call) {
+    if (!s.depth.open) return false;
+    g_last_error = std::string(call) + ": a depth run is open (rsq_sim_depth_begin); the job calls do not accumulate depth";
+    return true;
 }
 
 // The end of a sorted call (rsq_bamsort.h), behind its parts -- or, at the flush, over the held records alone: the sort of the directory's keys, the cut, and,
@@ -2223,6 +2278,10 @@ int rsq_sim_truth_alleles(rsq_sim *s, int on) {
     }
     REQUIRE(!s->truth_variants, "rsq_sim_truth_alleles: rsq_sim_truth_variants has chosen reference coordinates for the truth alignments; a record has one coordinate system (switch that off first)");
     REQUIRE(s->has_ref && s->has_variants, "rsq_sim_truth_alleles needs a reference with variants (rsq_ref_read_variants): without them there are no alleles");
+    if (s->depth.open) {
+        g_last_error = "rsq_sim_truth_alleles cannot be switched on while a depth run is open (rsq_sim_depth_begin): depth is in reference coordinates";
+        return RSQ_ESTATE;
+    }
     if (s->bam_sorted.open) {
         g_last_error = "rsq_sim_truth_alleles cannot change inside a sorted run (between rsq_sim_bam_sorted_begin and rsq_sim_bam_sorted_flush)";
         return RSQ_ESTATE;
@@ -2247,11 +2306,170 @@ int rsq_sim_truth_md(rsq_sim *s, int on) {
     }
     return RSQ_OK;
 }
+// ---- truth depth (rsq_depth.h; include/reseq_amd.h rsq_sim_depth_*)
+#define REQUIRE_STATE(cond, msg)    \
+    do {                            \
+        if (!(cond)) {              \
+            g_last_error = msg;     \
+            return RSQ_ESTATE;      \
+        }                           \
+    } while (0)
+int rsq_sim_depth_begin(rsq_sim *s) {
+    REQUIRE(s, "null argument");
+    REQUIRE_STATE(s->prepared && s->has_ref, "rsq_sim_prepare with a reference must run before rsq_sim_depth_begin");
+    REQUIRE_STATE(!s->depth.open, "rsq_sim_depth_begin: a depth run is open already (rsq_sim_depth_end ends it)");
+    REQUIRE(!s->truth_alleles, "rsq_sim_depth_begin: depth is in reference coordinates; rsq_sim_truth_alleles has chosen allele coordinates (switch that off first)");
+    return guard([&] {
+        HIP_CHECK(hipSetDevice(s->device));
+        rsq_sim::Depth &d = s->depth;
+        d.words = depth_words(s->total_ref_size, s->dev.n_seqs);
+        d.diff.reserve(d.words * 4u);
+        d.bad.reserve(8);
+        HIP_CHECK(hipMemset(d.diff.as<void>(), 0, d.words * 4u));
+        HIP_CHECK(hipMemset(d.bad.as<void>(), 0, 8));
+        d.open = true;
+        d.finished = d.have_part = false;
+        d.bg_seq = 0xFFFFFFFFu;
+        return (int)RSQ_OK;
+    });
+}
+int rsq_sim_depth_finish(rsq_sim *s, void *stream) {
+    REQUIRE(s, "null argument");
+    REQUIRE_STATE(s->depth.open && !s->depth.finished, "rsq_sim_depth_finish: no depth run is open, or it is finished already");
+    return guard([&] {
+        HIP_CHECK(hipSetDevice(s->device));
+        rsq_sim::Depth &d = s->depth;
+        const hipStream_t st = (hipStream_t)stream;
+        const uint32_t tiles = (uint32_t)(d.words / kDepthTile);
+        reset_call_timers(*s);
+        d.tile_sums.reserve((size_t)tiles * 4u + 16u);
+        s->timers["depth_scan"].start(st);
+        hipLaunchKernelGGL(k_depth_tile_sums, dim3(tiles), dim3(kDepthBlock), 0, st, d.diff.as<const uint32_t>(), d.tile_sums.as<uint32_t>());
+        hipLaunchKernelGGL(k_depth_tiles, dim3(1), dim3(kDepthTilesBlock), 0, st, d.tile_sums.as<uint32_t>(), tiles);
+        hipLaunchKernelGGL(k_depth_apply, dim3(tiles), dim3(kDepthBlock), 0, st, d.diff.as<uint32_t>(), d.tile_sums.as<const uint32_t>());
+        s->timers["depth_scan"].stop(st);
+        HIP_CHECK(hipGetLastError());
+        uint32_t bad = 0;
+        HIP_CHECK(hipMemcpyAsync(&bad, d.bad.as<uint32_t>(), 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        d.finished = true;
+        if (bad) {
+            g_last_error = "truth depth: " + std::to_string(bad) + " alignment elements lay outside their sequence and were left out";
+            return (int)RSQ_EINVAL;
+        }
+        return (int)RSQ_OK;
+    });
+}
+static int depth_window(const rsq_sim &s, const char *call, uint32_t seq, uint64_t lo, uint64_t hi) {
+    if (!s.depth.open || !s.depth.finished) {
+        g_last_error = std::string(call) + ": rsq_sim_depth_finish must have run (the array holds differences until then)";
+        return RSQ_ESTATE;
+    }
+    if (seq >= s.seq_len.size() || lo > hi || hi > s.seq_len[seq]) {
+        g_last_error = std::string(call) + ": no such sequence, or a window that is not inside it";
+        return RSQ_EINVAL;
+    }
+    return RSQ_OK;
+}
+int rsq_sim_depth_counts(rsq_sim *s, uint32_t seq, uint64_t lo, uint64_t hi, uint32_t *depth_dev, void *stream) {
+    REQUIRE(s, "null argument");
+    if (const int rc = depth_window(*s, "rsq_sim_depth_counts", seq, lo, hi)) return rc;
+    REQUIRE(depth_dev || lo == hi, "null argument");
+    if (lo == hi) return RSQ_OK;
+    return guard([&] {
+        HIP_CHECK(hipSetDevice(s->device));
+        const hipStream_t st = (hipStream_t)stream;
+        HIP_CHECK(hipMemcpyAsync(depth_dev, s->depth.diff.as<uint32_t>() + s->seq_base_off[seq] + seq + lo, (hi - lo) * 4u, hipMemcpyDeviceToDevice, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        return (int)RSQ_OK;
+    });
+}
+int rsq_sim_depth_bedgraph(rsq_sim *s, uint32_t seq, uint64_t lo, uint64_t hi, char *dst_dev, size_t cap, size_t *len, uint64_t *n_lines, void *stream) {
+    REQUIRE(s && len && n_lines, "null argument");
+    *len = 0;
+    *n_lines = 0;
+    if (const int rc = depth_window(*s, "rsq_sim_depth_bedgraph", seq, lo, hi)) return rc;
+    rsq_sim::Depth &d = s->depth;
+    REQUIRE_STATE(lo == 0 || (seq == d.bg_seq && lo == d.bg_next),
+                  "rsq_sim_depth_bedgraph: the pieces of a sequence are contiguous and rising from 0 -- this one does not continue the piece before it");
+    const uint32_t carry = lo ? d.bg_carry : 0u;                      // where the run that is open at lo began
+    const uint64_t n = hi - lo;
+    auto done = [&](uint32_t new_carry) {
+        d.bg_seq = seq;
+        d.bg_next = hi;
+        d.bg_carry = new_carry;
+        return (int)RSQ_OK;
+    };
+    if (!n) return done(carry);
+    return guard([&] {
+        HIP_CHECK(hipSetDevice(s->device));
+        const hipStream_t st = (hipStream_t)stream;
+        reset_call_timers(*s);
+        s->cur = &s->ws[0];                                             // (the scans' scratch)
+        const uint32_t *depths = d.diff.as<const uint32_t>() + s->seq_base_off[seq] + seq;
+        const uint32_t name_len = (uint32_t)s->ref_first_names[seq].size();
+        d.flags.reserve(n * 4u + 16u);
+        d.rank.reserve((n + 1u) * 8u);
+        s->timers["depth_lines"].start(st);
+        hipLaunchKernelGGL(k_depth_ends, dim3((uint32_t)cdiv(n, 256)), dim3(256), 0, st, depths, s->seq_len[seq], (uint32_t)lo, n, d.flags.as<uint32_t>());
+        exclusive_scan(*s, d.flags.as<uint32_t>(), n, d.rank.as<uint64_t>(), st);
+        s->timers["depth_lines"].stop(st);
+        uint64_t lines = 0;
+        HIP_CHECK(hipMemcpyAsync(&lines, d.rank.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (!lines) return done(carry);                                  // one run covers the piece and goes on
+        d.ends.reserve(lines * 4u + 16u);
+        d.sizes.reserve(lines * 4u + 16u);
+        d.offsets.reserve((lines + 1u) * 8u);
+        s->timers["depth_lines"].start(st);
+        hipLaunchKernelGGL(k_depth_run_ends, dim3((uint32_t)cdiv(n, 256)), dim3(256), 0, st, d.flags.as<const uint32_t>(), d.rank.as<const uint64_t>(), (uint32_t)lo, n, d.ends.as<uint32_t>());
+        hipLaunchKernelGGL(k_depth_line_sizes, dim3((uint32_t)cdiv(lines, 256)), dim3(256), 0, st, depths, d.ends.as<const uint32_t>(), lines, carry, name_len, d.sizes.as<uint32_t>());
+        exclusive_scan(*s, d.sizes.as<uint32_t>(), lines, d.offsets.as<uint64_t>(), st);
+        s->timers["depth_lines"].stop(st);
+        HIP_CHECK(hipGetLastError());
+        uint64_t bytes = 0;
+        uint32_t last_end = 0;
+        HIP_CHECK(hipMemcpyAsync(&bytes, d.offsets.as<uint64_t>() + lines, 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(&last_end, d.ends.as<uint32_t>() + (lines - 1u), 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        *len = bytes;
+        *n_lines = lines;
+        if (bytes > cap || !dst_dev) {                                   // nothing written, the carried start unchanged: the call can be repeated
+            g_last_error = "bedGraph buffer too small: need " + std::to_string(bytes) + " bytes";
+            return (int)RSQ_ENOSPC;
+        }
+        const uint32_t lds = depth_lds_bytes(name_len);
+        s->timers["depth_text"].start(st);
+        hipLaunchKernelGGL(k_depth_text, dim3((uint32_t)cdiv(lines, kDepthLines)), dim3(64), lds, st, s->names, seq, depths, d.ends.as<const uint32_t>(), carry, lines,
+                           d.offsets.as<const uint64_t>(), dst_dev, lds);
+        s->timers["depth_text"].stop(st);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(st));
+        return done(last_end);
+    });
+}
+int rsq_sim_depth_end(rsq_sim *s) {
+    REQUIRE(s, "null argument");
+    return guard([&] {
+        HIP_CHECK(hipSetDevice(s->device));
+        rsq_sim::Depth &d = s->depth;
+        for (DevBuf *b : {&d.diff, &d.bad, &d.tile_sums, &d.flags, &d.rank, &d.ends, &d.sizes, &d.offsets}) b->release();
+        d.open = d.finished = d.have_part = false;
+        d.words = 0;
+        return (int)RSQ_OK;
+    });
+}
+
 // the entry points of the pairs calls
 static int pairs_call(rsq_sim *s, const PairsCall &call, uint32_t block_lo, uint32_t block_hi, uint64_t *n_pairs) {
     REQUIRE(s && call.r1.len && call.r2.len && (call.truth.len || !call.has_truth()) && n_pairs, "null argument");
     if (call.has_truth() && truth_refusal(*s, call.bam())) return RSQ_EINVAL;
-    return guard([&] { return sim_pairs(*s, call, block_lo, block_hi, n_pairs); });
+    if (depth_refusal(*s)) return RSQ_ESTATE;
+    return guard([&] {
+        const int rc = sim_pairs(*s, call, block_lo, block_hi, n_pairs);
+        if (rc == RSQ_OK && s->depth.open) depth_take(*s, call.st);
+        return rc;
+    });
 }
 int rsq_sim_pairs(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, char *r1_dev, size_t r1_cap, size_t *r1_len, char *r2_dev, size_t r2_cap, size_t *r2_len,
                   uint64_t *n_pairs, rsq_fragment *frags_dev, size_t frags_cap, void *stream) {
@@ -2302,6 +2520,7 @@ int rsq_sim_pairs_bam_sorted(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, c
                              size_t bam_cap, size_t *bam_len, uint64_t *n_pairs, uint64_t *n_records, rsq_fragment *frags_dev, size_t frags_cap, void *stream) {
     REQUIRE(s && r1_len && r2_len && bam_len && n_pairs && n_records, "null argument");
     if (truth_refusal(*s, true)) return RSQ_EINVAL;
+    if (depth_refusal(*s)) return RSQ_ESTATE;
     rsq_sim::BamSorted &b = s->bam_sorted;
     *r1_len = *r2_len = *bam_len = 0;
     *n_pairs = *n_records = 0;
@@ -2329,6 +2548,7 @@ int rsq_sim_pairs_bam_sorted(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, c
         const uint64_t cut = bam_cut_key(block_hi, s->total_blocks, s->dev.n_seqs, s->block_seq.data(), s->first_block.data(), kBlockSize);
         const int end = sorted_finish(*s, call, rc, cut, block_hi);
         *n_records = b.call_records;
+        if (end == RSQ_OK && s->depth.open) depth_take(*s, st);         // (the run's state has moved on: the call will not be repeated)
         return end;
     });
 }
@@ -2384,6 +2604,7 @@ constexpr size_t kJobChunkBytes = (size_t)2 << 30, kJobSliceBytes = (size_t)32 <
 int rsq_sim_job_generate(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, uint32_t batch_blocks, uint64_t *n_pairs, uint64_t *r1_bytes, uint64_t *r2_bytes, void *stream) {
     REQUIRE(s && n_pairs && r1_bytes && r2_bytes, "null argument");
     *n_pairs = *r1_bytes = *r2_bytes = 0;
+    if (depth_refuses_job(*s, "rsq_sim_job_generate")) return RSQ_ESTATE;
     return guard([&] {
         HIP_CHECK(hipSetDevice(s->device));
         rsq_sim::JobText &job = s->job;
@@ -2453,6 +2674,7 @@ int rsq_sim_job_free(rsq_sim *s) {
 }
 int rsq_sim_job_write(rsq_sim *s, const char *r1_path, uint64_t r1_offset, const char *r2_path, uint64_t r2_offset, uint32_t threads_per_file) {
     REQUIRE(s && r1_path, "null argument");
+    if (depth_refuses_job(*s, "rsq_sim_job_write")) return RSQ_ESTATE;
     return guard([&] {
         const rsq_sim::JobText &job = s->job;
         if (!job.complete) {
@@ -2738,6 +2960,7 @@ static void job_compress_on_device(rsq_sim &s, hipStream_t st) {
 // A file of concatenated members is a gzip file: ranks exchange their COMPRESSED sizes and write their members at the offsets like plain text.
 int rsq_sim_job_compress(rsq_sim *s, uint64_t *r1_bytes, uint64_t *r2_bytes) {
     REQUIRE(s && r1_bytes && r2_bytes, "null argument");
+    if (depth_refuses_job(*s, "rsq_sim_job_compress")) return RSQ_ESTATE;
     return guard([&] {
         rsq_sim::JobText &job = s->job;
         if (!job.complete || job.is_packed || job.device_packed) {
@@ -2787,6 +3010,7 @@ int rsq_sim_job_compress(rsq_sim *s, uint64_t *r1_bytes, uint64_t *r2_bytes) {
 // a stretch of the kept text into device memory of the caller (what a rank contributes to one round of a gather of the output)
 int rsq_sim_job_read(rsq_sim *s, int file, uint64_t at, size_t bytes, char *dst_dev, void *stream) {
     REQUIRE(s && (file == 0 || file == 1) && (dst_dev || !bytes), "null argument, or a file that is neither 0 nor 1");
+    if (depth_refuses_job(*s, "rsq_sim_job_read")) return RSQ_ESTATE;
     return guard([&] {
         const rsq_sim::JobText &job = s->job;
         if (job.is_packed) {
