@@ -21,15 +21,25 @@ struct Words {
 
 
 // Philox4x32-10 (Salmon et al., SC11); key = seed, counter = (c0,c1,c2,c3).
+// KEYS_FROM: the first round in front of which the two round keys pass through RSQ_KEEP_IN_SGPR, for a caller whose seed is WAVE-UNIFORM and who draws in a loop.  The
+// compiler forms the twenty keys of a uniform seed ahead of the loop and keeps them in twenty scalar registers; a kernel at its scalar-register cap spills them and
+// pays a v_readlane_b32 per reload on the vector pipe.  Behind the barrier the keys of the later rounds are two s_add_u32 per round from two live registers.
+// kKeysAhead: no barrier (the compiler's own choice); 0: in front of every round.  The words do not depend on it.
+constexpr int kPhiloxRounds = 10, kKeysAhead = kPhiloxRounds;
+template <int KEYS_FROM = kKeysAhead>
 RSQ_HD Words philox(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
     uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
 #pragma unroll
-    for (int r = 0; r < 10; ++r) {
+    for (int r = 0; r < kPhiloxRounds; ++r) {
+        if (r >= KEYS_FROM) {
+            RSQ_KEEP_IN_SGPR(k0);
+            RSQ_KEEP_IN_SGPR(k1);
+        }
         const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;      // one v_mad_u64_u32 each
         const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        c0 = hi1 ^ c1 ^ k0;
+        c0 = xor3(hi1, c1, k0);                                                                // one v_bitop3_b32 each
         c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
+        c2 = xor3(hi0, c3, k1);
         c3 = lo0;
         k0 += 0x9E3779B9u;
         k1 += 0xBB67AE85u;
@@ -47,7 +57,8 @@ RSQ_HD double u53_to_unit(uint32_t hi, uint32_t lo) {
 struct Stream {
     uint64_t seed;
     uint32_t c0, c1, c2, c3base;
-    RSQ_HD Words step(uint32_t s) const { return philox(seed, c0, c1, c2, c3base | s); }
+    template <int KEYS_FROM = kKeysAhead>
+    RSQ_HD Words step(uint32_t s) const { return philox<KEYS_FROM>(seed, c0, c1, c2, c3base | s); }
 };
 RSQ_HD uint32_t pair_c3(uint32_t dom, uint32_t strand, uint32_t segsel, uint32_t allele = 0) { return (dom << 28) | (strand << 27) | (segsel << 25) | (allele << 17); }
 
@@ -356,6 +367,7 @@ RSQ_HD uint32_t draw_slim(const DevTable &t, const double *__restrict__ pool, Pa
 // (rsq_reads.h) which serves descriptors and the per-lane-varying margins from LDS.
 struct GlobalTables {
     using Sum = double;            // what a draw reports of prob_sum; the callers only ask whether it is 0
+    static constexpr int kKeysFrom = kKeysAhead;
     const DevSim &S;
     RSQ_HD const DevTable &quality(uint32_t i) const { return S.quality[i]; }
     RSQ_HD const DevTable &seq_quality(uint32_t i) const { return S.seq_quality[i]; }
@@ -721,7 +733,7 @@ struct ReadMachine {
         const bool tail = !TEMPLATE_PART && phase == kTail, from_template = TEMPLATE_PART || phase == kTemplate;
         const DevAdapters &ad = S.adapters[seg];
         const uint32_t it = par.iteration;                           // counted at the end of the step: old and new value never live side by side
-        const Words w = st.step(2u + it);
+        const Words w = st.template step<Tab::kKeysFrom>(2u + it);      // the step loops' draw: where its round keys are formed is the kernel's choice (philox)
         typename Tab::Sum prob_sum;
         uint32_t indel = 0, org_base = 0;
         if (!tail) {

@@ -40,6 +40,14 @@ typedef unsigned long uintptr_t;
 #else
 #define RSQ_ON_DEVICE 0
 #endif
+// the device pass of a compiler that knows v_bitop3_b32, for a target that has it (xor3 below; every other build takes the plain form)
+#define RSQ_HAS_BITOP3 0
+#if RSQ_ON_DEVICE && defined(__gfx950__) && defined(__has_builtin)
+#if __has_builtin(__builtin_amdgcn_bitop3_b32)
+#undef RSQ_HAS_BITOP3
+#define RSQ_HAS_BITOP3 1
+#endif
+#endif
 
 // ------------------------------------------------------------------------------------------------ attributes and macros
 #if RSQ_ON_DEVICE
@@ -47,13 +55,15 @@ typedef unsigned long uintptr_t;
 #define RSQ_NOINLINE __device__ __noinline__                     // a function that stays a call
 #define RSQ_SCHED_BARRIER() __builtin_amdgcn_sched_barrier(0)    // the instruction scheduler moves nothing across
 #define RSQ_KEEP_IN_VGPR(x) asm volatile("" : "+v"(x))           // the value is formed here, in a vector register: the compiler folds it into nothing earlier
-#define RSQ_UNROLL _Pragma("unroll")                             // where only the device wants the loop unrolled
+#define RSQ_KEEP_IN_SGPR(x) asm volatile("" : "+s"(x))           // the same for a WAVE-UNIFORM 32-bit value, in a scalar register: what is computed from it is computed behind this point, not ahead of the loop
+#define RSQ_UNROLL _Pragma("unroll")                           // where only the device wants the loop unrolled
 #define RSQ_DOMAIN(cond) ((void)0)
 #else
 #define RSQ_LDS
 #define RSQ_NOINLINE inline
 #define RSQ_SCHED_BARRIER() ((void)0)
 #define RSQ_KEEP_IN_VGPR(x) ((void)0)
+#define RSQ_KEEP_IN_SGPR(x) ((void)0)
 #define RSQ_UNROLL
 #define RSQ_DOMAIN(cond) assert(cond)                            // the stated domain of a primitive: outside it the two builds may differ
 #endif
@@ -136,6 +146,15 @@ RSQ_HD uint64_t bit_reverse64(uint64_t x) {
     return __builtin_bitreverse64(x);
 #else
     return ((uint64_t)bit_reverse32((uint32_t)x) << 32) | bit_reverse32((uint32_t)(x >> 32));
+#endif
+}
+// a ^ b ^ c: one v_bitop3_b32 (truth table 0x96, three-input parity) where the target has it -- the compiler pairs the xors up into two instructions by itself.  Any
+// words.  (Its table and its two programs are its own: tests/hostemu/xor3_trial.cpp, tests/test_portable_xor3.py, with RSQ_KEEP_IN_SGPR.)
+RSQ_HD uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
+#if RSQ_HAS_BITOP3
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96u);
+#else
+    return a ^ b ^ c;
 #endif
 }
 // min(max(d, 0), last): d held between 0 and last >= 0 (a median of three on the device)

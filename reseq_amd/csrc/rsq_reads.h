@@ -492,9 +492,12 @@ RSQ_HD bool word_screen_sure(const Float2 &a, const Float2 &p, const Float2 &e, 
 // geometry; a table's descriptor is read only on the double-precision route and for the rare fallbacks of FillReadPart.
 // QB = quads per batch of the quality draw (draw_screened_batched): its QQ quads are QQ / QB dependent round trips to LDS in every step.  RSQ_SCREEN_BATCH unless
 // the kernel asks for more (the kernel of the plain pairs: kQualityBatchPairs); the draws of short rows take RSQ_SCREEN_BATCH through draw_screened.
-template <uint32_t MASK, int QB = RSQ_SCREEN_BATCH>
+// KEYS: from which Philox round on the step's draw forms its round keys at their use (philox, rsq_core.h); kKeysAhead unless the kernel asks (the pairs' read
+// kernels: kKeysFromStep).
+template <uint32_t MASK, int QB = RSQ_SCREEN_BATCH, int KEYS = kKeysAhead>
 struct ScreenTables {
     using Sum = uint32_t;              // 0: prob_sum is 0, else 1 (all the callers ask; a double here costs the loop moves and 64-bit compares)
+    static constexpr int kKeysFrom = KEYS;
     static constexpr int QQ = (int)MASK;
     const DevSim &S;
     const RSQ_LDS float *img;          // image of the workgroup
@@ -1059,6 +1062,15 @@ RSQ_HD PackedRecordSrc packed_record_src(const uint16_t *codes, uint32_t at, uin
 #define RSQ_FILL_BLOCK_WALK 1024
 #endif
 constexpr int kQualityBatchPairs = RSQ_SCREEN_BATCH > 2 ? RSQ_SCREEN_BATCH : 2;      // quads per batch of the quality draw in the kernel of the plain pairs (ScreenTables QB): at least two
+// Where the read kernels of the pairs (plain and with variants) form the Philox round keys of a step (ScreenTables KEYS, philox's KEYS_FROM): from the third round on.
+// The seed is their argument, and both run at the scalar-register cap: with twenty keys held across the step loop they reload spilled ones through the vector pipe.
+// The first two rounds stay ahead of the barrier because the compiler computes their per-read-constant halves once per read.  The record kernel keeps the keys
+// ahead of the loop: it spills half as many scalar registers, gains four reloads and loses a vector register under one code generator (DESIGN_LOG.md section 30).
+// (Measurements: RSQ_SPEC_OPTIONS="-DRSQ_KEYS_FROM_STEP=10" compiles the kernel without the barrier, 0 with it in front of every round.)
+#ifndef RSQ_KEYS_FROM_STEP
+#define RSQ_KEYS_FROM_STEP 2
+#endif
+constexpr int kKeysFromStep = RSQ_KEYS_FROM_STEP;
 constexpr uint32_t kFillBlock = RSQ_FILL_BLOCK, kFillBlockWalk = RSQ_FILL_BLOCK_WALK;
 constexpr uint32_t kFillWavesMax = (kFillBlock > kFillBlockWalk ? kFillBlock : kFillBlockWalk) / 64u;      // the LDS image has a ring for every wave of the larger one
 RSQ_HD constexpr uint32_t fill_block(bool walk) { return walk ? kFillBlockWalk : kFillBlock; }
@@ -1109,7 +1121,7 @@ __device__ RSQ_LDS float *fill_stage_image(const DevSim &S, float *lds_image, ui
 // 64 reads of one wave through the state machine: one uniform step loop.  Screened (MASK != 0): at the beginning of a step the wave
 // copies the quality rows over the step's read position into its ring.  `tile` (index among the profile's tiles) is the lane's own.
 // `whole`: the template as init() wants it (the totals of the read's start); `src`: as the steps read it (the same object, or its WaveFragmentSrc).
-template <uint32_t MASK, int QB = RSQ_SCREEN_BATCH, class Whole, class Src, class Out>
+template <uint32_t MASK, int QB = RSQ_SCREEN_BATCH, int KEYS = kKeysAhead, class Whole, class Src, class Out>
 __device__ void fill_wave_reads(const DevSim &S, RSQ_LDS float *img, uint32_t qbase, uint32_t seg, bool active, const Stream &st, uint32_t tile, uint32_t fragment_length,
                                 const Whole &whole, const Src &src, Out &out, ReadMeta &meta) {
     ReadMachine m;
@@ -1122,7 +1134,7 @@ __device__ void fill_wave_reads(const DevSim &S, RSQ_LDS float *img, uint32_t qb
     } else {
         const uint32_t lane = threadIdx.x & 63u, n_items = lds_ring_items(S);
         RSQ_LDS float *ring = img + RSQ_PLAN(S, ring_off) + (threadIdx.x >> 6) * kRingRows * RSQ_PLAN(S, ring_stride);
-        ScreenTables<MASK, QB> tab{S, img, qbase, ring, 0u};
+        ScreenTables<MASK, QB, KEYS> tab{S, img, qbase, ring, 0u};
         m.idle();
         if (active) m.init(S, tab, st, seg, tile, fragment_length, whole);
         const RingItem mine = lds_ring_item(S, qbase, lane < n_items ? lane : 0u);      // the lane's first item (with one tile per image: its only one)
@@ -1265,7 +1277,7 @@ __device__ void fill_pair_chunk(const DevSim &S, const NameTable &names, RSQ_LDS
         VariantSrc src = variant_src(S, f, fvars ? &fv : nullptr, seg);
         if (raw.templates) src.converted = raw.templates + ((uint64_t)seg * n_pairs + pair0) * raw.template_words;
         ReadOut out = raw.out_of(r_out);
-        fill_wave_reads<MASK>(S, img, qbase, seg, active, st, tile, f.len, src, src, out, meta);
+        fill_wave_reads<MASK, RSQ_SCREEN_BATCH, kKeysFromStep>(S, img, qbase, seg, active, st, tile, f.len, src, src, out, meta);
     } else {
         // The kernel of the plain pairs carries the slim forms of cursor and template through its steps, and with the registers they leave it draws the quality
         // two quads at a time.  The kernels whose source walks per-lane state (variants above, records) have no registers to gain from them: compiled for P0
@@ -1276,7 +1288,7 @@ __device__ void fill_pair_chunk(const DevSim &S, const NameTable &names, RSQ_LDS
         if (templates) src.converted = templates + template_at;
         const WaveFragmentSrc walk = wave_fragment_src(S, src, templates, template_at);
         WaveReadOut out = raw.wave_out_of(r_out);
-        fill_wave_reads<MASK, kQualityBatchPairs>(S, img, qbase, seg, active, st, tile, f.len, src, walk, out, meta);
+        fill_wave_reads<MASK, kQualityBatchPairs, kKeysFromStep>(S, img, qbase, seg, active, st, tile, f.len, src, walk, out, meta);
     }
     if (active) {
         raw.meta[r_out] = meta;
