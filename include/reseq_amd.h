@@ -497,6 +497,68 @@ int rsq_sim_depth_counts(rsq_sim *s, uint32_t seq, uint64_t lo, uint64_t hi, uin
 int rsq_sim_depth_bedgraph(rsq_sim *s, uint32_t seq, uint64_t lo, uint64_t hi, char *dst_dev, size_t cap, size_t *len, uint64_t *n_lines, void *stream);
 int rsq_sim_depth_end(rsq_sim *s);
 
+/* Simulation report: exact integer histograms of what the pairs calls simulated, accumulated on the device while the pairs are simulated
+ * (reseq_amd/csrc/rsq_stats.h) -- the margins a user checks a run against the profile with, a few hundred KB where the FASTQ text is hundreds of GB.
+ *   The tables.  All counters are uint64 and exact.  Segment s is the template segment (file s + 1); a cycle is the 0-based position in the read as the FASTQ line
+ * has it, for reverse mates too.  L_s = the longest read length of segment s, L = the larger of the two (the per-segment tables have L rows for either segment;
+ * nothing is counted beyond L_s), F = the insert lengths' upper end, Q = one more than the largest quality value of the profile's quality tables, T = the tiles.
+ *   RSQ_STATS_PAIRS [2]: pairs with a fragment, adapter-only pairs (fragment length 0).  RSQ_STATS_STRAND [2], RSQ_STATS_TILE [T] (the index among the profile's
+ * tiles) and RSQ_STATS_FRAGMENT_LENGTH [F + 1]: over pairs with a fragment.
+ *   Per segment ([2] in front): RSQ_STATS_READ_LENGTH [L + 1]; RSQ_STATS_ERRORS_PER_READ [L + 1], indexed by min(the id's E<n>, L_s); RSQ_STATS_BASE_QUALITY [L][Q],
+ * the quality character minus the profile's offset; RSQ_STATS_BASE_CALL [L][5], A C G T N as written; RSQ_STATS_INSERTION, _DELETION, _ADAPTER, _TAIL [L] from
+ * the id's own CIGAR (the XC tag: read orientation, all parts) walked with q = 0: M n: q += n; I n: insertion[q .. q + n) += 1, q += n; D n:
+ * deletion[min(q, L_s - 1)] += n; S n: adapter[q .. q + n) += 1, q += n; H n: tail[q .. q + n) += 1, q += n (the id's H bases are in the read).
+ *   RSQ_STATS_MISMATCH [L]: every M column of a mapped record whose SEQ base differs from the reference as loaded, at that base's cycle (q in SEQ for a forward
+ * mate, read_len - 1 - q for a reverse one) -- exactly the columns rsq_sim_truth_md's MD:Z names (N is a mismatch; copy 0 of the reference; with variants the
+ * columns of rsq_sim_truth_variants, in reference coordinates whatever rsq_sim_truth_alleles says), so with variants or methylation it includes those differences.
+ *   RSQ_STATS_BAD [1]: a quality outside [0, Q), a base code outside the five, an element outside its sequence -- counted here and filed nowhere else.
+ *   rsq_sim_stats_begin opens a run: one zeroed device array of counters.  After rsq_sim_prepare with a reference, else RSQ_ESTATE; RSQ_ESTATE while a run is open.
+ * While a run is open rsq_sim_pairs, rsq_sim_pairs_sam, rsq_sim_pairs_bam and rsq_sim_pairs_bam_sorted, in any truth mode, add their pairs if and only if they return
+ * RSQ_OK: a call repeated after RSQ_ENOSPC counts once.  Such a call runs as one part whatever option overlap says, and the texts it writes are what it writes
+ * without a run.  A depth run may be open at the same time.  rsq_sim_job_generate, _write, _compress and _read return RSQ_ESTATE while a run is open.  The
+ * seqToIllumina calls (rsq_sim_error_model*) and the adapter-only calls are neither counted nor refused.
+ *   rsq_sim_stats_layout: the dimensions and, per table id, where the table lies in the array (offset in words; per-segment tables: segment 1 lies
+ * dim[0] * dim[1] words behind segment 0; rows of dim[1] words).  A caller reads the tables by id, never by their order.
+ *   rsq_sim_stats_counts: a snapshot of all counters into host memory, at any time between calls; the run goes on.  RSQ_ENOSPC when cap_words is below the
+ * layout's words.  rsq_last_warning says how many were filed under RSQ_STATS_BAD when that is not 0.
+ *   rsq_sim_stats_end frees the array (RSQ_OK without a run as well).
+ * Kernel times: "stats_rows" (base_quality, base_call) and "stats_mates" (the rest), one launch each per call that had pairs.  With no run open no call launches
+ * either, and every call is, launch for launch and byte for byte, what it is without these entry points.  Options stats_chunk (positions per LDS image),
+ * stats_slab (reads per slab), stats_groups (workgroups) and stats_form (1: the rows kernel without the skewed staging) are for tests and measurements. */
+enum {
+    RSQ_STATS_PAIRS = 0,
+    RSQ_STATS_STRAND,
+    RSQ_STATS_TILE,
+    RSQ_STATS_FRAGMENT_LENGTH,
+    RSQ_STATS_READ_LENGTH,
+    RSQ_STATS_ERRORS_PER_READ,
+    RSQ_STATS_BASE_QUALITY,
+    RSQ_STATS_BASE_CALL,
+    RSQ_STATS_INSERTION,
+    RSQ_STATS_DELETION,
+    RSQ_STATS_ADAPTER,
+    RSQ_STATS_TAIL,
+    RSQ_STATS_MISMATCH,
+    RSQ_STATS_BAD,
+    RSQ_STATS_COUNT
+};
+typedef struct rsq_stats_table {
+    uint64_t offset;          /* of segment 0's first counter, in words */
+    uint32_t segments;        /* 1, or 2 for a per-segment table */
+    uint32_t n_dims;          /* 1 or 2 */
+    uint32_t dim[2];          /* dim[1] is 1 for a table of one dimension */
+} rsq_stats_table;
+typedef struct rsq_stats_layout {
+    uint64_t words;           /* counters of the whole array */
+    uint32_t read_length[2];  /* L_0, L_1 */
+    uint32_t insert_to, n_quality, n_tiles, phred_offset;      /* F, Q, T, the profile's quality offset */
+    rsq_stats_table table[RSQ_STATS_COUNT];
+} rsq_stats_layout;
+int rsq_sim_stats_begin(rsq_sim *s);
+int rsq_sim_stats_layout(const rsq_sim *s, rsq_stats_layout *layout);
+int rsq_sim_stats_counts(rsq_sim *s, uint64_t *host, size_t cap_words, void *stream);
+int rsq_sim_stats_end(rsq_sim *s);
+
 /* Simulator::ApplyErrorsAndQualityToFastaInput with the FASTA header already parsed (reseq/Simulator.cpp:2403-2512):
  * n records of `read_len` template bases each.  Inputs (device): seqs[n][read_len] base codes 0..3, seg[n] template
  * segment 0/1, frag_len[n], dom[n][read_len] dominant-error base codes 0..4, rate[n][read_len] error percent.

@@ -122,6 +122,10 @@ SYMBOLS = {
     "rsq_sim_depth_counts": (C.c_int, [_vp, _u32, _u64, _u64, _vp, _vp]),
     "rsq_sim_depth_bedgraph": (C.c_int, [_vp, _u32, _u64, _u64, _vp, _sz, _psz, C.POINTER(_u64), _vp]),
     "rsq_sim_depth_end": (C.c_int, [_vp]),
+    "rsq_sim_stats_begin": (C.c_int, [_vp]),
+    "rsq_sim_stats_layout": (C.c_int, [_vp, _vp]),
+    "rsq_sim_stats_counts": (C.c_int, [_vp, _vp, _sz, _vp]),
+    "rsq_sim_stats_end": (C.c_int, [_vp]),
     "rsq_sim_bam_sorted_begin": (C.c_int, [_vp, _u64]),
     "rsq_sim_pairs_bam_sorted": (C.c_int, [_vp, _u32, _u32, _vp, _sz, _psz, _vp, _sz, _psz, _vp, _sz, _psz, C.POINTER(_u64), C.POINTER(_u64), _vp, _sz, _vp]),
     "rsq_sim_bam_sorted_flush": (C.c_int, [_vp, _vp, _sz, _psz, C.POINTER(_u64), C.POINTER(_u64), _vp]),
@@ -154,6 +158,20 @@ SYMBOLS = {
 }
 
 _lib = None
+
+
+# the tables of the simulation report by id (RSQ_STATS_* of include/reseq_amd.h)
+STATS_TABLES = ("pairs", "strand", "tile", "fragment_length", "read_length", "errors_per_read", "base_quality", "base_call", "insertion", "deletion", "adapter", "tail",
+                "mismatch", "bad")
+
+
+class StatsTable(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("segments", C.c_uint32), ("n_dims", C.c_uint32), ("dim", C.c_uint32 * 2)]
+
+
+class StatsLayout(C.Structure):
+    _fields_ = [("words", C.c_uint64), ("read_length", C.c_uint32 * 2), ("insert_to", C.c_uint32), ("n_quality", C.c_uint32), ("n_tiles", C.c_uint32),
+                ("phred_offset", C.c_uint32), ("table", StatsTable * len(STATS_TABLES))]
 
 
 def lib():
@@ -722,6 +740,32 @@ class Simulator:
         finally:
             if dst is not None:
                 dst.free()
+
+    def stats_begin(self):
+        """rsq_sim_stats_begin: opens a stats run; every pairs call that returns RSQ_OK adds its pairs to the simulation report's histograms"""
+        _check(lib().rsq_sim_stats_begin(self.h))
+
+    def stats_end(self):
+        """rsq_sim_stats_end: frees the run's counters; a new run may begin"""
+        _check(lib().rsq_sim_stats_end(self.h))
+
+    def stats_layout(self):
+        """rsq_sim_stats_layout: the dimensions and every table's place in the run's array of counters (StatsLayout)"""
+        layout = StatsLayout()
+        _check(lib().rsq_sim_stats_layout(self.h, C.byref(layout)))
+        return layout
+
+    def stats(self, stream=None):
+        """a snapshot of the open run's counters: {table name: numpy uint64 array}, shaped by the layout -- per-segment tables have a leading axis of 2 --; the
+        run goes on"""
+        layout = self.stats_layout()
+        words = np.zeros(int(layout.words), np.uint64)
+        _check(lib().rsq_sim_stats_counts(self.h, words.ctypes.data, len(words), stream))
+        out = {}
+        for name, t in zip(STATS_TABLES, layout.table):
+            shape = ([2] if t.segments == 2 else []) + [int(t.dim[i]) for i in range(t.n_dims)]
+            out[name] = words[int(t.offset):int(t.offset) + int(np.prod(shape))].reshape(shape).copy()
+        return out
 
     def pairs_sam_device(self, block_lo, block_hi, r1, r2, sam, frags=None, stream=None):
         """rsq_sim_pairs_sam into caller-owned DeviceArrays (None: only the sizes).  Returns (n_pairs, len1, len2, sam_len, rc)."""

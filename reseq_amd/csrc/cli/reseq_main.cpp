@@ -507,6 +507,53 @@ bool write_depth(rsq_sim *sim, const rsq_ref *ref, int device, const std::string
     return ok;
 }
 
+// --simStats report.tsv[.gz]: the simulation report (rsq_sim_stats_*), formatted here -- it is small --: "#reseq_amd simStats v1", '#' lines with the dimensions and
+// the quality offset, then one line per non-zero counter "table<TAB>segment<TAB>i<TAB>j<TAB>count" ('.' where an index does not apply), tables by id, indices
+// ascending.  .gz: one gzip member (zlib).  A failure leaves no file.
+const char *const kStatsNames[RSQ_STATS_COUNT] = {"pairs", "strand", "tile", "fragment_length", "read_length", "errors_per_read", "base_quality", "base_call", "insertion",
+                                                  "deletion", "adapter", "tail", "mismatch", "bad"};
+bool write_stats(const rsq_stats_layout &lay, const std::vector<uint64_t> &counts, const std::string &path) {
+    INFO("Writing the simulation report to " << path);
+    std::string text = "#reseq_amd simStats v1\n";
+    text += "#read_length\t" + std::to_string(lay.read_length[0]) + "\t" + std::to_string(lay.read_length[1]) + "\n";
+    text += "#insert_to\t" + std::to_string(lay.insert_to) + "\n#n_quality\t" + std::to_string(lay.n_quality) + "\n#n_tiles\t" + std::to_string(lay.n_tiles) + "\n#phred_offset\t" +
+            std::to_string(lay.phred_offset) + "\n";
+    for (uint32_t t = 0; t < RSQ_STATS_COUNT; ++t) {
+        const rsq_stats_table &tab = lay.table[t];
+        for (uint32_t seg = 0; seg < tab.segments; ++seg)
+            for (uint32_t i = 0; i < tab.dim[0]; ++i)
+                for (uint32_t j = 0; j < tab.dim[1]; ++j) {
+                    const uint64_t v = counts[tab.offset + ((uint64_t)seg * tab.dim[0] + i) * tab.dim[1] + j];
+                    if (!v) continue;
+                    text += kStatsNames[t];
+                    text += '\t';
+                    text += tab.segments == 2 ? std::to_string(seg) : std::string(".");
+                    text += '\t';
+                    text += t == RSQ_STATS_BAD ? std::string(".") : std::to_string(i);
+                    text += '\t';
+                    text += tab.n_dims == 2 ? std::to_string(j) : std::string(".");
+                    text += '\t';
+                    text += std::to_string(v);
+                    text += '\n';
+                }
+    }
+    bool ok;
+    if (rsq::textio::has_suffix(path, ".gz")) {
+        gzFile f = gzopen(path.c_str(), "wb");
+        ok = f && gzwrite(f, text.data(), (unsigned)text.size()) == (int)text.size();
+        if (f) ok = gzclose(f) == Z_OK && ok;
+    } else {
+        FILE *f = fopen(path.c_str(), "wb");
+        ok = f && fwrite(text.data(), 1, text.size(), f) == text.size();
+        if (f) ok = fclose(f) == 0 && ok;
+    }
+    if (!ok) {
+        ERR("Could not write '" << path << "'.");
+        remove(path.c_str());
+    }
+    return ok;
+}
+
 // illuminaPE on several devices inside one process (Simulator::Simulate starts its own worker threads, Simulator.cpp:2830-2836, and hands them blocks, :2384-2401).
 // N host threads, one simulator each on device (worker % devices): every worker prepares, simulates its contiguous share of the blocks with the text kept in device
 // memory (rsq_sim_job_generate), the exclusive scan of the workers' text sizes gives every worker its place in the two files, and all workers write at once
@@ -861,6 +908,27 @@ int illumina_pe(const Args &a) {
                 return 1;
             }
     }
+    // --simStats: the simulation report (rsq_sim_stats_*)
+    const std::string stats_out = a.get("simStats", "");
+    if (a.has("simStats")) {
+        if (stats_out.empty()) {
+            ERR("--simStats needs a file name");
+            return 1;
+        }
+        if (rsq::textio::has_suffix(stats_out, ".bz2")) {
+            ERR("--simStats: bzip2 output is not supported (write .gz or plain text)");
+            return 1;
+        }
+        if (stats_out == depth_out) {
+            ERR("--simStats and --truthDepth name the same file");
+            return 1;
+        }
+        for (const TruthOut &t : truths)
+            if (t.path == stats_out) {
+                ERR("--simStats and " << t.option << " name the same file");
+                return 1;
+            }
+    }
     const char *truth_option = any_truth ? truths.front().option : "";
     const std::string alleles_out = a.get("writeAlleles", "");
     if (a.has("writeAlleles") && alleles_out.empty()) {
@@ -911,6 +979,15 @@ int illumina_pe(const Args &a) {
                 ok = false;
             } else {
                 WARN("-j: the truth depth (--truthDepth) is accumulated by one worker only; one worker runs");
+                n_workers = 1;
+            }
+        }
+        if (ok && n_workers > 1 && !stats_out.empty()) {
+            if (a.has("gpus")) {
+                ERR("--simStats: the simulation report is accumulated by one worker only (run without --gpus, or with --gpus 1)");
+                ok = false;
+            } else {
+                WARN("-j: the simulation report (--simStats) is accumulated by one worker only; one worker runs");
                 n_workers = 1;
             }
         }
@@ -990,6 +1067,23 @@ int illumina_pe(const Args &a) {
     }
     if (ok && !sys_read.empty()) ok = check(rsq_sim_read_sys_errors(sim, sys_read.c_str()), "Could not read systematic error profile");
     if (ok && !depth_out.empty()) ok = check(rsq_sim_depth_begin(sim), "--truthDepth");      // every batch's pairs count once, whichever call simulates them
+    // --simStats: one run over all batches -- a batch repeated after RSQ_ENOSPC counts once (rsq_sim_stats_begin).  With both --truthSam and --truthBam a batch is
+    // simulated once for each: then a run is open only around the batch's first call and its counters are added up here, so that every batch counts once.
+    rsq_stats_layout stats_lay{};
+    std::vector<uint64_t> stats_sum, stats_part;
+    const bool stats_per_batch = !stats_out.empty() && truths.size() == 2;
+    bool stats_batch_counted = false;
+    auto stats_collect = [&] {                                   // the open run's counters into stats_sum
+        stats_part.assign(stats_lay.words, 0);
+        if (!check(rsq_sim_stats_counts(sim, stats_part.data(), stats_part.size(), nullptr), "--simStats")) return false;
+        for (size_t i = 0; i < stats_part.size(); ++i) stats_sum[i] += stats_part[i];
+        return true;
+    };
+    if (ok && !stats_out.empty()) {
+        ok = check(rsq_sim_stats_begin(sim), "--simStats") && check(rsq_sim_stats_layout(sim, &stats_lay), "--simStats");
+        if (ok) stats_sum.assign(stats_lay.words, 0);
+        if (ok && stats_per_batch) ok = check(rsq_sim_stats_end(sim), "--simStats");
+    }
     trace.at("prepared");
     AsyncOut f1, f2;
     // .gz outputs: the text of every call becomes gzip members on the device (rsq_sim_gzip_device) -- a third of the bytes cross the link and the writer threads
@@ -1099,12 +1193,21 @@ int illumina_pe(const Args &a) {
         for (uint32_t lo = 1; ok && lo <= info.total_blocks; lo += step) {
             const uint32_t hi = std::min(info.total_blocks + 1, lo + step);
             uint64_t n = 0;
+            stats_batch_counted = false;
             batch([&] { return rsq_sim_pairs(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, &n, nullptr, 0, nullptr); },
                   [&](TruthOut &t) {
                       uint64_t n_records = 0;
-                      if (t.sorted)
-                          return rsq_sim_pairs_bam_sorted(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)t.text.p, t.text.cap, &t.len, &n, &n_records, nullptr, 0, nullptr);
-                      return t.pairs(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)t.text.p, t.text.cap, &t.len, &n, nullptr, 0, nullptr);
+                      auto call = [&] {
+                          if (t.sorted)
+                              return rsq_sim_pairs_bam_sorted(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)t.text.p, t.text.cap, &t.len, &n, &n_records, nullptr, 0, nullptr);
+                          return t.pairs(sim, lo, hi, (char *)d1.p, d1.cap, &l1, (char *)d2.p, d2.cap, &l2, (char *)t.text.p, t.text.cap, &t.len, &n, nullptr, 0, nullptr);
+                      };
+                      if (!stats_per_batch || stats_batch_counted) return call();
+                      if (rsq_sim_stats_begin(sim) != RSQ_OK) return (int)RSQ_ESTATE;      // the first call of the batch that returns RSQ_OK is the one that counts
+                      const int rc = call();
+                      if (rc == RSQ_OK) stats_batch_counted = stats_collect();
+                      rsq_sim_stats_end(sim);
+                      return rc == RSQ_OK && !stats_batch_counted ? (int)RSQ_ESTATE : rc;
                   },
                   true,
                   "Simulation failed", n);
@@ -1126,6 +1229,12 @@ int illumina_pe(const Args &a) {
                   "Simulation of adapter-only pairs failed", n);
         }
         if (ok && !depth_out.empty()) ok = write_depth(sim, ref, (int)device, depth_out);
+        if (ok && !stats_out.empty()) {
+            if (!stats_per_batch) ok = stats_collect();
+            rsq_sim_stats_end(sim);
+            if (ok && *rsq_last_warning()) WARN(rsq_last_warning());
+            ok = ok && write_stats(stats_lay, stats_sum, stats_out);
+        }
     }
     for (TruthOut &t : truths) {                                 // truth.bam.bai: the block table ends with the end-of-file member
         if (!ok || !t.sorted) continue;
@@ -1167,6 +1276,7 @@ int illumina_pe(const Args &a) {
             if (t.sorted) remove((t.path + ".bai").c_str());
         }
         if (!depth_out.empty()) remove(depth_out.c_str());
+        if (!stats_out.empty()) remove(stats_out.c_str());
         return 1;
     }
     INFO("Simulation finished succesfully");
@@ -1389,6 +1499,7 @@ const char *kUsage =
     "                 \t--writeAlleles alleles.fa[.gz]: with -V, the sequences the reads are drawn from -- every allele of every sequence as a FASTA record <name>_allele<a>, written on the device before generation (plain: with its index alleles.fa.fai; .gz: BGZF blocks)\n"
     "                 \t--truthAlleles: with -V, --truthSam / --truthBam write their records in ALLELE coordinates: against the sequences of --writeAlleles (RNAME <name>_allele<a>, the plain CIGAR, tag XI:i; not with --truthVariants, --truthMD, --truthBamSort)\n"
     "                 \t--truthDepth depth.bedgraph[.gz]: the per-base coverage of the simulated reads (the M columns of the mapped truth records, as `samtools depth` counts them) accumulated on the device and written after the last batch as bedGraph, one line per run of equal depth, zero runs included; with or without --truthSam / --truthBam (at most one of them), with -V in reference coordinates; not with --truthAlleles; one worker\n"
+    "                 \t--simStats report.tsv[.gz]: the simulation report -- exact per-cycle histograms of the simulated reads (quality and base call by cycle, read and fragment lengths, errors per read, insertions, deletions, adapter and tail bases and mismatches to the reference by cycle, pairs, strands, tiles), counted on the device while the reads are made and written after the last batch as '#' lines with the dimensions and one line table<TAB>segment<TAB>i<TAB>j<TAB>count per non-zero counter; with or without any --truth* option; one worker\n"
     "                 \t--truthBam truth.bam: the same records as BAM (BGZF blocks made on the device; unsorted, no index; may be given beside --truthSam; with -V only with --truthVariants or --truthAlleles; not with --hostGzip, one worker)\n"
     "                 \t--truthBamSort: with --truthBam, the records sorted by coordinate on the device (@HD SO:coordinate) and the index truth.bam.bai beside the file\n"
     "                 \t--truthVariants: with -V, --truthSam / --truthBam [--truthBamSort] write their records in reference coordinates (inserted bases as I, deleted ones as D, tag XI:i)\n"

@@ -47,6 +47,7 @@ const OptionEntry kOptionTable[] = {
     {"hiprtc_by_name", &Options::hiprtc_by_name}, {"gzip_route", &Options::gzip_route},       {"gzip_stretch", &Options::gzip_stretch},
     {"sieve_lds", &Options::sieve_lds},         {"sieve_lds_bytes", &Options::sieve_lds_bytes}, {"sieve_tracks_mb", &Options::sieve_tracks_mb},
     {"wide_rows", &Options::wide_rows},
+    {"stats_chunk", &Options::stats_chunk},     {"stats_slab", &Options::stats_slab},       {"stats_groups", &Options::stats_groups},   {"stats_form", &Options::stats_form},
 };
 }  // namespace
 bool set_option(const char *name, int64_t value) {

@@ -53,6 +53,10 @@ struct Options {
     int64_t sieve_tracks_mb = 4096;    // the surrounding-bias tracks of the pre-pass (16 bytes per position) stay for the sieve's candidate kernel when they take no more MB than this; 0: never
     int64_t wide_rows = 0;             // 1: the read kernel's cursor forms 64-bit addresses (RawLayout::wide) as for raw arrays of 4 GB and more, whatever the call's size (tests)
     int64_t overlap = 0;               // n > 1: rsq_sim_pairs cuts its block range into n sub-ranges whose sieve / reads / text stages are pipelined on three streams
+    int64_t stats_chunk = 0;           // > 0: positions per LDS image of the simulation report's rows kernel (rsq_stats.h; rounded up to a multiple of four).  Tests: so that a short read crosses chunks
+    int64_t stats_slab = 0;            // > 0: reads per slab of the rows kernel (default 1024)
+    int64_t stats_groups = 0;          // > 0: workgroups of the report's persistent grids (default: four a CU)
+    int64_t stats_form = 0;            // 1: the rows kernel in its direct form, every lane of a wave at the same word (the measurement of DESIGN_LOG section 31); 0: staged and skewed
 };
 Options &options();                                               // the process-wide values
 bool set_option(const char *name, int64_t value);                 // false: no such option

@@ -68,6 +68,13 @@ struct MdRef {
     }
 };
 
+// A sink that wants to know WHERE a mismatch stands has a member mismatch(q), q the column's place in SEQ as written (rsq_stats.h); the sinks that write the
+// string have none and are handed nothing more than before.
+template <class Out>
+RSQ_HD auto md_note_mismatch(Out &o, uint32_t q, int) -> decltype(o.mismatch(q), void()) { o.mismatch(q); }
+template <class Out>
+RSQ_HD void md_note_mismatch(Out &, uint32_t, long) {}
+
 // The visitor of a mate's columns in ascending reference order (op: 0 M, 1 D, 2 I; p: the reference position of the first of `count` M or D columns): the MD
 // string into `o` (num, ch, bytes, element: any sink of rsq_text.h / rsq_format.h, or MdCount), NM in nm.  q: the column's place in SEQ as written.
 template <class Out>
@@ -94,6 +101,7 @@ struct MdCols {
             while (mm) {                                                // (the rare step: one round a mismatch)
                 const uint32_t i = lowest_set_bit64(mm) >> 1;
                 o.element((char)md_ref_letter((uint32_t)(r >> (2u * i)) & 3u), run + i - done);
+                md_note_mismatch(o, q + i, 0);
                 run = 0;
                 done = i + 1u;
                 ++nm;

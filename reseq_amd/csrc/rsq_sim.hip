@@ -33,6 +33,7 @@
 #include "rsq_md.h"
 #include "rsq_bamsort.h"
 #include "rsq_depth.h"
+#include "rsq_stats.h"
 #include "rsq_alleles.h"
 #include "rsq_pack.h"
 #include "rsq_prepass.h"
@@ -302,18 +303,28 @@ struct rsq_sim : PrepassSim {
         bool open = false, finished = false;      // between rsq_sim_depth_begin and rsq_sim_depth_end; rsq_sim_depth_finish has turned the differences into depths
         DevBuf diff, bad, tile_sums;              // the array (differences, then depths); elements that fell outside their sequence; the prefix sum's scratch
         uint64_t words = 0;                       // of the array: depth_words()
-        // the part of the running pairs call (a call is one part while a run is open), added once the call's return code is RSQ_OK
-        bool have_part = false;
-        const Fragment *frags = nullptr;
-        const FragmentVar *fvars = nullptr;
-        uint64_t n_pairs = 0;
-        RawLayout raw{};
-        const uint32_t *row_order = nullptr;
         // rsq_sim_depth_bedgraph: the sequence and the end of the piece before, and where the run that was open there began
         uint32_t bg_seq = 0xFFFFFFFFu, bg_carry = 0;
         uint64_t bg_next = 0;
         DevBuf flags, rank, ends, sizes, offsets;
     } depth;
+    // rsq_sim_stats_*: a run that accumulates the simulation report of the pairs calls (rsq_stats.h)
+    struct Stats {
+        bool open = false;                        // between rsq_sim_stats_begin and rsq_sim_stats_end
+        DevBuf counts;                            // the run's array of 64-bit counters
+        StatsLayout lay{};
+    } stats;
+    // The part of the running pairs call that the open runs (depth, stats) take once the call's return code is RSQ_OK: while one is open a call is one part
+    // (pairs_parts), whose fragments and raw arrays still lie in the workspace when the call ends.
+    struct KeptPart {
+        bool have = false;
+        const Fragment *frags = nullptr;
+        const FragmentVar *fvars = nullptr;
+        uint64_t n_pairs = 0;
+        RawLayout raw{};
+        const uint32_t *row_order = nullptr;
+    } kept;
+    bool keeps_part() const { return depth.open || stats.open; }
     // rsq_sim_alleles_fasta (rsq_alleles.h): the records of the alleles' FASTA text, made at the first call (n == 0: not yet; a reference taken in later starts over)
     struct AllelesText {
         DevBuf records;
@@ -1077,7 +1088,7 @@ static uint32_t pairs_parts(const rsq_sim &s, uint32_t n_blocks) {
     // formatter both live on the memory system (gathers in the 24 MB surrounding table; 15 GB of raw arrays and text), so side by side each takes nearly as long
     // as the two in a row, and every part adds a read-kernel tail.  One part unless asked (option overlap = n, tests).
     const int64_t opt = s.opt.overlap;
-    if (s.depth.open) return 1u;                                     // a depth run adds the call's part once its return code is known (depth_take): the part's arrays must still be there
+    if (s.keeps_part()) return 1u;                                   // an open run (depth, stats) takes the call's part once its return code is known (runs_take): the part's arrays must still be there
     return opt > 0 ? (uint32_t)std::min<int64_t>(opt, std::max<uint32_t>(n_blocks, 1u)) : 1u;
 }
 // what rsq_sim_pairs and rsq_sim_job_generate ask of a block range before anything is sized from it
@@ -1103,7 +1114,7 @@ static int sim_pairs(rsq_sim &s, const PairsCall &call, uint32_t block_lo, uint3
     *n_pairs = 0;
     *call.r1.len = *call.r2.len = 0;
     if (call.has_truth()) *call.truth.len = 0;
-    s.depth.have_part = false;
+    s.kept.have = false;
     if (block_lo == block_hi) return RSQ_OK;
     reset_call_timers(s);
     const uint32_t parts = pairs_parts(s, block_hi - block_lo);
@@ -1160,15 +1171,7 @@ static int sim_pairs(rsq_sim &s, const PairsCall &call, uint32_t block_lo, uint3
             }
             text_stage(s, call, part, s_text);
             if (call.has_truth()) sam_stage(s, call, part, s_text);
-            if (s.depth.open) {                                      // (one part: pairs_parts)
-                rsq_sim::Depth &d = s.depth;
-                d.have_part = true;
-                d.frags = part.frags;
-                d.fvars = part.fvars;
-                d.n_pairs = part.n_pairs;
-                d.raw = part.raw;
-                d.row_order = part.row_order;
-            }
+            if (s.keeps_part()) s.kept = rsq_sim::KeptPart{true, part.frags, part.fvars, part.n_pairs, part.raw, part.row_order};      // (one part: pairs_parts)
         } else {                                                     // no pairs in this part: its text ends where it begins
             HIP_CHECK(hipMemcpyAsync(s.totals.as<uint64_t>() + 2 * (k + 1), s.totals.as<uint64_t>() + 2 * k, 16, hipMemcpyDeviceToDevice, s_text));
             if (call.has_truth()) HIP_CHECK(hipMemcpyAsync(s.sam_totals.as<uint64_t>() + k + 1, s.sam_totals.as<uint64_t>() + k, 8, hipMemcpyDeviceToDevice, s_text));
@@ -1191,17 +1194,58 @@ static int sim_pairs(rsq_sim &s, const PairsCall &call, uint32_t block_lo, uint3
     return rc;
 }
 
-// A depth run (rsq_depth.h) takes the pairs of a call that has returned RSQ_OK -- and of no other, so a call repeated after RSQ_ENOSPC counts its pairs once: the
-// call was one part, whose fragments and raw arrays still lie in the workspace.  The stream is idle afterwards (the next call may reuse the arrays on another).
-static void depth_take(rsq_sim &s, hipStream_t st) {
+// The open runs take the pairs of a call that has returned RSQ_OK -- and of no other, so a call repeated after RSQ_ENOSPC counts its pairs once: the call was one
+// part, whose fragments and raw arrays still lie in the workspace (rsq_sim::KeptPart).  The stream is idle afterwards (the next call may reuse the arrays on another).
+static void depth_take(rsq_sim &s, const rsq_sim::KeptPart &k, hipStream_t st) {
     rsq_sim::Depth &d = s.depth;
-    if (!d.have_part || !d.n_pairs) return;
-    d.have_part = false;
-    const dim3 grid((uint32_t)cdiv(2u * d.n_pairs, 256)), block(256);
+    const dim3 grid((uint32_t)cdiv(2u * k.n_pairs, 256)), block(256);
     s.timers["depth_add"].start(st);
-    if (s.has_variants) hipLaunchKernelGGL(k_depth_add<true>, grid, block, 0, st, s.dev, d.frags, d.fvars, d.n_pairs, d.raw, d.row_order, d.diff.as<uint32_t>(), d.bad.as<uint32_t>());
-    else hipLaunchKernelGGL(k_depth_add<false>, grid, block, 0, st, s.dev, d.frags, d.fvars, d.n_pairs, d.raw, d.row_order, d.diff.as<uint32_t>(), d.bad.as<uint32_t>());
+    if (s.has_variants) hipLaunchKernelGGL(k_depth_add<true>, grid, block, 0, st, s.dev, k.frags, k.fvars, k.n_pairs, k.raw, k.row_order, d.diff.as<uint32_t>(), d.bad.as<uint32_t>());
+    else hipLaunchKernelGGL(k_depth_add<false>, grid, block, 0, st, s.dev, k.frags, k.fvars, k.n_pairs, k.raw, k.row_order, d.diff.as<uint32_t>(), d.bad.as<uint32_t>());
     s.timers["depth_add"].stop(st);
+}
+// The rows kernel's geometry (rsq_stats.h StatsRowsPlan): the chunk is the largest multiple of four positions, 64 at the most, whose image and staged words fit
+// 48 KB of LDS -- four workgroups a CU --, evened out over the longer segment's chunks (150 cycles: three chunks of 52, not 64 + 64 + 22); the grid is persistent,
+// four workgroups a CU and never fewer than there are units while that many are resident.  Options stats_chunk, stats_slab and stats_groups replace the three.
+static void stats_take(rsq_sim &s, const rsq_sim::KeptPart &k, hipStream_t st) {
+    const StatsLayout &y = s.stats.lay;
+    uint64_t *counts = s.stats.counts.as<uint64_t>();
+    const bool skew = s.opt.stats_form != 1;
+    constexpr uint32_t kLds = 48u * 1024u;
+    if (2u * k.n_pairs >= (1ull << 32)) throw Error("more than 2^32 reads in one call: a workgroup of the report's kernels counts in 32 bits (use smaller block ranges)");
+    if (y.lmax) {
+        uint32_t chunk = 64u;
+        if (s.opt.stats_chunk > 0) chunk = (uint32_t)std::min<int64_t>((s.opt.stats_chunk + 3) / 4 * 4, 1024);
+        else {
+            while (chunk > 4u && stats_rows_lds_bytes(chunk, y.Q, skew) > kLds) chunk -= 4u;
+            const uint32_t n = stats_chunks(y.lmax, chunk);
+            chunk = std::min(chunk, (cdiv(y.lmax, n) + 3u) / 4u * 4u);
+        }
+        const uint32_t lds = stats_rows_lds_bytes(chunk, y.Q, skew);
+        if (lds > 64u * 1024u) throw Error("the simulation report's image of " + std::to_string(chunk) + " positions does not fit the LDS (option stats_chunk, or a profile with more than 250 quality values)");
+        StatsRowsPlan plan{chunk, s.opt.stats_slab > 0 ? (uint32_t)std::min<int64_t>(s.opt.stats_slab, 1 << 30) : 1024u, {stats_chunks(y.len[0], chunk), stats_chunks(y.len[1], chunk)}, s.read_stride / 4u};
+        const uint32_t units = plan.units[0] + plan.units[1];
+        uint32_t groups = s.opt.stats_groups > 0 ? (uint32_t)std::min<int64_t>(s.opt.stats_groups, 1 << 16) : std::max(4u * s.n_cu, std::min(units, 8u * s.n_cu));
+        if (!(s.opt.stats_groups > 0)) groups = (uint32_t)std::min<uint64_t>(groups, (uint64_t)units * std::max<uint64_t>(cdiv(k.n_pairs, plan.slab), 1u));      // (no workgroup without a slab)
+        if (units) {
+            s.timers["stats_rows"].start(st);
+            if (skew) hipLaunchKernelGGL(k_stats_rows<true>, dim3(groups), dim3(kStatsRowsBlock), lds, st, k.raw.seq, k.raw.qual, k.raw.meta, k.raw.pitch, k.n_pairs, y, plan, counts);
+            else hipLaunchKernelGGL(k_stats_rows<false>, dim3(groups), dim3(kStatsRowsBlock), lds, st, k.raw.seq, k.raw.qual, k.raw.meta, k.raw.pitch, k.n_pairs, y, plan, counts);
+            s.timers["stats_rows"].stop(st);
+        }
+    }
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(cdiv(2u * k.n_pairs, kStatsMatesBlock), s.opt.stats_groups > 0 ? (uint64_t)s.opt.stats_groups : 4ull * s.n_cu);
+    s.timers["stats_mates"].start(st);
+    if (s.has_variants) hipLaunchKernelGGL(k_stats_mates<true>, dim3(grid), dim3(kStatsMatesBlock), y.image_words * 4u, st, s.dev, k.frags, k.fvars, k.n_pairs, k.raw, k.row_order, y, counts);
+    else hipLaunchKernelGGL(k_stats_mates<false>, dim3(grid), dim3(kStatsMatesBlock), y.image_words * 4u, st, s.dev, k.frags, k.fvars, k.n_pairs, k.raw, k.row_order, y, counts);
+    s.timers["stats_mates"].stop(st);
+}
+static void runs_take(rsq_sim &s, hipStream_t st) {
+    rsq_sim::KeptPart &k = s.kept;
+    if (!k.have || !k.n_pairs) return;
+    k.have = false;
+    if (s.depth.open) depth_take(s, k, st);
+    if (s.stats.open) stats_take(s, k, st);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(st));
 }
@@ -1212,6 +1256,10 @@ static bool depth_refusal(const rsq_sim &s) {
     return true;
 }
 static bool depth_refuses_job(const rsq_sim &s, const char *call) {
+    if (s.stats.open) {
+        g_last_error = std::string(call) + ": a stats run is open (rsq_sim_stats_begin); the job calls are not counted in the simulation report";
+        return true;
+    }
     if (!s.depth.open) return false;
     g_last_error = std::string(call) + ": a depth run is open (rsq_sim_depth_begin); the job calls do not accumulate depth";
     return true;
@@ -2328,7 +2376,7 @@ int rsq_sim_depth_begin(rsq_sim *s) {
         HIP_CHECK(hipMemset(d.diff.as<void>(), 0, d.words * 4u));
         HIP_CHECK(hipMemset(d.bad.as<void>(), 0, 8));
         d.open = true;
-        d.finished = d.have_part = false;
+        d.finished = false;
         d.bg_seq = 0xFFFFFFFFu;
         return (int)RSQ_OK;
     });
@@ -2454,8 +2502,82 @@ int rsq_sim_depth_end(rsq_sim *s) {
         HIP_CHECK(hipSetDevice(s->device));
         rsq_sim::Depth &d = s->depth;
         for (DevBuf *b : {&d.diff, &d.bad, &d.tile_sums, &d.flags, &d.rank, &d.ends, &d.sizes, &d.offsets}) b->release();
-        d.open = d.finished = d.have_part = false;
+        d.open = d.finished = false;
         d.words = 0;
+        return (int)RSQ_OK;
+    });
+}
+
+// ---- simulation report (rsq_stats.h; include/reseq_amd.h rsq_sim_stats_*)
+static_assert(RSQ_STATS_PAIRS == kStPairs && RSQ_STATS_STRAND == kStStrand && RSQ_STATS_TILE == kStTile && RSQ_STATS_FRAGMENT_LENGTH == kStFragmentLength &&
+                  RSQ_STATS_READ_LENGTH == kStReadLength && RSQ_STATS_ERRORS_PER_READ == kStErrorsPerRead && RSQ_STATS_BASE_QUALITY == kStBaseQuality &&
+                  RSQ_STATS_BASE_CALL == kStBaseCall && RSQ_STATS_INSERTION == kStInsertion && RSQ_STATS_DELETION == kStDeletion && RSQ_STATS_ADAPTER == kStAdapter &&
+                  RSQ_STATS_TAIL == kStTail && RSQ_STATS_MISMATCH == kStMismatch && RSQ_STATS_BAD == kStBad && RSQ_STATS_COUNT == kStTables,
+              "the ABI's table ids are rsq_stats.h's");
+// Q: one more than the largest quality value the profile's quality tables can draw (their outcome values)
+static uint32_t stats_quality_values(const rsq_sim &s) {
+    uint32_t top = 0;
+    for (const HostTable &t : s.prof.quality)
+        for (const uint32_t v : t.par0) top = std::max(top, v);
+    return top + 1u;
+}
+int rsq_sim_stats_begin(rsq_sim *s) {
+    REQUIRE(s, "null argument");
+    REQUIRE_STATE(s->prepared && s->has_ref, "rsq_sim_prepare with a reference must run before rsq_sim_stats_begin");
+    REQUIRE_STATE(!s->stats.open, "rsq_sim_stats_begin: a stats run is open already (rsq_sim_stats_end ends it)");
+    return guard([&] {
+        HIP_CHECK(hipSetDevice(s->device));
+        rsq_sim::Stats &t = s->stats;
+        const uint32_t Q = stats_quality_values(*s);
+        if (Q > 256u) throw Error("the simulation report: quality values beyond 255 do not fit a character");
+        t.lay = stats_layout(s->dev.read_lengths[0].to, s->dev.read_lengths[1].to, s->dev.insert_to, Q, s->dev.n_tiles, s->dev.phred_offset);
+        if ((uint64_t)t.lay.image_words * 4u > kStatsMatesLds) throw Error("the simulation report: the per-cycle tables of reads this long do not fit the LDS");
+        t.counts.reserve((size_t)t.lay.words * 8u + 16u);
+        HIP_CHECK(hipMemset(t.counts.as<void>(), 0, (size_t)t.lay.words * 8u));
+        t.open = true;
+        return (int)RSQ_OK;
+    });
+}
+int rsq_sim_stats_layout(const rsq_sim *s, rsq_stats_layout *layout) {
+    REQUIRE(s && layout, "null argument");
+    REQUIRE_STATE(s->stats.open, "rsq_sim_stats_layout: no stats run is open (rsq_sim_stats_begin)");
+    const StatsLayout &y = s->stats.lay;
+    *layout = rsq_stats_layout{};
+    layout->words = y.words;
+    layout->read_length[0] = y.len[0];
+    layout->read_length[1] = y.len[1];
+    layout->insert_to = y.F;
+    layout->n_quality = y.Q;
+    layout->n_tiles = y.T;
+    layout->phred_offset = y.phred;
+    for (uint32_t t = 0; t < kStTables; ++t) layout->table[t] = rsq_stats_table{y.off[t], y.segments(t), t == kStBaseQuality || t == kStBaseCall ? 2u : 1u, {y.dim0(t), y.dim1(t)}};
+    return RSQ_OK;
+}
+int rsq_sim_stats_counts(rsq_sim *s, uint64_t *host, size_t cap_words, void *stream) {
+    REQUIRE(s && host, "null argument");
+    REQUIRE_STATE(s->stats.open, "rsq_sim_stats_counts: no stats run is open (rsq_sim_stats_begin)");
+    const StatsLayout &y = s->stats.lay;
+    if (cap_words < y.words) {
+        g_last_error = "stats buffer too small: need " + std::to_string(y.words) + " words";
+        return RSQ_ENOSPC;
+    }
+    return guard([&] {
+        HIP_CHECK(hipSetDevice(s->device));
+        const hipStream_t st = (hipStream_t)stream;
+        HIP_CHECK(hipMemcpyAsync(host, s->stats.counts.as<uint64_t>(), (size_t)y.words * 8u, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        g_last_warning.clear();
+        if (host[y.off[kStBad]])
+            g_last_warning = "simulation report: " + std::to_string(host[y.off[kStBad]]) + " values were out of range (a quality, a base code, or a CIGAR element outside its read) and are counted under RSQ_STATS_BAD only";
+        return (int)RSQ_OK;
+    });
+}
+int rsq_sim_stats_end(rsq_sim *s) {
+    REQUIRE(s, "null argument");
+    return guard([&] {
+        HIP_CHECK(hipSetDevice(s->device));
+        s->stats.counts.release();
+        s->stats.open = false;
         return (int)RSQ_OK;
     });
 }
@@ -2467,7 +2589,7 @@ static int pairs_call(rsq_sim *s, const PairsCall &call, uint32_t block_lo, uint
     if (depth_refusal(*s)) return RSQ_ESTATE;
     return guard([&] {
         const int rc = sim_pairs(*s, call, block_lo, block_hi, n_pairs);
-        if (rc == RSQ_OK && s->depth.open) depth_take(*s, call.st);
+        if (rc == RSQ_OK && s->keeps_part()) runs_take(*s, call.st);
         return rc;
     });
 }
@@ -2548,7 +2670,7 @@ int rsq_sim_pairs_bam_sorted(rsq_sim *s, uint32_t block_lo, uint32_t block_hi, c
         const uint64_t cut = bam_cut_key(block_hi, s->total_blocks, s->dev.n_seqs, s->block_seq.data(), s->first_block.data(), kBlockSize);
         const int end = sorted_finish(*s, call, rc, cut, block_hi);
         *n_records = b.call_records;
-        if (end == RSQ_OK && s->depth.open) depth_take(*s, st);         // (the run's state has moved on: the call will not be repeated)
+        if (end == RSQ_OK && s->keeps_part()) runs_take(*s, st);        // (the run's state has moved on: the call will not be repeated)
         return end;
     });
 }
