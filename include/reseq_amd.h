@@ -559,6 +559,46 @@ int rsq_sim_stats_layout(const rsq_sim *s, rsq_stats_layout *layout);
 int rsq_sim_stats_counts(rsq_sim *s, uint64_t *host, size_t cap_words, void *stream);
 int rsq_sim_stats_end(rsq_sim *s);
 
+/* Truth pileup: per reference position the depth, the called bases, the deleted columns and the insertions of the simulated reads, optionally per strand,
+ * accumulated on the device while the pairs are simulated (reseq_amd/csrc/rsq_pileup.h; DESIGN.md 4.8 "Truth pileup"), as counts or as TSV text.
+ *   The rule.  Coordinates and reference are MD:Z's: reference positions (with variants the reference-coordinate records of rsq_sim_truth_variants, whatever
+ * coordinates the truth calls write), the reference base is copy 0 of the reference as loaded, never an allele.  Only MAPPED truth records count; a record's
+ * strand is its FLAG 0x10.  With r = POS - 1 and q = 0, over the CIGAR as the record writes it: nM: per column depth[r] += 1 and base[SEQ[q]][r] += 1 (SEQ as
+ * written; a read base N goes to the N counter), ++r, ++q; nD: del[r .. r + n) += 1, r += n (the D runs dropped at either end are not in the CIGAR); nI:
+ * ins[max(r, 1) - 1] += 1, ONE count per element at the base in front of the insertion (position 0 where there is none; a leading I stands at POS - 2, which need
+ * not be covered), q += n; nS: q += n.  depth is exactly what a depth run counts for the same pairs.  Every count is a sum of ones: the result does not depend on
+ * how blocks are cut into calls, nor on any option.
+ *   A row is RSQ_PILEUP_COLUMNS uint32: depth, A, C, G, T, N, del, ins.  An unstranded run has one row per position; a run begun with RSQ_PILEUP_STRANDS has two,
+ * the records without 0x10 and then those with it, whose sum is the unstranded row.
+ *   rsq_sim_pileup_begin opens a run: zeroed device arrays of 32 bytes per reference base (64 per strand) and as much per sequence; when the allocation fails the
+ * error names the bytes needed.  After rsq_sim_prepare with a reference, else RSQ_ESTATE; RSQ_ESTATE while a run is open; RSQ_EINVAL while rsq_sim_truth_alleles
+ * is on (rsq_sim_truth_alleles(s, 1) returns RSQ_ESTATE while a run is open) and for unknown flags.
+ *   While a run is open, rsq_sim_pairs, rsq_sim_pairs_sam, rsq_sim_pairs_bam and rsq_sim_pairs_bam_sorted add their pairs to it if and only if they return RSQ_OK:
+ * a call repeated after RSQ_ENOSPC counts its pairs once.  Which of the four is called does not matter, and the texts they write are what they write without a
+ * run.  Such a call runs as one part whatever option overlap says.  The adapter-only calls and the seqToIllumina calls add nothing.  rsq_sim_job_generate,
+ * _write, _compress and _read return RSQ_ESTATE while a run is open.  A depth run and a stats run may be open at the same time; the three are independent.
+ *   rsq_sim_pileup_finish turns the depth differences into depths.  Afterwards the pairs calls return RSQ_ESTATE until rsq_sim_pileup_end.  RSQ_EINVAL if an
+ * alignment lay outside its sequence (the records' rules exclude it).
+ *   rsq_sim_pileup_counts (after finish, else RSQ_ESTATE): the rows of positions [lo, hi) of sequence seq into rows_dev, [hi - lo][S][RSQ_PILEUP_COLUMNS] with S
+ * the strand sets (1 or 2), any window in any order; RSQ_EINVAL for a bad seq, lo > hi or hi beyond the sequence.
+ *   rsq_sim_pileup_text (after finish): TSV text of positions [lo, hi), a line "<name>\t<pos, 1-based>\t<ref letter>" and per strand set
+ * "\t<depth>\t<A>\t<C>\t<G>\t<T>\t<N>\t<del>\t<ins>", then "\n"; <name> is the RNAME of rsq_ref_sam_header.  By default a position has a line if any value other than
+ * the depth and the reference letter's own count is non-zero (the sites); with RSQ_PILEUP_ALL, if any value at all is.  Rows are independent: pieces may be asked
+ * for in any order and at any alignment, and the concatenation of any cut of [0, length) is the whole text.  *len = the piece's bytes, *n_lines its lines.
+ * RSQ_ENOSPC (cap < *len, or dst_dev NULL while there is text): nothing is written, the call can be repeated.
+ *   rsq_sim_pileup_end frees the run's memory (RSQ_OK without a run as well); a new run may begin.
+ * Kernel times: "pileup_add" (one launch per pairs call that had pairs), "pileup_scan" (finish, once per strand set), "pileup_rows" (counts), "pileup_lines" and
+ * "pileup_text" (text).  With no run open no call launches any of them, and every other call is, launch for launch and byte for byte, what it is without these
+ * entry points. */
+#define RSQ_PILEUP_COLUMNS 8u
+#define RSQ_PILEUP_STRANDS 1u   /* rsq_sim_pileup_begin: per strand */
+#define RSQ_PILEUP_ALL 1u       /* rsq_sim_pileup_text: every non-zero row */
+int rsq_sim_pileup_begin(rsq_sim *s, uint32_t flags);
+int rsq_sim_pileup_finish(rsq_sim *s, void *stream);
+int rsq_sim_pileup_counts(rsq_sim *s, uint32_t seq, uint64_t lo, uint64_t hi, uint32_t *rows_dev, void *stream);
+int rsq_sim_pileup_text(rsq_sim *s, uint32_t seq, uint64_t lo, uint64_t hi, uint32_t flags, char *dst_dev, size_t cap, size_t *len, uint64_t *n_lines, void *stream);
+int rsq_sim_pileup_end(rsq_sim *s);
+
 /* Simulator::ApplyErrorsAndQualityToFastaInput with the FASTA header already parsed (reseq/Simulator.cpp:2403-2512):
  * n records of `read_len` template bases each.  Inputs (device): seqs[n][read_len] base codes 0..3, seg[n] template
  * segment 0/1, frag_len[n], dom[n][read_len] dominant-error base codes 0..4, rate[n][read_len] error percent.

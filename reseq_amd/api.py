@@ -122,6 +122,11 @@ SYMBOLS = {
     "rsq_sim_depth_counts": (C.c_int, [_vp, _u32, _u64, _u64, _vp, _vp]),
     "rsq_sim_depth_bedgraph": (C.c_int, [_vp, _u32, _u64, _u64, _vp, _sz, _psz, C.POINTER(_u64), _vp]),
     "rsq_sim_depth_end": (C.c_int, [_vp]),
+    "rsq_sim_pileup_begin": (C.c_int, [_vp, _u32]),
+    "rsq_sim_pileup_finish": (C.c_int, [_vp, _vp]),
+    "rsq_sim_pileup_counts": (C.c_int, [_vp, _u32, _u64, _u64, _vp, _vp]),
+    "rsq_sim_pileup_text": (C.c_int, [_vp, _u32, _u64, _u64, _u32, _vp, _sz, _psz, C.POINTER(_u64), _vp]),
+    "rsq_sim_pileup_end": (C.c_int, [_vp]),
     "rsq_sim_stats_begin": (C.c_int, [_vp]),
     "rsq_sim_stats_layout": (C.c_int, [_vp, _vp]),
     "rsq_sim_stats_counts": (C.c_int, [_vp, _vp, _sz, _vp]),
@@ -163,6 +168,10 @@ _lib = None
 # the tables of the simulation report by id (RSQ_STATS_* of include/reseq_amd.h)
 STATS_TABLES = ("pairs", "strand", "tile", "fragment_length", "read_length", "errors_per_read", "base_quality", "base_call", "insertion", "deletion", "adapter", "tail",
                 "mismatch", "bad")
+# the truth pileup: a row's columns, and the flags of rsq_sim_pileup_begin and rsq_sim_pileup_text (RSQ_PILEUP_* of include/reseq_amd.h)
+PILEUP_NAMES = ("depth", "A", "C", "G", "T", "N", "del", "ins")
+PILEUP_COLUMNS = len(PILEUP_NAMES)
+RSQ_PILEUP_STRANDS, RSQ_PILEUP_ALL = 1, 1
 
 
 class StatsTable(C.Structure):
@@ -733,6 +742,66 @@ class Simulator:
                             dst.free()
                         dst = DeviceArray(self.device, n + n // 4 + 64)
                         n, _, rc = self.depth_bedgraph_device(seq, lo, hi, dst)
+                    _check(rc)
+                    if n:
+                        out.append(dst.to_numpy(np.uint8, n).tobytes())
+            return b"".join(out)
+        finally:
+            if dst is not None:
+                dst.free()
+
+    def pileup_begin(self, strands=False):
+        """rsq_sim_pileup_begin: opens a pileup run (strands: a row per strand, forward then reverse); every pairs call that returns RSQ_OK adds the columns of its
+        mapped truth records to it"""
+        _check(lib().rsq_sim_pileup_begin(self.h, RSQ_PILEUP_STRANDS if strands else 0))
+        self._pileup_sets = 2 if strands else 1
+
+    def pileup_finish(self, stream=None):
+        """rsq_sim_pileup_finish: the depth differences become depths; pileup() and pileup_text() read the run, the pairs calls are refused until pileup_end()"""
+        _check(lib().rsq_sim_pileup_finish(self.h, stream))
+
+    def pileup_end(self):
+        """rsq_sim_pileup_end: frees the run's memory; a new run may begin"""
+        _check(lib().rsq_sim_pileup_end(self.h))
+
+    def pileup_counts_device(self, seq, lo, hi, rows_dev, stream=None):
+        """rsq_sim_pileup_counts: the rows [hi - lo][S][8] of [lo, hi) of sequence seq to rows_dev, a DeviceArray or an address in device memory; returns the return
+        code"""
+        return lib().rsq_sim_pileup_counts(self.h, seq, lo, hi, rows_dev.ptr if isinstance(rows_dev, DeviceArray) else rows_dev, stream)
+
+    def pileup(self, seq, lo=0, hi=None):
+        """the rows of positions [lo, hi) of sequence seq (hi None: up to its end) as a numpy uint32 array [n, S, 8]: depth, A, C, G, T, N, del, ins per strand set"""
+        hi = self.sequence_lengths()[seq] if hi is None else hi
+        sets = getattr(self, "_pileup_sets", 1)
+        n = max(hi - lo, 0)
+        dst = DeviceArray(self.device, max(4 * PILEUP_COLUMNS * sets * n, 16))
+        try:
+            _check(self.pileup_counts_device(seq, lo, hi, dst))
+            return dst.to_numpy(np.uint32, n * sets * PILEUP_COLUMNS).reshape(n, sets, PILEUP_COLUMNS)
+        finally:
+            dst.free()
+
+    def pileup_text_device(self, seq, lo, hi, dst, all_rows=False, stream=None):
+        """rsq_sim_pileup_text into a caller-owned DeviceArray (None: only the sizes): the lines of positions [lo, hi) of sequence seq, the sites or (all_rows) every
+        non-zero row.  Returns (len, n_lines, rc)."""
+        n, lines = C.c_size_t(), C.c_uint64()
+        rc = lib().rsq_sim_pileup_text(self.h, seq, lo, hi, RSQ_PILEUP_ALL if all_rows else 0, dst.ptr if dst else None, dst.nbytes if dst else 0, C.byref(n), C.byref(lines), stream)
+        return n.value, lines.value, rc
+
+    def pileup_text(self, all_rows=False, piece=1 << 22, seqs=None):
+        """the TSV text of the whole reference (seqs: of these sequences) as bytes, without a header line, fetched in pieces of `piece` positions"""
+        lengths = self.sequence_lengths()
+        out, dst = [], None
+        try:
+            for seq in (range(len(lengths)) if seqs is None else seqs):
+                for lo in range(0, int(lengths[seq]), piece):
+                    hi = min(lo + piece, int(lengths[seq]))
+                    n, _, rc = self.pileup_text_device(seq, lo, hi, dst, all_rows)
+                    if rc == RSQ_ENOSPC:                            # (nothing was written: the same piece again, with room)
+                        if dst is not None:
+                            dst.free()
+                        dst = DeviceArray(self.device, n + n // 4 + 64)
+                        n, _, rc = self.pileup_text_device(seq, lo, hi, dst, all_rows)
                     _check(rc)
                     if n:
                         out.append(dst.to_numpy(np.uint8, n).tobytes())

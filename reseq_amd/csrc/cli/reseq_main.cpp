@@ -66,7 +66,7 @@ const std::map<std::string, std::string> kShort = {{"-j", "threads"}, {"-h", "he
                                                    {"-v", "vcfIn"},   {"-p", "probabilitiesIn"}, {"-P", "probabilitiesOut"}, {"-1", "firstReadsOut"},
                                                    {"-2", "secondReadsOut"}, {"-c", "coverage"}, {"-R", "refSim"}, {"-V", "vcfSim"}, {"-i", "input"}, {"-o", "output"}};
 const std::set<std::string> kFlags = {"help", "version", "noBias", "noTiles", "statsOnly", "tiles", "stopAfterEstimation", "noInDelErrors", "noSubstitutionErrors", "maxLenDeletion", "maxReadLength",
-                                      "dumpArchiveLayout", "traceStages", "hostGzip", "truthBamSort", "truthVariants", "truthMD", "truthAlleles"};
+                                      "dumpArchiveLayout", "traceStages", "hostGzip", "truthBamSort", "truthVariants", "truthMD", "truthAlleles", "truthPileupStrands", "truthPileupAll"};
 
 bool parse(int argc, char **argv, int first, Args &a) {
     for (int i = first; i < argc; ++i) {
@@ -507,6 +507,71 @@ bool write_depth(rsq_sim *sim, const rsq_ref *ref, int device, const std::string
     return ok;
 }
 
+// --truthPileup pileup.tsv[.gz]: the per-position base counts of the simulated reads (rsq_sim_pileup_*): one header line written here, then the text made on the
+// device, fetched after the last batch in pieces of a bounded number of positions; .gz as write_depth.  A failure leaves no file.
+bool write_pileup(rsq_sim *sim, const rsq_ref *ref, int device, const std::string &path, bool strands, bool all_rows) {
+    constexpr uint64_t kPiece = 4ull << 20;                      // positions: at most a line each
+    const bool gz = rsq::textio::has_suffix(path, ".gz");
+    INFO("Writing the truth pileup to " << path);
+    uint64_t at_file = 0;
+    uint32_t n_seqs = 0;
+    bool ok = check(rsq_sim_pileup_finish(sim, nullptr), "--truthPileup") && check(rsq_ref_num_sequences(ref, &n_seqs), "--truthPileup");
+    if (ok) {
+        const int fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (fd < 0) {
+            ERR("Could not open '" << path << "' for writing.");
+            return false;
+        }
+        ::close(fd);
+    }
+    DevBuffer text, packed;
+    text.device = packed.device = device;
+    auto put = [&](size_t n) {                                   // n bytes of text.p
+        const void *src = text.p;
+        if (gz) {
+            ok = packed.ensure(rsq_gzip_bound(n)) && check(rsq_sim_gzip_device(sim, (const char *)text.p, n, (char *)packed.p, packed.cap, &n, nullptr), "Compressing the truth pileup failed");
+            src = packed.p;
+        }
+        ok = ok && check(rsq_dev_pwrite(device, src, n, path.c_str(), at_file), "Writing the truth pileup failed");
+        at_file += n;
+    };
+    if (ok) {
+        std::string header = "#chrom\tpos\tref";
+        for (const char *strand : {strands ? "+" : "", strands ? "-" : nullptr}) {
+            if (!strand) continue;
+            for (const char *name : {"depth", "A", "C", "G", "T", "N", "del", "ins"}) header += std::string("\t") + name + strand;
+        }
+        header += "\n";
+        ok = text.ensure(header.size() + 4096) && check(rsq_dev_upload(device, text.p, header.data(), header.size()), "--truthPileup");
+        if (ok) put(header.size());
+    }
+    for (uint32_t seq = 0; ok && seq < n_seqs; ++seq) {
+        uint32_t length = 0;
+        ok = check(rsq_ref_sequence_length(ref, seq, &length), "--truthPileup");
+        for (uint64_t lo = 0; ok && lo < length; lo += kPiece) {
+            const uint64_t hi = std::min<uint64_t>(length, lo + kPiece);
+            size_t n = 0;
+            uint64_t lines = 0;
+            const uint32_t flags = all_rows ? RSQ_PILEUP_ALL : 0u;
+            int rc = rsq_sim_pileup_text(sim, seq, lo, hi, flags, (char *)text.p, text.cap, &n, &lines, nullptr);
+            if (rc == RSQ_ENOSPC && text.ensure(n + n / 8 + 4096)) rc = rsq_sim_pileup_text(sim, seq, lo, hi, flags, (char *)text.p, text.cap, &n, &lines, nullptr);
+            ok = check(rc, "--truthPileup");
+            if (ok && n) put(n);
+        }
+    }
+    if (ok && gz) {
+        char eof[32];
+        const size_t n = rsq_gzip_eof_member(eof, sizeof eof);
+        const int fd = ::open(path.c_str(), O_WRONLY);
+        ok = fd >= 0 && pwrite(fd, eof, n, (off_t)at_file) == (ssize_t)n;
+        if (fd >= 0) ::close(fd);
+        if (!ok) ERR("Writing the truth pileup failed");
+    }
+    rsq_sim_pileup_end(sim);
+    if (!ok) remove(path.c_str());
+    return ok;
+}
+
 // --simStats report.tsv[.gz]: the simulation report (rsq_sim_stats_*), formatted here -- it is small --: "#reseq_amd simStats v1", '#' lines with the dimensions and
 // the quality offset, then one line per non-zero counter "table<TAB>segment<TAB>i<TAB>j<TAB>count" ('.' where an index does not apply), tables by id, indices
 // ascending.  .gz: one gzip member (zlib).  A failure leaves no file.
@@ -929,6 +994,38 @@ int illumina_pe(const Args &a) {
                 return 1;
             }
     }
+    // --truthPileup: per-position base counts of the same records (rsq_sim_pileup_*)
+    const std::string pileup_out = a.get("truthPileup", "");
+    if (a.has("truthPileup")) {
+        if (pileup_out.empty()) {
+            ERR("--truthPileup needs a file name");
+            return 1;
+        }
+        if (rsq::textio::has_suffix(pileup_out, ".bz2")) {
+            ERR("--truthPileup: bzip2 output is not supported (write .gz or plain text)");
+            return 1;
+        }
+        if (a.has("truthAlleles")) {
+            ERR("--truthPileup: the pileup is in reference coordinates; it is not offered beside --truthAlleles");
+            return 1;
+        }
+        if (truths.size() == 2) {
+            ERR("--truthPileup: a batch is simulated once for each of --truthSam and --truthBam and would be counted twice; give at most one of them beside --truthPileup");
+            return 1;
+        }
+        if (pileup_out == depth_out || pileup_out == stats_out) {
+            ERR("--truthPileup and " << (pileup_out == depth_out ? "--truthDepth" : "--simStats") << " name the same file");
+            return 1;
+        }
+        for (const TruthOut &t : truths)
+            if (t.path == pileup_out) {
+                ERR("--truthPileup and " << t.option << " name the same file");
+                return 1;
+            }
+    } else if (a.has("truthPileupStrands") || a.has("truthPileupAll")) {
+        ERR((a.has("truthPileupStrands") ? "--truthPileupStrands" : "--truthPileupAll") << " shapes the file of --truthPileup: give --truthPileup pileup.tsv as well");
+        return 1;
+    }
     const char *truth_option = any_truth ? truths.front().option : "";
     const std::string alleles_out = a.get("writeAlleles", "");
     if (a.has("writeAlleles") && alleles_out.empty()) {
@@ -979,6 +1076,15 @@ int illumina_pe(const Args &a) {
                 ok = false;
             } else {
                 WARN("-j: the truth depth (--truthDepth) is accumulated by one worker only; one worker runs");
+                n_workers = 1;
+            }
+        }
+        if (ok && n_workers > 1 && !pileup_out.empty()) {
+            if (a.has("gpus")) {
+                ERR("--truthPileup: the truth pileup is accumulated by one worker only (run without --gpus, or with --gpus 1)");
+                ok = false;
+            } else {
+                WARN("-j: the truth pileup (--truthPileup) is accumulated by one worker only; one worker runs");
                 n_workers = 1;
             }
         }
@@ -1067,6 +1173,7 @@ int illumina_pe(const Args &a) {
     }
     if (ok && !sys_read.empty()) ok = check(rsq_sim_read_sys_errors(sim, sys_read.c_str()), "Could not read systematic error profile");
     if (ok && !depth_out.empty()) ok = check(rsq_sim_depth_begin(sim), "--truthDepth");      // every batch's pairs count once, whichever call simulates them
+    if (ok && !pileup_out.empty()) ok = check(rsq_sim_pileup_begin(sim, a.has("truthPileupStrands") ? RSQ_PILEUP_STRANDS : 0u), "--truthPileup");
     // --simStats: one run over all batches -- a batch repeated after RSQ_ENOSPC counts once (rsq_sim_stats_begin).  With both --truthSam and --truthBam a batch is
     // simulated once for each: then a run is open only around the batch's first call and its counters are added up here, so that every batch counts once.
     rsq_stats_layout stats_lay{};
@@ -1091,7 +1198,7 @@ int illumina_pe(const Args &a) {
     int64_t host_gzip = 0;
     rsq_get_option("host_gzip", &host_gzip);
     const bool gz1 = !host_gzip && rsq::textio::has_suffix(out1, ".gz"), gz2 = !host_gzip && rsq::textio::has_suffix(out2, ".gz");
-    bool truth_gz = rsq::textio::has_suffix(depth_out, ".gz");     // (text of another kind than FASTQ: no Huffman code is kept over the calls)
+    bool truth_gz = rsq::textio::has_suffix(depth_out, ".gz") || rsq::textio::has_suffix(pileup_out, ".gz");     // (text of another kind than FASTQ: no Huffman code is kept over the calls)
     for (TruthOut &t : truths) {
         t.gz = t.bam || (!host_gzip && rsq::textio::has_suffix(t.path, ".gz"));
         t.text.device = t.packed.device = (int)device;
@@ -1229,6 +1336,7 @@ int illumina_pe(const Args &a) {
                   "Simulation of adapter-only pairs failed", n);
         }
         if (ok && !depth_out.empty()) ok = write_depth(sim, ref, (int)device, depth_out);
+        if (ok && !pileup_out.empty()) ok = write_pileup(sim, ref, (int)device, pileup_out, a.has("truthPileupStrands"), a.has("truthPileupAll"));
         if (ok && !stats_out.empty()) {
             if (!stats_per_batch) ok = stats_collect();
             rsq_sim_stats_end(sim);
@@ -1500,6 +1608,7 @@ const char *kUsage =
     "                 \t--truthAlleles: with -V, --truthSam / --truthBam write their records in ALLELE coordinates: against the sequences of --writeAlleles (RNAME <name>_allele<a>, the plain CIGAR, tag XI:i; not with --truthVariants, --truthMD, --truthBamSort)\n"
     "                 \t--truthDepth depth.bedgraph[.gz]: the per-base coverage of the simulated reads (the M columns of the mapped truth records, as `samtools depth` counts them) accumulated on the device and written after the last batch as bedGraph, one line per run of equal depth, zero runs included; with or without --truthSam / --truthBam (at most one of them), with -V in reference coordinates; not with --truthAlleles; one worker\n"
     "                 \t--simStats report.tsv[.gz]: the simulation report -- exact per-cycle histograms of the simulated reads (quality and base call by cycle, read and fragment lengths, errors per read, insertions, deletions, adapter and tail bases and mismatches to the reference by cycle, pairs, strands, tiles), counted on the device while the reads are made and written after the last batch as '#' lines with the dimensions and one line table<TAB>segment<TAB>i<TAB>j<TAB>count per non-zero counter; with or without any --truth* option; one worker\n"
+    "                 \t--truthPileup pileup.tsv[.gz] [--truthPileupStrands] [--truthPileupAll]: per reference position the depth, the called bases A C G T N, the deleted columns and the insertions of the mapped truth records, accumulated on the device and written after the last batch as tab-separated text behind one header line; by default the positions where a read differs from the reference (a call other than the reference base, N, del or ins), with --truthPileupAll every position with a count; --truthPileupStrands: the eight counts per strand (+ then -); with or without --truthSam / --truthBam (at most one of them), beside --truthDepth and --simStats, with -V in reference coordinates; not with --truthAlleles; one worker\n"
     "                 \t--truthBam truth.bam: the same records as BAM (BGZF blocks made on the device; unsorted, no index; may be given beside --truthSam; with -V only with --truthVariants or --truthAlleles; not with --hostGzip, one worker)\n"
     "                 \t--truthBamSort: with --truthBam, the records sorted by coordinate on the device (@HD SO:coordinate) and the index truth.bam.bai beside the file\n"
     "                 \t--truthVariants: with -V, --truthSam / --truthBam [--truthBamSort] write their records in reference coordinates (inserted bases as I, deleted ones as D, tag XI:i)\n"

@@ -74,6 +74,17 @@ template <class Out>
 RSQ_HD auto md_note_mismatch(Out &o, uint32_t q, int) -> decltype(o.mismatch(q), void()) { o.mismatch(q); }
 template <class Out>
 RSQ_HD void md_note_mismatch(Out &, uint32_t, long) {}
+// A sink that wants the columns themselves (rsq_pileup.h) has two members more, found the same way: column_run(op, p, n) for every merged run before it is taken
+// -- op 0 M, 1 a kept D run, 2 I (p means nothing), 3 a D run dropped at either end --, and mismatch_base(p, code) with the reference position of a mismatch and
+// the read's base as written (0..3 ACGT, 4 N).
+template <class Out>
+RSQ_HD auto md_note_run(Out &o, uint32_t op, uint32_t p, uint32_t n, int) -> decltype(o.column_run(op, p, n), void()) { o.column_run(op, p, n); }
+template <class Out>
+RSQ_HD void md_note_run(Out &, uint32_t, uint32_t, uint32_t, long) {}
+template <class Out>
+RSQ_HD auto md_note_base(Out &o, uint32_t p, uint32_t n_bit, uint32_t code, int) -> decltype(o.mismatch_base(p, code), void()) { o.mismatch_base(p, n_bit ? 4u : code); }
+template <class Out>
+RSQ_HD void md_note_base(Out &, uint32_t, uint32_t, uint32_t, long) {}
 
 // The visitor of a mate's columns in ascending reference order (op: 0 M, 1 D, 2 I; p: the reference position of the first of `count` M or D columns): the MD
 // string into `o` (num, ch, bytes, element: any sink of rsq_text.h / rsq_format.h, or MdCount), NM in nm.  q: the column's place in SEQ as written.
@@ -102,6 +113,7 @@ struct MdCols {
                 const uint32_t i = lowest_set_bit64(mm) >> 1;
                 o.element((char)md_ref_letter((uint32_t)(r >> (2u * i)) & 3u), run + i - done);
                 md_note_mismatch(o, q + i, 0);
+                md_note_base(o, p + i, (uint32_t)(s.n >> (2u * i)) & 1u, (uint32_t)(s.codes >> (2u * i)) & 3u, 0);
                 run = 0;
                 done = i + 1u;
                 ++nm;
@@ -130,6 +142,7 @@ struct MdCols {
     }
     RSQ_HD void take(bool last) {
         if (!cn) return;
+        md_note_run(o, cur == 1u && !(any && !last) ? 3u : cur, cp, cn, 0);
         if (cur == 0u) compare(cp, cn);
         else if (cur == 2u) {
             nm += cn;

@@ -33,6 +33,7 @@
 #include "rsq_md.h"
 #include "rsq_bamsort.h"
 #include "rsq_depth.h"
+#include "rsq_pileup.h"
 #include "rsq_stats.h"
 #include "rsq_alleles.h"
 #include "rsq_pack.h"
@@ -314,7 +315,15 @@ struct rsq_sim : PrepassSim {
         DevBuf counts;                            // the run's array of 64-bit counters
         StatsLayout lay{};
     } stats;
-    // The part of the running pairs call that the open runs (depth, stats) take once the call's return code is RSQ_OK: while one is open a call is one part
+    // rsq_sim_pileup_*: a run that accumulates the truth pileup of the pairs calls (rsq_pileup.h)
+    struct Pileup {
+        bool open = false, finished = false;      // between rsq_sim_pileup_begin and rsq_sim_pileup_end; rsq_sim_pileup_finish has turned plane 0 into depths
+        uint32_t sets = 1;                        // strand sets: 1, or 2 (RSQ_PILEUP_STRANDS: forward, reverse)
+        DevBuf planes, bad, tile_sums;            // sets * kPileupPlanes planes of `words`; elements that fell outside their sequence; the prefix sum's scratch
+        uint64_t words = 0;                       // of a plane: depth_words()
+        DevBuf flags, sizes, rank, at_pos, line_pos, offsets;      // rsq_sim_pileup_text's piece
+    } pileup;
+    // The part of the running pairs call that the open runs (depth, stats, pileup) take once the call's return code is RSQ_OK: while one is open a call is one part
     // (pairs_parts), whose fragments and raw arrays still lie in the workspace when the call ends.
     struct KeptPart {
         bool have = false;
@@ -324,7 +333,7 @@ struct rsq_sim : PrepassSim {
         RawLayout raw{};
         const uint32_t *row_order = nullptr;
     } kept;
-    bool keeps_part() const { return depth.open || stats.open; }
+    bool keeps_part() const { return depth.open || stats.open || pileup.open; }
     // rsq_sim_alleles_fasta (rsq_alleles.h): the records of the alleles' FASTA text, made at the first call (n == 0: not yet; a reference taken in later starts over)
     struct AllelesText {
         DevBuf records;
@@ -1240,17 +1249,33 @@ static void stats_take(rsq_sim &s, const rsq_sim::KeptPart &k, hipStream_t st) {
     else hipLaunchKernelGGL(k_stats_mates<false>, dim3(grid), dim3(kStatsMatesBlock), y.image_words * 4u, st, s.dev, k.frags, k.fvars, k.n_pairs, k.raw, k.row_order, y, counts);
     s.timers["stats_mates"].stop(st);
 }
+static void pileup_take(rsq_sim &s, const rsq_sim::KeptPart &k, hipStream_t st) {
+    rsq_sim::Pileup &u = s.pileup;
+    const dim3 grid((uint32_t)cdiv(2u * k.n_pairs, 256)), block(256);
+    const uint32_t strands = u.sets > 1u ? 1u : 0u;
+    s.timers["pileup_add"].start(st);
+    if (s.has_variants)
+        hipLaunchKernelGGL(k_pileup_add<true>, grid, block, 0, st, s.dev, k.frags, k.fvars, k.n_pairs, k.raw, k.row_order, u.planes.as<uint32_t>(), u.words, strands, u.bad.as<uint32_t>());
+    else
+        hipLaunchKernelGGL(k_pileup_add<false>, grid, block, 0, st, s.dev, k.frags, k.fvars, k.n_pairs, k.raw, k.row_order, u.planes.as<uint32_t>(), u.words, strands, u.bad.as<uint32_t>());
+    s.timers["pileup_add"].stop(st);
+}
 static void runs_take(rsq_sim &s, hipStream_t st) {
     rsq_sim::KeptPart &k = s.kept;
     if (!k.have || !k.n_pairs) return;
     k.have = false;
     if (s.depth.open) depth_take(s, k, st);
     if (s.stats.open) stats_take(s, k, st);
+    if (s.pileup.open) pileup_take(s, k, st);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(st));
 }
 // what a depth run refuses of the calls that simulate: pairs after rsq_sim_depth_finish
 static bool depth_refusal(const rsq_sim &s) {
+    if (s.pileup.open && s.pileup.finished) {
+        g_last_error = "the pileup run is finished (rsq_sim_pileup_finish): rsq_sim_pileup_end must run before more pairs are simulated";
+        return true;
+    }
     if (!s.depth.open || !s.depth.finished) return false;
     g_last_error = "the depth run is finished (rsq_sim_depth_finish): rsq_sim_depth_end must run before more pairs are simulated";
     return true;
@@ -1258,6 +1283,10 @@ static bool depth_refusal(const rsq_sim &s) {
 static bool depth_refuses_job(const rsq_sim &s, const char *call) {
     if (s.stats.open) {
         g_last_error = std::string(call) + ": a stats run is open (rsq_sim_stats_begin); the job calls are not counted in the simulation report";
+        return true;
+    }
+    if (s.pileup.open) {
+        g_last_error = std::string(call) + ": a pileup run is open (rsq_sim_pileup_begin); the job calls do not accumulate the pileup";
         return true;
     }
     if (!s.depth.open) return false;
@@ -2330,6 +2359,10 @@ int rsq_sim_truth_alleles(rsq_sim *s, int on) {
         g_last_error = "rsq_sim_truth_alleles cannot be switched on while a depth run is open (rsq_sim_depth_begin): depth is in reference coordinates";
         return RSQ_ESTATE;
     }
+    if (s->pileup.open) {
+        g_last_error = "rsq_sim_truth_alleles cannot be switched on while a pileup run is open (rsq_sim_pileup_begin): the pileup is in reference coordinates";
+        return RSQ_ESTATE;
+    }
     if (s->bam_sorted.open) {
         g_last_error = "rsq_sim_truth_alleles cannot change inside a sorted run (between rsq_sim_bam_sorted_begin and rsq_sim_bam_sorted_flush)";
         return RSQ_ESTATE;
@@ -2578,6 +2611,161 @@ int rsq_sim_stats_end(rsq_sim *s) {
         HIP_CHECK(hipSetDevice(s->device));
         s->stats.counts.release();
         s->stats.open = false;
+        return (int)RSQ_OK;
+    });
+}
+
+// ---- truth pileup (rsq_pileup.h; include/reseq_amd.h rsq_sim_pileup_*)
+static_assert(kPileupPlanes == RSQ_PILEUP_COLUMNS, "the ABI's row is rsq_pileup.h's");
+int rsq_sim_pileup_begin(rsq_sim *s, uint32_t flags) {
+    REQUIRE(s, "null argument");
+    REQUIRE_STATE(s->prepared && s->has_ref, "rsq_sim_prepare with a reference must run before rsq_sim_pileup_begin");
+    REQUIRE_STATE(!s->pileup.open, "rsq_sim_pileup_begin: a pileup run is open already (rsq_sim_pileup_end ends it)");
+    REQUIRE(!s->truth_alleles, "rsq_sim_pileup_begin: the pileup is in reference coordinates; rsq_sim_truth_alleles has chosen allele coordinates (switch that off first)");
+    REQUIRE(!(flags & ~RSQ_PILEUP_STRANDS), "rsq_sim_pileup_begin: unknown flags");
+    return guard([&] {
+        HIP_CHECK(hipSetDevice(s->device));
+        rsq_sim::Pileup &u = s->pileup;
+        u.sets = flags & RSQ_PILEUP_STRANDS ? 2u : 1u;
+        u.words = depth_words(s->total_ref_size, s->dev.n_seqs);
+        const uint64_t bytes = (uint64_t)u.sets * kPileupPlanes * u.words * 4u;
+        try {
+            u.planes.reserve(bytes);
+        } catch (const std::exception &e) {
+            u.words = 0;
+            throw Error("rsq_sim_pileup_begin: the run needs " + std::to_string(bytes) + " bytes of device memory (" + std::to_string(4u * kPileupPlanes * u.sets) +
+                        " per reference base): " + e.what());
+        }
+        u.bad.reserve(8);
+        HIP_CHECK(hipMemset(u.planes.as<void>(), 0, bytes));
+        HIP_CHECK(hipMemset(u.bad.as<void>(), 0, 8));
+        u.open = true;
+        u.finished = false;
+        return (int)RSQ_OK;
+    });
+}
+int rsq_sim_pileup_finish(rsq_sim *s, void *stream) {
+    REQUIRE(s, "null argument");
+    REQUIRE_STATE(s->pileup.open && !s->pileup.finished, "rsq_sim_pileup_finish: no pileup run is open, or it is finished already");
+    return guard([&] {
+        HIP_CHECK(hipSetDevice(s->device));
+        rsq_sim::Pileup &u = s->pileup;
+        const hipStream_t st = (hipStream_t)stream;
+        const uint32_t tiles = (uint32_t)(u.words / kDepthTile);
+        reset_call_timers(*s);
+        u.tile_sums.reserve((size_t)tiles * 4u + 16u);
+        for (uint32_t set = 0; set < u.sets; ++set) {                   // plane 0 of every strand set: differences -> depths
+            uint32_t *plane = u.planes.as<uint32_t>() + (uint64_t)set * kPileupPlanes * u.words;
+            s->timers["pileup_scan"].start(st);
+            hipLaunchKernelGGL(k_depth_tile_sums, dim3(tiles), dim3(kDepthBlock), 0, st, (const uint32_t *)plane, u.tile_sums.as<uint32_t>());
+            hipLaunchKernelGGL(k_depth_tiles, dim3(1), dim3(kDepthTilesBlock), 0, st, u.tile_sums.as<uint32_t>(), tiles);
+            hipLaunchKernelGGL(k_depth_apply, dim3(tiles), dim3(kDepthBlock), 0, st, plane, u.tile_sums.as<const uint32_t>());
+            s->timers["pileup_scan"].stop(st);
+        }
+        HIP_CHECK(hipGetLastError());
+        uint32_t bad = 0;
+        HIP_CHECK(hipMemcpyAsync(&bad, u.bad.as<uint32_t>(), 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        u.finished = true;
+        if (bad) {
+            g_last_error = "truth pileup: " + std::to_string(bad) + " alignment elements lay outside their sequence and were left out";
+            return (int)RSQ_EINVAL;
+        }
+        return (int)RSQ_OK;
+    });
+}
+static int pileup_window(const rsq_sim &s, const char *call, uint32_t seq, uint64_t lo, uint64_t hi) {
+    if (!s.pileup.open || !s.pileup.finished) {
+        g_last_error = std::string(call) + ": rsq_sim_pileup_finish must have run (plane 0 holds differences until then)";
+        return RSQ_ESTATE;
+    }
+    if (seq >= s.seq_len.size() || lo > hi || hi > s.seq_len[seq]) {
+        g_last_error = std::string(call) + ": no such sequence, or a window that is not inside it";
+        return RSQ_EINVAL;
+    }
+    return RSQ_OK;
+}
+int rsq_sim_pileup_counts(rsq_sim *s, uint32_t seq, uint64_t lo, uint64_t hi, uint32_t *rows_dev, void *stream) {
+    REQUIRE(s, "null argument");
+    if (const int rc = pileup_window(*s, "rsq_sim_pileup_counts", seq, lo, hi)) return rc;
+    REQUIRE(rows_dev || lo == hi, "null argument");
+    if (lo == hi) return RSQ_OK;
+    return guard([&] {
+        HIP_CHECK(hipSetDevice(s->device));
+        const hipStream_t st = (hipStream_t)stream;
+        const rsq_sim::Pileup &u = s->pileup;
+        const uint64_t n = hi - lo;
+        reset_call_timers(*s);
+        s->timers["pileup_rows"].start(st);
+        hipLaunchKernelGGL(k_pileup_rows, dim3((uint32_t)cdiv(n, 256)), dim3(256), 0, st, u.planes.as<const uint32_t>() + s->seq_base_off[seq] + seq, u.words, u.sets,
+                           s->dev.ref_words + s->seq_word_off[seq], (uint32_t)lo, n, rows_dev);
+        s->timers["pileup_rows"].stop(st);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(st));
+        return (int)RSQ_OK;
+    });
+}
+int rsq_sim_pileup_text(rsq_sim *s, uint32_t seq, uint64_t lo, uint64_t hi, uint32_t flags, char *dst_dev, size_t cap, size_t *len, uint64_t *n_lines, void *stream) {
+    REQUIRE(s && len && n_lines, "null argument");
+    *len = 0;
+    *n_lines = 0;
+    if (const int rc = pileup_window(*s, "rsq_sim_pileup_text", seq, lo, hi)) return rc;
+    REQUIRE(!(flags & ~RSQ_PILEUP_ALL), "rsq_sim_pileup_text: unknown flags");
+    const uint64_t n = hi - lo;
+    if (!n) return RSQ_OK;
+    return guard([&] {
+        HIP_CHECK(hipSetDevice(s->device));
+        const hipStream_t st = (hipStream_t)stream;
+        rsq_sim::Pileup &u = s->pileup;
+        reset_call_timers(*s);
+        s->cur = &s->ws[0];                                             // (the scan's scratch)
+        const uint32_t *at = u.planes.as<const uint32_t>() + s->seq_base_off[seq] + seq;
+        const uint64_t *ref_words = s->dev.ref_words + s->seq_word_off[seq];
+        const uint32_t name_len = (uint32_t)s->ref_first_names[seq].size();
+        u.flags.reserve(n * 4u + 16u);
+        u.sizes.reserve(n * 4u + 16u);
+        u.rank.reserve((n + 1u) * 8u);
+        u.at_pos.reserve((n + 1u) * 8u);
+        s->timers["pileup_lines"].start(st);
+        hipLaunchKernelGGL(k_pileup_lines, dim3((uint32_t)cdiv(n, 256)), dim3(256), 0, st, at, u.words, u.sets, ref_words, (uint32_t)lo, n, flags & RSQ_PILEUP_ALL ? 1u : 0u, name_len,
+                           u.flags.as<uint32_t>(), u.sizes.as<uint32_t>());
+        exclusive_scans(*s, ScanArrays{{u.flags.as<const uint32_t>(), u.sizes.as<const uint32_t>()}, {u.rank.as<uint64_t>(), u.at_pos.as<uint64_t>()}, {nullptr, nullptr}, {nullptr, nullptr}}, 2, n, st);
+        s->timers["pileup_lines"].stop(st);
+        uint64_t lines = 0, bytes = 0;
+        HIP_CHECK(hipMemcpyAsync(&lines, u.rank.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(&bytes, u.at_pos.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        *len = bytes;
+        *n_lines = lines;
+        if (!lines) return (int)RSQ_OK;
+        if (bytes > cap || !dst_dev) {                                   // nothing written: the call can be repeated
+            g_last_error = "pileup text buffer too small: need " + std::to_string(bytes) + " bytes";
+            return (int)RSQ_ENOSPC;
+        }
+        u.line_pos.reserve(lines * 4u + 16u);
+        u.offsets.reserve((lines + 1u) * 8u);
+        s->timers["pileup_lines"].start(st);
+        hipLaunchKernelGGL(k_pileup_place, dim3((uint32_t)cdiv(n + 1u, 256)), dim3(256), 0, st, u.flags.as<const uint32_t>(), u.rank.as<const uint64_t>(), u.at_pos.as<const uint64_t>(),
+                           (uint32_t)lo, n, u.line_pos.as<uint32_t>(), u.offsets.as<uint64_t>());
+        s->timers["pileup_lines"].stop(st);
+        const uint32_t lds = pileup_lds_bytes(name_len, u.sets);
+        s->timers["pileup_text"].start(st);
+        hipLaunchKernelGGL(k_pileup_text, dim3((uint32_t)cdiv(lines, kPileupLines)), dim3(64), lds, st, s->names, seq, at, u.words, u.sets, ref_words, u.line_pos.as<const uint32_t>(), lines,
+                           u.offsets.as<const uint64_t>(), dst_dev, lds);
+        s->timers["pileup_text"].stop(st);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(st));
+        return (int)RSQ_OK;
+    });
+}
+int rsq_sim_pileup_end(rsq_sim *s) {
+    REQUIRE(s, "null argument");
+    return guard([&] {
+        HIP_CHECK(hipSetDevice(s->device));
+        rsq_sim::Pileup &u = s->pileup;
+        for (DevBuf *b : {&u.planes, &u.bad, &u.tile_sums, &u.flags, &u.sizes, &u.rank, &u.at_pos, &u.line_pos, &u.offsets}) b->release();
+        u.open = u.finished = false;
+        u.words = 0;
         return (int)RSQ_OK;
     });
 }
