@@ -1213,29 +1213,17 @@ static void depth_take(rsq_sim &s, const rsq_sim::KeptPart &k, hipStream_t st) {
     else hipLaunchKernelGGL(k_depth_add<false>, grid, block, 0, st, s.dev, k.frags, k.fvars, k.n_pairs, k.raw, k.row_order, d.diff.as<uint32_t>(), d.bad.as<uint32_t>());
     s.timers["depth_add"].stop(st);
 }
-// The rows kernel's geometry (rsq_stats.h StatsRowsPlan): the chunk is the largest multiple of four positions, 64 at the most, whose image and staged words fit
-// 48 KB of LDS -- four workgroups a CU --, evened out over the longer segment's chunks (150 cycles: three chunks of 52, not 64 + 64 + 22); the grid is persistent,
-// four workgroups a CU and never fewer than there are units while that many are resident.  Options stats_chunk, stats_slab and stats_groups replace the three.
+// The rows kernel's geometry is rsq_stats.h's stats_rows_geometry; options stats_chunk, stats_slab and stats_groups replace its three choices.
 static void stats_take(rsq_sim &s, const rsq_sim::KeptPart &k, hipStream_t st) {
     const StatsLayout &y = s.stats.lay;
     uint64_t *counts = s.stats.counts.as<uint64_t>();
     const bool skew = s.opt.stats_form != 1;
-    constexpr uint32_t kLds = 48u * 1024u;
     if (2u * k.n_pairs >= (1ull << 32)) throw Error("more than 2^32 reads in one call: a workgroup of the report's kernels counts in 32 bits (use smaller block ranges)");
     if (y.lmax) {
-        uint32_t chunk = 64u;
-        if (s.opt.stats_chunk > 0) chunk = (uint32_t)std::min<int64_t>((s.opt.stats_chunk + 3) / 4 * 4, 1024);
-        else {
-            while (chunk > 4u && stats_rows_lds_bytes(chunk, y.Q, skew) > kLds) chunk -= 4u;
-            const uint32_t n = stats_chunks(y.lmax, chunk);
-            chunk = std::min(chunk, (cdiv(y.lmax, n) + 3u) / 4u * 4u);
-        }
-        const uint32_t lds = stats_rows_lds_bytes(chunk, y.Q, skew);
-        if (lds > 64u * 1024u) throw Error("the simulation report's image of " + std::to_string(chunk) + " positions does not fit the LDS (option stats_chunk, or a profile with more than 250 quality values)");
-        StatsRowsPlan plan{chunk, s.opt.stats_slab > 0 ? (uint32_t)std::min<int64_t>(s.opt.stats_slab, 1 << 30) : 1024u, {stats_chunks(y.len[0], chunk), stats_chunks(y.len[1], chunk)}, s.read_stride / 4u};
-        const uint32_t units = plan.units[0] + plan.units[1];
-        uint32_t groups = s.opt.stats_groups > 0 ? (uint32_t)std::min<int64_t>(s.opt.stats_groups, 1 << 16) : std::max(4u * s.n_cu, std::min(units, 8u * s.n_cu));
-        if (!(s.opt.stats_groups > 0)) groups = (uint32_t)std::min<uint64_t>(groups, (uint64_t)units * std::max<uint64_t>(cdiv(k.n_pairs, plan.slab), 1u));      // (no workgroup without a slab)
+        const StatsRowsGeometry geo = stats_rows_geometry(y.lmax, y.len[0], y.len[1], y.Q, skew, s.read_stride / 4u, s.n_cu, k.n_pairs, s.opt.stats_chunk, s.opt.stats_slab, s.opt.stats_groups);
+        const StatsRowsPlan &plan = geo.plan;
+        const uint32_t lds = geo.lds, groups = geo.groups, units = plan.units[0] + plan.units[1];
+        if (lds > 64u * 1024u) throw Error("the simulation report's image of " + std::to_string(plan.chunk) + " positions does not fit the LDS (option stats_chunk, or a profile with more than 250 quality values)");
         if (units) {
             s.timers["stats_rows"].start(st);
             if (skew) hipLaunchKernelGGL(k_stats_rows<true>, dim3(groups), dim3(kStatsRowsBlock), lds, st, k.raw.seq, k.raw.qual, k.raw.meta, k.raw.pitch, k.n_pairs, y, plan, counts);

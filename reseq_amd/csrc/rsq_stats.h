@@ -212,6 +212,40 @@ constexpr uint32_t kStatsRowsBlock = 256, kStatsRowsWaves = kStatsRowsBlock / 64
 RSQ_HD uint32_t stats_rows_lds_bytes(uint32_t chunk, uint32_t Q, bool skew) {
     return (chunk * stats_row_stride(Q) + (skew ? kStatsRowsWaves * 2u * (chunk / 4u) * 64u : 0u)) * 4u;
 }
+// The rows kernel's geometry for a call of n_pairs pairs on n_cu compute units: the chunk is the largest multiple of four positions, 64 at the most, whose image
+// and staged words fit 48 KB of LDS -- four workgroups a CU --, evened out over the longer segment's chunks (150 cycles: three chunks of 52, not 64 + 64 + 22);
+// the grid is persistent, four workgroups a CU and never fewer than there are units while that many are resident, and no workgroup without a slab.  The options
+// (> 0) replace the three: opt_chunk (rounded up to a multiple of four), opt_slab, opt_groups.  lds: what the launch asks for (the caller refuses more than the
+// device has).  tests/hostemu/stats_trial.cpp exports it, tests/hostemu/kernel_trial.cpp launches by it.
+constexpr uint32_t kStatsRowsLds = 48u * 1024u;
+struct StatsRowsGeometry {
+    StatsRowsPlan plan;
+    uint32_t lds, groups;
+};
+RSQ_HD StatsRowsGeometry stats_rows_geometry(uint32_t lmax, uint32_t len0, uint32_t len1, uint32_t Q, bool skew, uint32_t row_words, uint32_t n_cu, uint64_t n_pairs, int64_t opt_chunk,
+                                             int64_t opt_slab, int64_t opt_groups) {
+    uint32_t chunk = 64u;
+    if (opt_chunk > 0) {
+        const int64_t c = (opt_chunk + 3) / 4 * 4;
+        chunk = (uint32_t)(c < 1024 ? c : 1024);
+    } else {
+        while (chunk > 4u && stats_rows_lds_bytes(chunk, Q, skew) > kStatsRowsLds) chunk -= 4u;
+        const uint32_t n = lmax ? stats_chunks(lmax, chunk) : 1u, even =((lmax + n - 1u) / n + 3u) / 4u * 4u;
+        if (even && even < chunk) chunk = even;                          // (lmax 0: no unit, the chunk is never used)
+    }
+    StatsRowsGeometry g{};
+    g.lds = stats_rows_lds_bytes(chunk, Q, skew);
+    g.plan = StatsRowsPlan{chunk, opt_slab > 0 ? (uint32_t)(opt_slab < (1 << 30) ? opt_slab : (1 << 30)) : 1024u, {stats_chunks(len0, chunk), stats_chunks(len1, chunk)}, row_words};
+    const uint32_t units = g.plan.units[0] + g.plan.units[1];
+    if (opt_groups > 0) g.groups = (uint32_t)(opt_groups < (1 << 16) ? opt_groups : (1 << 16));
+    else {
+        const uint32_t few = units < 8u * n_cu ? units : 8u * n_cu;
+        g.groups = 4u * n_cu > few ? 4u * n_cu : few;
+        const uint64_t slabs = (n_pairs + g.plan.slab - 1u) / g.plan.slab, most = (uint64_t)units * (slabs > 1u ? slabs : 1u);
+        if (g.groups > most) g.groups = (uint32_t)most;
+    }
+    return g;
+}
 
 #if RSQ_DEVICE_BUILD
 // a 64-bit counter of the run's array: an atomic without a result

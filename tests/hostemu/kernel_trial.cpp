@@ -1,16 +1,22 @@
 // kernel_trial.cpp -- TEST-ONLY: the library's cooperative kernels run alone on inputs made in Python (tests/kernel_trial_cases.py, tests/test_kernel_trial_gpu.py).
 // These are the kernels whose code exists only for the device -- ballots, shuffles, LDS counters, tile sums -- so that the host emulation replaces them with a
 // loop: the scan (rsq_scan.h), the sorted BAM's radix passes, cut, gather and index kernels (rsq_bamsort.h), the bins' plan and scatter (rsq_format.h) and the
-// FASTA record starts (rsq_fasta.h).  Compiled by hipcc for the library's architecture with the library's flags (tests/hostemu/Makefile: kernel_trial).
+// FASTA record starts (rsq_fasta.h); and the kernels that turn a run's arrays into results: the truth depth's in-place prefix sum and its bedGraph text
+// (rsq_depth.h), the truth pileup's rows and TSV text (rsq_pileup.h), the simulation report's rows kernel and its ballot-aggregated adds (rsq_stats.h).
+// Compiled by hipcc for the library's architecture with the library's flags (tests/hostemu/Makefile: kernel_trial).
 //
-//   kernel_trial FAMILY input.bin output.bin        FAMILY: scan | sort | gather | index | bins | fasta
+//   kernel_trial FAMILY input.bin output.bin        FAMILY: scan | sort | gather | index | bins | fasta | depthscan | bedgraph | pileup | stats
 //
 // input.bin:  a word (uint64) with the number of cases; per case sixteen words of parameters, then the case's blobs, each a word with its bytes followed by the
 //             bytes, padded to a multiple of eight.
 // output.bin: per case its result blobs in the same form.
 // Launches go through scan_launch and bam_sort_passes where the library's do; the sequences with a host read in the middle are restated here with the library's
-// grid formulas (rsq_sim.hip: sorted_finish, build_fill_bins, rsq_sim_error_model_fasta).  The one kernel of its own is k_trial_keys, which reads bin keys from
-// memory where k_pair_tiles / k_record_tiles draw them, and counts them with the library's bin_count_key.
+// grid formulas (rsq_sim.hip: sorted_finish, build_fill_bins, rsq_sim_error_model_fasta, rsq_sim_depth_finish, rsq_sim_depth_bedgraph, rsq_sim_pileup_counts,
+// rsq_sim_pileup_text, stats_take) and the library's LDS sizes (depth_lds_bytes, pileup_lds_bytes, stats_rows_geometry).  The kernels of its own: k_trial_keys, which
+// reads bin keys from memory where k_pair_tiles / k_record_tiles draw them, and counts them with the library's bin_count_key; k_trial_shared, which reads the
+// indices of StatsMatesAdd's adds from memory where k_stats_mates walks a mate for them.
+// High positions without large arrays: the depth, pileup and reference arrays of a case exist from a position `base` on, and the kernels get the address moved back
+// by `base` elements (moved_back), so that position p of the sequence is element p - base of the buffer; a right kernel reads nothing in front of the window.
 // Every HIP call is checked; the first error ends the program with a message and a non-zero status.  Nothing is tried twice.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -30,6 +36,9 @@
 #include "../../reseq_amd/csrc/rsq_bam.h"
 #include "../../reseq_amd/csrc/rsq_md.h"
 #include "../../reseq_amd/csrc/rsq_bamsort.h"
+#include "../../reseq_amd/csrc/rsq_depth.h"
+#include "../../reseq_amd/csrc/rsq_pileup.h"
+#include "../../reseq_amd/csrc/rsq_stats.h"
 
 using namespace rsq;
 
@@ -312,11 +321,245 @@ static void run_fasta(const uint64_t *par, Reader &in, Writer &out) {
     emit<uint32_t>(out, d_summary, 4);
 }
 
+// ------------------------------------------------------------------------------------------------ guarded buffers of the families below
+// `count` elements between kMarker guard bytes (0xA5) on either side; emitted with both, so that the checker sees what was written in front of and behind them
+template <class T>
+static T *guarded(Arena &mem, uint64_t count, uint64_t shift_bytes = 0) {
+    return reinterpret_cast<T *>(mem.get<char>(kMarker + shift_bytes + count * sizeof(T) + kMarker, 0xA5) + kMarker + shift_bytes);
+}
+template <class T>
+static T *guarded_put(Arena &mem, const Blob &b) {
+    return reinterpret_cast<T *>(mem.put<char>(b, kMarker, kMarker, 0xA5));
+}
+template <class T>
+static void emit_guarded(Writer &w, const T *dev, uint64_t count) {
+    emit<char>(w, reinterpret_cast<const char *>(dev) - kMarker, kMarker + count * sizeof(T) + kMarker);
+}
+// the address of element 0 of an array of which only the elements from `base` on exist, at `window`: element p is window[p - base]
+template <class T>
+static const T *moved_back(const T *window, uint64_t base) {
+    return reinterpret_cast<const T *>(reinterpret_cast<uintptr_t>(window) - (uintptr_t)(base * sizeof(T)));
+}
+// a name table of one sequence
+static NameTable one_name(Arena &mem, const Blob &name) {
+    NameTable names{};
+    names.names = mem.put<char>(name, 0, 8);
+    const uint32_t ptr[2] = {0u, (uint32_t)name.size()};
+    uint32_t *d_ptr = mem.get<uint32_t>(8);
+    CHECK(hipMemcpy(d_ptr, ptr, 8, hipMemcpyHostToDevice));
+    names.name_ptr = d_ptr;
+    return names;
+}
+
+// ------------------------------------------------------------------------------------------------ depthscan
+// parameters: tiles.  blob: tiles * kDepthTile words.
+// results: the array after the three launches of rsq_sim_depth_finish, tile_sums (the library's tiles * 4 + 16 bytes lie inside the guards' reach), both guarded
+static void run_depthscan(const uint64_t *par, Reader &in, Writer &out) {
+    const uint64_t tiles = par[0];
+    const Blob values = in.blob();
+    if (tiles < 1 || tiles > 65536 || values.size() != tiles * kDepthTile * 4u) fail("depthscan: bad case");
+    Arena mem;
+    uint32_t *d_a = guarded_put<uint32_t>(mem, values), *d_sums = guarded<uint32_t>(mem, tiles);
+    hipLaunchKernelGGL(k_depth_tile_sums, dim3((uint32_t)tiles), dim3(kDepthBlock), 0, nullptr, (const uint32_t *)d_a, d_sums);
+    hipLaunchKernelGGL(k_depth_tiles, dim3(1), dim3(kDepthTilesBlock), 0, nullptr, d_sums, (uint32_t)tiles);
+    hipLaunchKernelGGL(k_depth_apply, dim3((uint32_t)tiles), dim3(kDepthBlock), 0, nullptr, d_a, (const uint32_t *)d_sums);
+    finish_launches();
+    emit_guarded<uint32_t>(out, d_a, tiles * kDepthTile);
+    emit_guarded<uint32_t>(out, d_sums, tiles);
+}
+
+// ------------------------------------------------------------------------------------------------ bedgraph
+// parameters: len, base (a multiple of 32; the first piece's carry), the text's offset from a 16-byte boundary, the bytes of all pieces' text (the destination's
+// capacity: a piece that needs more ends the trial).  blobs: the depths of [base, len], the name, the piece bounds (uint64, rising from base).
+// The pieces in order as rsq_sim_depth_bedgraph runs them, their texts one behind the other.  results: {lines, bytes, carry after it} per piece; the text, guarded
+static void run_bedgraph(const uint64_t *par, Reader &in, Writer &out) {
+    const uint64_t len = par[0], base = par[1], lead = par[2], cap = par[3];
+    const Blob depths = in.blob(), name = in.blob(), bounds_blob = in.blob();
+    const uint64_t *bounds = reinterpret_cast<const uint64_t *>(bounds_blob.data()), n_bounds = bounds_blob.size() / 8u;
+    if (len < 1 || len > 0xFFFFFFFFull || base >= len || base % 32u || lead > 15 || depths.size() != (len - base + 1u) * 4u || name.empty() || n_bounds < 2 || bounds_blob.size() % 8u ||
+        bounds[0] != base || bounds[n_bounds - 1u] > len)
+        fail("bedgraph: bad case");
+    for (uint64_t k = 1; k < n_bounds; ++k)
+        if (bounds[k] < bounds[k - 1u]) fail("bedgraph: the bounds fall");
+    Arena mem;
+    const uint32_t *d = moved_back(mem.put<uint32_t>(depths, kMarker, kMarker, 0xA5), base);
+    const NameTable names = one_name(mem, name);
+    const uint32_t name_len = (uint32_t)name.size(), lds = depth_lds_bytes(name_len);
+    char *d_dst = guarded<char>(mem, cap, lead);
+    uint64_t at = 0;
+    uint32_t carry = (uint32_t)base;
+    std::vector<uint64_t> per_piece;
+    for (uint64_t k = 0; k + 1u < n_bounds; ++k) {
+        const uint64_t lo = bounds[k], n = bounds[k + 1u] - lo;
+        uint64_t lines = 0, bytes = 0;
+        if (n) {
+            Arena piece;
+            uint32_t *d_flags = piece.get<uint32_t>(n * 4u + 16u, 0xA5);
+            uint64_t *d_rank = piece.get<uint64_t>((n + 1u) * 8u);
+            hipLaunchKernelGGL(k_depth_ends, dim3(cdiv32(n, 256)), dim3(256), 0, nullptr, d, (uint32_t)len, (uint32_t)lo, n, d_flags);
+            scan_one(piece, d_flags, n, d_rank);
+            finish_launches();
+            lines = fetch<uint64_t>(d_rank + n, 1)[0];
+            if (lines > n) fail("bedgraph: more lines than positions");
+            if (lines) {
+                uint32_t *d_ends = piece.get<uint32_t>(lines * 4u + 16u, 0xA5), *d_sizes = piece.get<uint32_t>(lines * 4u + 16u, 0xA5);
+                uint64_t *d_offsets = piece.get<uint64_t>((lines + 1u) * 8u);
+                hipLaunchKernelGGL(k_depth_run_ends, dim3(cdiv32(n, 256)), dim3(256), 0, nullptr, (const uint32_t *)d_flags, (const uint64_t *)d_rank, (uint32_t)lo, n, d_ends);
+                hipLaunchKernelGGL(k_depth_line_sizes, dim3(cdiv32(lines, 256)), dim3(256), 0, nullptr, d, (const uint32_t *)d_ends, lines, carry, name_len, d_sizes);
+                scan_one(piece, d_sizes, lines, d_offsets);
+                finish_launches();
+                bytes = fetch<uint64_t>(d_offsets + lines, 1)[0];
+                const uint32_t last_end = fetch<uint32_t>(d_ends + (lines - 1u), 1)[0];
+                if (bytes > cap - at) fail("bedgraph: a piece's text does not fit what the case allows");
+                hipLaunchKernelGGL(k_depth_text, dim3(cdiv32(lines, kDepthLines)), dim3(64), lds, nullptr, names, 0u, d, (const uint32_t *)d_ends, carry, lines, (const uint64_t *)d_offsets,
+                                   d_dst + at, lds);
+                finish_launches();
+                carry = last_end;
+                at += bytes;
+            }
+        }
+        per_piece.insert(per_piece.end(), {lines, bytes, (uint64_t)carry});
+    }
+    out.blob(per_piece.data(), per_piece.size() * 8u);
+    emit_guarded<char>(out, d_dst, cap);
+}
+
+// ------------------------------------------------------------------------------------------------ pileup
+// parameters: the window's length n, base (a multiple of 32), sets, all, the text's offset from a 16-byte boundary, the rows' offset from one in words, the bytes
+// of all pieces' text.  blobs: the planes [sets * 8][n], the packed reference codes of the window (uint64), the name, the piece bounds (uint64, rising from base).
+// results: the rows of the window (rsq_sim_pileup_counts); per piece, as rsq_sim_pileup_text runs it, flags, sizes, {lines, bytes}, line_pos, offsets; the text.
+// Every array guarded.
+static void run_pileup(const uint64_t *par, Reader &in, Writer &out) {
+    const uint64_t n_all = par[0], base = par[1], sets = par[2], all = par[3], lead = par[4], rows_shift = par[5], cap = par[6];
+    const Blob planes = in.blob(), ref = in.blob(), name = in.blob(), bounds_blob = in.blob();
+    const uint64_t *bounds = reinterpret_cast<const uint64_t *>(bounds_blob.data()), n_bounds = bounds_blob.size() / 8u;
+    if (n_all < 1 || base + n_all > 0xFFFFFFFFull || base % 32u || sets < 1 || sets > 2 || all > 1 || lead > 15 || rows_shift > 3 || planes.size() != sets * kPileupPlanes * n_all * 4u ||
+        ref.size() != (n_all + 31u) / 32u * 8u || name.empty() || n_bounds < 2 || bounds_blob.size() % 8u || bounds[0] != base || bounds[n_bounds - 1u] > base + n_all)
+        fail("pileup: bad case");
+    for (uint64_t k = 1; k < n_bounds; ++k)
+        if (bounds[k] < bounds[k - 1u]) fail("pileup: the bounds fall");
+    Arena mem;
+    const uint64_t words = n_all;
+    const uint32_t *at = moved_back(mem.put<uint32_t>(planes, kMarker, kMarker, 0xA5), base);
+    const uint64_t *ref_words = moved_back(mem.put<uint64_t>(ref, kMarker, kMarker, 0xA5), base / 32u);
+    const NameTable names = one_name(mem, name);
+    const uint32_t name_len = (uint32_t)name.size(), lds = pileup_lds_bytes(name_len, (uint32_t)sets);
+    uint32_t *d_rows = guarded<uint32_t>(mem, n_all * sets * kPileupPlanes, rows_shift * 4u);
+    hipLaunchKernelGGL(k_pileup_rows, dim3(cdiv32(n_all, 256)), dim3(256), 0, nullptr, at, words, (uint32_t)sets, ref_words, (uint32_t)base, n_all, d_rows);
+    finish_launches();
+    emit_guarded<uint32_t>(out, d_rows, n_all * sets * kPileupPlanes);
+    char *d_dst = guarded<char>(mem, cap, lead);
+    uint64_t text_at = 0;
+    for (uint64_t k = 0; k + 1u < n_bounds; ++k) {
+        const uint64_t lo = bounds[k], n = bounds[k + 1u] - lo;
+        Arena piece;
+        uint32_t *d_flags = guarded<uint32_t>(piece, n), *d_sizes = guarded<uint32_t>(piece, n);
+        uint64_t lines = 0, bytes = 0;
+        uint64_t *d_rank = piece.get<uint64_t>((n + 1u) * 8u), *d_at_pos = piece.get<uint64_t>((n + 1u) * 8u);
+        if (n) {
+            uint64_t *d_tiles = piece.get<uint64_t>(2u * ((uint64_t)cdiv32(n, kScanTile) + 1u) * 8u), *d_totals = piece.get<uint64_t>(16);      // (exclusive_scans: the totals' scratch)
+            hipLaunchKernelGGL(k_pileup_lines, dim3(cdiv32(n, 256)), dim3(256), 0, nullptr, at, words, (uint32_t)sets, ref_words, (uint32_t)lo, n, (uint32_t)all, name_len, d_flags, d_sizes);
+            scan_launch(ScanArrays{{d_flags, d_sizes}, {d_rank, d_at_pos}, {nullptr, nullptr}, {d_totals, d_totals + 1}}, 2, n, d_tiles, nullptr, nullptr);
+            finish_launches();
+            lines = fetch<uint64_t>(d_rank + n, 1)[0];
+            bytes = fetch<uint64_t>(d_at_pos + n, 1)[0];
+            if (lines > n) fail("pileup: more lines than positions");
+        }
+        uint32_t *d_line_pos = guarded<uint32_t>(piece, lines);
+        uint64_t *d_offsets = guarded<uint64_t>(piece, lines ? lines + 1u : 0u);
+        if (lines) {
+            if (bytes > cap - text_at) fail("pileup: a piece's text does not fit what the case allows");
+            hipLaunchKernelGGL(k_pileup_place, dim3(cdiv32(n + 1u, 256)), dim3(256), 0, nullptr, (const uint32_t *)d_flags, (const uint64_t *)d_rank, (const uint64_t *)d_at_pos, (uint32_t)lo, n,
+                               d_line_pos, d_offsets);
+            hipLaunchKernelGGL(k_pileup_text, dim3(cdiv32(lines, kPileupLines)), dim3(64), lds, nullptr, names, 0u, at, words, (uint32_t)sets, ref_words, (const uint32_t *)d_line_pos, lines,
+                               (const uint64_t *)d_offsets, d_dst + text_at, lds);
+            finish_launches();
+            text_at += bytes;
+        }
+        emit_guarded<uint32_t>(out, d_flags, n);
+        emit_guarded<uint32_t>(out, d_sizes, n);
+        const uint64_t counts[2] = {lines, bytes};
+        out.blob(counts, sizeof counts);
+        emit_guarded<uint32_t>(out, d_line_pos, lines);
+        emit_guarded<uint64_t>(out, d_offsets, lines ? lines + 1u : 0u);
+    }
+    emit_guarded<char>(out, d_dst, cap);
+}
+
+// ------------------------------------------------------------------------------------------------ stats
+static_assert(sizeof(ReadMeta) == 16, "the trial builds the read kernel's ReadMeta entries");
+// the stand-in for k_stats_mates' walk: per round every lane takes {index, on, index2, v} from memory, calls shared(index, on) with its whole wave and add(index2, v);
+// the image is cleared and flushed as k_stats_mates does it
+__global__ void __launch_bounds__(kStatsMatesBlock) k_trial_shared(const uint32_t *rounds, uint32_t n_rounds, uint32_t image_words, uint64_t *counts) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_trial[];
+    for (uint32_t i = threadIdx.x; i < image_words; i += kStatsMatesBlock) s_trial[i] = 0u;
+    __syncthreads();
+    const StatsMatesAdd a{s_trial, counts, image_words};
+    for (uint32_t r = 0; r < n_rounds; ++r) {
+        const uint32_t *e = rounds + ((uint64_t)r * kStatsMatesBlock + threadIdx.x) * 4u;
+        a.shared(e[0], e[1] != 0u);
+        a.add(e[2], e[3]);
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < image_words; i += kStatsMatesBlock)
+        if (const uint32_t v = s_trial[i]) stats_flush_add(counts + i, v);
+}
+// parameters: 0, n_pairs, len0, len1, Q, phred, row_words, pitch, chunk, slab, groups (chunk, slab, groups 0: the library's choice, stats_rows_geometry as
+// stats_take calls it), skew.  blobs: the seq words and the qual words [row_words][pitch], read_len (uint16) of the 2 n_pairs rows.
+// results: the layout {off of base_quality, of base_call, of bad, words}; the counts of stats_layout(len0, len1, 0, Q, 1, phred), guarded
+// parameters: 1, the words of the counts, image_words, workgroups.  blob: the rounds [round][256]{index, on, index2, v}.  result: the counts, guarded
+static void run_stats(const uint64_t *par, Reader &in, Writer &out) {
+    Arena mem;
+    if (par[0] == 1u) {
+        const uint64_t words = par[1], image_words = par[2], groups = par[3];
+        const Blob rounds = in.blob();
+        const uint64_t n_rounds = rounds.size() / (kStatsMatesBlock * 16u);
+        if (words < 1 || image_words > words || image_words * 4u > kStatsMatesLds || groups < 1 || groups > 64 || rounds.size() % (kStatsMatesBlock * 16u)) fail("stats: bad case of shared adds");
+        for (uint64_t i = 0; i < rounds.size() / 16u; ++i) {
+            const uint32_t *e = reinterpret_cast<const uint32_t *>(rounds.data()) + 4u * i;
+            if (e[0] >= words || e[2] >= words) fail("stats: an index outside the counts");
+        }
+        uint64_t *d_counts = guarded<uint64_t>(mem, words);
+        CHECK(hipMemset(d_counts, 0, words * 8u));
+        hipLaunchKernelGGL(k_trial_shared, dim3((uint32_t)groups), dim3(kStatsMatesBlock), (uint32_t)image_words * 4u, nullptr, mem.put<uint32_t>(rounds), (uint32_t)n_rounds, (uint32_t)image_words,
+                           d_counts);
+        finish_launches();
+        emit_guarded<uint64_t>(out, d_counts, words);
+        return;
+    }
+    const uint64_t n_pairs = par[1], pitch = par[7];
+    const uint32_t len0 = (uint32_t)par[2], len1 = (uint32_t)par[3], Q = (uint32_t)par[4], phred = (uint32_t)par[5], row_words = (uint32_t)par[6];
+    const bool skew = par[11] != 0;
+    const Blob seq = in.blob(), qual = in.blob(), lens = in.blob();
+    if (par[0] || n_pairs < 1 || n_pairs > (1u << 24) || !(len0 | len1) || len0 > 4096 || len1 > 4096 || Q < 1 || Q > 250 || row_words < 1 || pitch < 2u * n_pairs ||
+        seq.size() != (uint64_t)row_words * pitch * 4u || qual.size() != seq.size() || lens.size() != 4u * n_pairs || par[8] % 4u || par[8] > 1024)
+        fail("stats: bad case of rows");
+    const StatsLayout y = stats_layout(len0, len1, 0u, Q, 1u, phred);
+    hipDeviceProp_t prop;
+    CHECK(hipGetDeviceProperties(&prop, 0));
+    const StatsRowsGeometry geo = stats_rows_geometry(y.lmax, len0, len1, Q, skew, row_words, (uint32_t)prop.multiProcessorCount, n_pairs, (int64_t)par[8], (int64_t)par[9], (int64_t)par[10]);
+    if (geo.lds > 64u * 1024u) fail("stats: the image does not fit the LDS");
+    std::vector<ReadMeta> meta(2u * n_pairs, ReadMeta{});
+    for (uint64_t r = 0; r < 2u * n_pairs; ++r) meta[r].read_len = reinterpret_cast<const uint16_t *>(lens.data())[r];
+    ReadMeta *d_meta = mem.get<ReadMeta>(meta.size() * sizeof(ReadMeta));
+    CHECK(hipMemcpy(d_meta, meta.data(), meta.size() * sizeof(ReadMeta), hipMemcpyHostToDevice));
+    const uint32_t *d_seq = mem.put<uint32_t>(seq), *d_qual = mem.put<uint32_t>(qual);
+    uint64_t *d_counts = guarded<uint64_t>(mem, y.words);
+    CHECK(hipMemset(d_counts, 0, (uint64_t)y.words * 8u));
+    if (skew) hipLaunchKernelGGL(k_stats_rows<true>, dim3(geo.groups), dim3(kStatsRowsBlock), geo.lds, nullptr, d_seq, d_qual, (const ReadMeta *)d_meta, pitch, n_pairs, y, geo.plan, d_counts);
+    else hipLaunchKernelGGL(k_stats_rows<false>, dim3(geo.groups), dim3(kStatsRowsBlock), geo.lds, nullptr, d_seq, d_qual, (const ReadMeta *)d_meta, pitch, n_pairs, y, geo.plan, d_counts);
+    finish_launches();
+    const uint32_t layout[4] = {y.off[kStBaseQuality], y.off[kStBaseCall], y.off[kStBad], y.words};
+    out.blob(layout, sizeof layout);
+    emit_guarded<uint64_t>(out, d_counts, y.words);
+}
+
 int main(int argc, char **argv) {
     if (argc != 4) fail("usage: kernel_trial FAMILY input.bin output.bin");
     const std::string family = argv[1];
     void (*run)(const uint64_t *, Reader &, Writer &) = family == "scan" ? run_scan : family == "sort" ? run_sort : family == "gather" ? run_gather : family == "index" ? run_index
-                                                        : family == "bins" ? run_bins : family == "fasta" ? run_fasta : nullptr;
+                                                        : family == "bins" ? run_bins : family == "fasta" ? run_fasta : family == "depthscan" ? run_depthscan
+                                                        : family == "bedgraph" ? run_bedgraph : family == "pileup" ? run_pileup : family == "stats" ? run_stats : nullptr;
     if (!run) fail("no such family: " + family);
     Reader in{fopen(argv[2], "rb")};
     Writer out{fopen(argv[3], "wb")};

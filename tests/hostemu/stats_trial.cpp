@@ -39,6 +39,20 @@ extern "C" uint32_t stats_trial_layout(uint32_t len0, uint32_t len1, uint32_t F,
     return y.words;
 }
 
+// the rows kernel's geometry as the library chooses it (options 0: its own choice) -> out = {chunk, slab, units of segment 0, of segment 1, lds, groups}
+extern "C" void stats_trial_geometry(uint32_t lmax, uint32_t len0, uint32_t len1, uint32_t Q, int32_t skew, uint32_t row_words, uint32_t n_cu, uint64_t n_pairs, int64_t opt_chunk,
+                                     int64_t opt_slab, int64_t opt_groups, uint32_t *out) {
+    const StatsRowsGeometry g = stats_rows_geometry(lmax, len0, len1, Q, skew != 0, row_words, n_cu, n_pairs, opt_chunk, opt_slab, opt_groups);
+    const uint32_t v[6] = {g.plan.chunk, g.plan.slab, g.plan.units[0], g.plan.units[1], g.lds, g.groups};
+    for (uint32_t i = 0; i < 6u; ++i) out[i] = v[i];
+}
+// ... for every Q in [1, q_hi], lmax in [1, l_hi] and both forms (len0 = lmax, len1 = lmax / 2): out[((Q - 1) * l_hi + lmax - 1) * 2 + skew][6]
+extern "C" void stats_trial_geometry_table(uint32_t q_hi, uint32_t l_hi, uint32_t n_cu, uint64_t n_pairs, uint32_t *out) {
+    for (uint32_t Q = 1; Q <= q_hi; ++Q)
+        for (uint32_t lmax = 1; lmax <= l_hi; ++lmax)
+            for (int32_t skew = 0; skew < 2; ++skew, out += 6) stats_trial_geometry(lmax, lmax, lmax / 2u, Q, skew, (lmax + 3u) / 4u, n_cu, n_pairs, 0, 0, 0, out);
+}
+
 struct RowSrc {
     const uint32_t *s, *q;
     uint64_t pitch;

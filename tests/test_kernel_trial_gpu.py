@@ -8,6 +8,12 @@ plain references' of that module, exactly -- integers and bytes, no tolerance (t
   index    k_bam_index_flags / k_bam_index_runs: records over several 16 kb windows, short ones behind long ones
   bins     bin_count_key / k_bins_plan / k_bin_scatter: several scatter workgroups, more than 1024 bins, both sides of kBinKeysLds
   fasta    tile_starts in k_fasta_count / k_fasta_starts, k_fasta_lead: a start on either side of every seam, texts that end there, unaligned text
+  depthscan  k_depth_tile_sums / k_depth_tiles / k_depth_apply: dense values whose sums wrap, spikes on the tile seams, one to three tiles a thread of k_depth_tiles
+  bedgraph   k_depth_ends / k_depth_run_ends / k_depth_line_sizes / k_depth_text piece by piece: numbers of one to ten digits, positions up to 4294967295, every
+             alignment, names on both sides of the image's cap and a launch whose waves take both routes
+  pileup     k_pileup_rows / k_pileup_lines / k_pileup_place / k_pileup_text: the predicate over one and two strand sets, counts of every width, the unaligned
+             rows, 0 to 129 kept lines a piece, both routes in one launch
+  stats      k_stats_rows in both forms over units, slabs and workgroups of every relation, Q up to 250 with the library's chunk; StatsMatesAdd's shared adds
 
 A child that ends by a signal, by abort, at its limit or with a HIP error in its output stops the module: the family tests after it fail at once and start nothing
 on the device."""
@@ -73,3 +79,20 @@ def test_bins(trial, tmp_path):
 
 def test_fasta_starts(trial, tmp_path):
     family_holds(trial, tmp_path, "fasta")
+
+
+def test_depth_prefix_sum(trial, tmp_path):
+    family_holds(trial, tmp_path, "depthscan")
+
+
+def test_depth_bedgraph(trial, tmp_path):
+    family_holds(trial, tmp_path, "bedgraph")
+
+
+def test_pileup_rows_and_text(trial, tmp_path):
+    family_holds(trial, tmp_path, "pileup")
+
+
+def test_stats_rows_and_shared_adds(trial, tmp_path):
+    """(the sums are integers: the order of the atomics does not show)"""
+    family_holds(trial, tmp_path, "stats")

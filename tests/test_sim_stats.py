@@ -28,6 +28,9 @@ def trial_lib(tmp_path_factory):
     L.stats_trial_layout.restype = C.c_uint32
     L.stats_trial_layout.argtypes = [C.c_uint32] * 7 + [C.c_void_p] * 3
     L.stats_rows_trial.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64] + [C.c_uint32] * 8 + [C.c_int32, C.c_void_p]
+    L.stats_trial_geometry.restype = L.stats_trial_geometry_table.restype = None
+    L.stats_trial_geometry.argtypes = [C.c_uint32] * 4 + [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint64] + [C.c_int64] * 3 + [C.c_void_p]
+    L.stats_trial_geometry_table.argtypes = [C.c_uint32] * 3 + [C.c_uint64, C.c_void_p]
     L.stats_mates_trial.argtypes = [C.POINTER(MdIn), C.c_int] + [C.c_uint32] * 4 + [C.c_void_p, C.c_char_p, C.c_uint32, C.c_void_p]
     return L
 
@@ -140,6 +143,34 @@ def test_segments_of_different_lengths_and_odd_slabs(trial_lib):
         assert trial_lib.stats_rows_trial(seq.ctypes.data, qual.ctypes.data, lens.ctypes.data, pitch, n, row_words, 30, 21, Q_ROWS, PHRED, chunk, slab, groups, 1, got.ctypes.data) == 0
         t, _ = tables_of(trial_lib, got, (30, 21), 10, Q_ROWS, 1)
         same(t, want)
+
+
+def test_the_librarys_geometry_of_the_rows_kernel(trial_lib):
+    """stats_rows_geometry, what stats_take launches k_stats_rows by, for every Q in 1 .. 250, every longest read of 1 .. 400 and both forms: the chunk is a multiple
+    of four between 4 and 64, the LDS at most 48 KiB, the units cover every position of either segment and none lies behind it, and no workgroup is without a slab"""
+    q_hi, l_hi = 250, 400
+    Q = np.arange(1, q_hi + 1)[:, None, None]
+    lmax = np.arange(1, l_hi + 1)[None, :, None]
+    skew = np.arange(2)[None, None, :]
+    for n_cu, n_pairs in ((256, 1), (256, 1025), (256, 5000), (256, 10_000_000), (1, 5000), (8, 3)):
+        out = np.zeros((q_hi, l_hi, 2, 6), np.uint32)
+        trial_lib.stats_trial_geometry_table(q_hi, l_hi, n_cu, n_pairs, out.ctypes.data)
+        chunk, slab, units0, units1, lds, groups = (out[..., k].astype(np.int64) for k in range(6))
+        assert (chunk % 4 == 0).all() and (chunk >= 4).all() and (chunk <= 64).all()
+        assert (lds <= 48 * 1024).all()
+        stride = (Q + 5) | 1                                       # the image and, staged, per wave two words a lane for every four positions
+        assert (lds == (chunk * stride + skew * 4 * 2 * (chunk // 4) * 64) * 4).all()
+        for units, length in ((units0, lmax + 0 * Q + 0 * skew), (units1, lmax // 2 + 0 * Q + 0 * skew)):
+            assert (units * chunk >= length).all() and ((units - 1) * chunk < length).all()
+        assert (slab == 1024).all()
+        slabs = max(-(-n_pairs // 1024), 1)
+        assert (groups >= 1).all() and (groups <= (units0 + units1) * slabs).all()
+    # the options replace the three choices
+    one = np.zeros(6, np.uint32)
+    trial_lib.stats_trial_geometry(151, 150, 151, 42, 1, 38, 256, 5000, 0, 0, 0, one.ctypes.data)
+    assert one.tolist()[:4] == [52, 1024, 3, 3]                    # (three chunks of 52, not 64 + 64 + 22)
+    trial_lib.stats_trial_geometry(151, 150, 151, 42, 1, 38, 256, 5000, 7, 100, 9, one.ctypes.data)
+    assert one.tolist() == [8, 100, 19, 19, (8 * 47 + 4 * 2 * 2 * 64) * 4, 9]
 
 
 # ------------------------------------------------------------------------------------------------ the mates
